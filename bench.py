@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the PNEConvLayerRotEquiv hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--precision bf16x3|fp32]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--precision bf16x3|fp32] [--full] [--dump-outputs DIR]
 
 N > 1: one rank per GPU.  Under ``torch.distributed.run`` (RANK / WORLD_SIZE in the environment) this process is
 a rank; started plainly it first launches ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a
@@ -16,10 +16,17 @@ convolution per level of a grid-subsampled hierarchy (cell doubling, radius = 2 
 backward (dX, dA, dbeta, dW) of all four levels, neighbourhoods prebuilt ("conv-only").
 value = level-0 points of all ranks / step time.  Other workloads: se3conv3d_amd/workloads.py.
 
-The JSON line also carries (N = 1 only): the single full-resolution layer, the same stack in exact-fp32 arithmetic
-and launched eagerly, the end-to-end step with per-step neighbourhoods, ``roofline`` of the dominant kernel on
-SURVEY section 8d's algorithmic bytes (HIP events inside the library, on the launch stream; intermediates only
-show up in ``traffic``), ``layer_frac`` / ``stack_frac``, and ``cpu_baseline`` (the oracle on this box's host cores).
+A plain run sets up, warms up, times the K steps and prints the JSON line.  With ``--full`` the line also carries
+(N = 1 only): the single full-resolution layer, the same stack in exact-fp32 arithmetic and launched eagerly, the
+end-to-end step with per-step neighbourhoods, ``roofline`` of the dominant kernel on SURVEY section 8d's algorithmic
+bytes (HIP events inside the library, on the launch stream; intermediates only show up in ``traffic``),
+``layer_frac`` / ``stack_frac``, and ``cpu_baseline`` (the oracle on this box's host cores); at any N, one checksum
+of the level-0 output per scene, gathered from every rank.
+
+``--dump-outputs DIR`` writes what the last timed step computed on rank 0 -- per level the convolution's output and the
+gradients of its input features and parameters -- as DIR/<name>.npy in float32, at most DUMP_BYTES in all: arrays that
+do not fit whole keep a fixed, seeded sample of their rows.  The inputs are seeded, so two builds can be compared output
+for output.
 """
 import argparse
 import ctypes as C
@@ -42,6 +49,7 @@ METRIC = "Mpoints/sec fwd+bwd PNEConvLayerRotEquiv (N=64k,k=32,F=2)"
 PEAK_MFMA_TFLOPS = {"fp32": 157.3, "bf16x3": 2500.0, "bf16x3_t16": 2500.0}
 PEAK_HBM_GBPS = 8000.0          # HBM3E spec
 TRAFFIC_JSON = os.path.join(ROOT, "profiles", "r06_traffic.json")
+DUMP_BYTES = 48 << 20           # --dump-outputs: float32 payload of all files together
 
 
 def library_source_sha() -> str:
@@ -102,6 +110,39 @@ def step(levels):
             p.grad = None
         out = lv["conv"](p_pc_in=lv["pc"], p_pc_out=lv["pc"], p_in_features=lv["x"], p_neighborhood=lv["nbh"])
         out.backward(lv["g"])
+        lv["out"] = out.detach()  # (a captured step's output buffer: every replay refreshes it, --dump-outputs reads it)
+
+
+def step_outputs(levels):
+    """What a caller of `step` receives, per level: the convolution's output and the gradients of its input features
+    and of its parameters."""
+    arrays = {}
+    for i, lv in enumerate(levels):
+        arrays[f"level{i}_out"] = lv["out"]
+        arrays[f"level{i}_grad_x"] = lv["x"].grad
+        for name, p in lv["conv"].named_parameters():
+            arrays[f"level{i}_grad_{name.rstrip('_')}"] = p.grad
+    return arrays
+
+
+def dump_outputs(directory, arrays):
+    """arrays (name -> tensor) as directory/<name>.npy in float32, DUMP_BYTES in all.  The budget is shared out smallest
+    array first; an array that does not fit whole keeps a sample of its rows drawn from a fixed seed (the same rows in
+    every run of the same shape), in ascending order."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    left = DUMP_BYTES // 4
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        t = t.detach().float()
+        share = left // (len(todo) - i)
+        if t.numel() > share:
+            per_row = t[0].numel() if t.dim() > 1 else 1
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[: share // per_row]
+            t = t[rows.sort().values.to(t.device)]
+        left -= t.numel()
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
 
 
 class GraphedStep:
@@ -414,8 +455,10 @@ def run_rank(args):
                    "launch": launch, "cpu_threads_per_rank": cpu_threads,
                    "sharding": "one scene per rank, no data-path collective" + (" (REHEARSAL: ranks share GPUs)" if args.share_gpu else "")},
     }
+    if args.dump_outputs and rank == 0:  # before any other leg runs the stack's convolutions again
+        dump_outputs(args.dump_outputs, step_outputs(levels))
 
-    if world == 1:
+    if world == 1 and args.full:
         lv0 = levels[0]
         mark("single layer / eager / stages")
         result["timing"]["hip_events"] = timed_events(run_stack, max(args.steps, 50))
@@ -858,24 +901,25 @@ def run_rank(args):
             finally:
                 amd.set_precision(args.precision)
 
-    mark("result gather")
-    # the "trivial result gather": one checksum of the level-0 output per scene.  A fixed-size record per rank, so it
-    # travels as one tensor all-gather (RCCL over xGMI; gloo in the rehearsal) rather than through pickled objects.
-    with torch.no_grad():
-        lv = levels[0]
-        out0 = lv["conv"](p_pc_in=lv["pc"], p_pc_out=lv["pc"], p_in_features=lv["x"], p_neighborhood=lv["nbh"])
-        rec = torch.stack((torch.tensor(float(my_scenes[0]), dtype=torch.float64, device=device), out0.double().sum()))
-        if dist is not None:
-            rec = rec.to(reduce_device)
-            parts = [torch.empty_like(rec) for _ in range(world)]
-            dist.all_gather(parts, rec)
-        else:
-            parts = [rec]
-        sums = {int(p[0].item()): float(p[1].item()) for p in parts}
-    if rank == 0:
-        assert sorted(sums) == list(range(world)), "every scene exactly once"
-        result["scene_checksums"] = {str(k): round(float(v), 6) for k, v in sorted(sums.items())}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        mark("result gather")
+        # the "trivial result gather": one checksum of the level-0 output per scene.  A fixed-size record per rank, so it
+        # travels as one tensor all-gather (RCCL over xGMI; gloo in the rehearsal) rather than through pickled objects.
+        with torch.no_grad():
+            lv = levels[0]
+            out0 = lv["conv"](p_pc_in=lv["pc"], p_pc_out=lv["pc"], p_in_features=lv["x"], p_neighborhood=lv["nbh"])
+            rec = torch.stack((torch.tensor(float(my_scenes[0]), dtype=torch.float64, device=device), out0.double().sum()))
+            if dist is not None:
+                rec = rec.to(reduce_device)
+                parts = [torch.empty_like(rec) for _ in range(world)]
+                dist.all_gather(parts, rec)
+            else:
+                parts = [rec]
+            sums = {int(p[0].item()): float(p[1].item()) for p in parts}
+        if rank == 0:
+            assert sorted(sums) == list(range(world)), "every scene exactly once"
+            result["scene_checksums"] = {str(k): round(float(v), 6) for k, v in sorted(sums.items())}
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -892,6 +936,11 @@ def main(argv=None):
     ap.add_argument("--workload", default="headline", choices=["headline", "scannet150k_f1", "dfaust_f2", "dfaust_f4"])
     ap.add_argument("--point-order", default="random", choices=["random", "morton"],
                     help="row order of the synthetic points: as drawn, or sorted along a Z-order curve per scene")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the other legs, stage times, roofline, result gather and CPU baseline "
+                         "(the --no-* switches below act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; see the module docstring)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fp32", action="store_true", help="skip the exact-fp32 leg")
     ap.add_argument("--no-extra", action="store_true", help="A/B runs: only the stack, the single layer and its stage times (no forward_only / "

@@ -78,3 +78,28 @@ def test_workloads_match_the_baseline_configurations():
     own = W.stage_owned_bytes(n, e, 2, 64)
     assert sum(own.values()) == W.layer_bytes(n, e, 2, 64) == 3304053280
     assert own["edge_param_grad"] == 1076491152
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files, DUMP_BYTES in all; arrays that fit are written whole, a larger one as a sample of
+    its rows that is the same in every run."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 4000)
+    arrays = {"big": torch.arange(3000 * 8, dtype=torch.float64).reshape(3000, 8), "vec": torch.arange(5.0),
+              "mat": torch.ones(3, 4)}
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), arrays)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.size for v in got.values()) <= 4000
+    np.testing.assert_array_equal(got["vec"], arrays["vec"].numpy())
+    np.testing.assert_array_equal(got["mat"], arrays["mat"].numpy())
+    rows = got["big"][:, 0].astype(np.int64) // 8
+    assert 0 < len(rows) < 3000 and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(got["big"], arrays["big"].numpy()[rows])
+    np.testing.assert_array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))

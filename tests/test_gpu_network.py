@@ -146,7 +146,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal(workload):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline", "--workload", workload],
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--workload", workload],
                        capture_output=True, text=True, timeout=550, env=env, cwd=root)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -176,7 +176,7 @@ def test_bench_rccl_path_with_one_rank():
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                SE3_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-fp32"], capture_output=True, text=True, timeout=550, env=env, cwd=root)
+                        "--full", "--no-cpu-baseline", "--no-fp32"], capture_output=True, text=True, timeout=550, env=env, cwd=root)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
     rec = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 1 and rec["value"] > 0 and list(rec["scene_checksums"]) == ["0"]
@@ -185,3 +185,47 @@ def test_bench_rccl_path_with_one_rank():
     # next to the communicator too: in round 4 they faulted there -- memset nodes of rocPRIM's one-sweep sort
     legs = rec["down_up"]["headline"]
     assert {legs["down"]["launch"], legs["up"]["launch"]} == {"hipGraph replay"}, legs
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_the_timed_outputs(built_library, tmp_path):
+    """A plain `bench.py` run: the headline keys only (no leg of --full), `--steps` timed steps, and `--dump-outputs`
+    writes what the step computed -- float32 files inside the size budget, the arrays that fit whole equal to the same
+    seeded stack computed again in this process."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    import bench
+    import se3conv3d_amd as amd
+    from conftest import rel_err
+    from se3conv3d_amd import workloads as W
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=550, env=env, cwd=root)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
+    rec = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["higher_is_better"] is True
+    assert rec["unit"] == "Mpoints/s" and rec["dtype"].startswith("bf16x3")
+    assert not {"roofline", "single_layer", "cpu_baseline", "scene_checksums", "fp32_mode"} & set(rec)
+
+    files = sorted(os.listdir(tmp_path))
+    assert len(files) == 4 * 5 and sum(os.path.getsize(tmp_path / f) for f in files) <= 64 * 10 ** 6
+    amd.set_precision("bf16x3")
+    levels = W.build_stack(W.WORKLOADS["headline"], torch.device(DEV), seed=0)
+    bench.step(levels)
+    whole = 0
+    for name, t in bench.step_outputs(levels).items():
+        got = np.load(tmp_path / (name + ".npy"))
+        assert got.dtype == np.float32 and np.isfinite(got).all(), name
+        if got.shape == tuple(t.shape):
+            whole += 1
+            assert rel_err(torch.from_numpy(got), t) < 1e-5, name
+        else:  # a seeded sample of the rows
+            assert got.shape[1:] == tuple(t.shape[1:]) and 0 < got.shape[0] < t.shape[0], name
+    assert whole >= 4 * 3  # at least every parameter gradient is written whole

@@ -1,8 +1,8 @@
 #!/bin/bash
-# One A/B harness for every switch of the library (run on the GPU box through gpurun), replacing the ab_*.sh /
+# One A/B harness for every switch of the library (run on the GPU box), replacing the ab_*.sh /
 # ablate*.sh / variants_*.sh family:
 #
-#   tools/ab.sh <outdir> [--reps N] [--levels] [--bench-args "<args>"] <variant> [<variant> ...]
+#   tools/ab.sh <name> [--reps N] [--levels] [--bench-args "<args>"] <variant> [<variant> ...]
 #
 # A variant is "-" (the shipped library, default environment), "lib:<suffix>" (a variant build
 # lib/libse3conv_hip<suffix>.so made beforehand with SE3_LIB_SUFFIX=<suffix> SE3_CXXFLAGS="-D..." python -m
@@ -11,7 +11,7 @@
 # and drift effects cancel.  One line per run: ms per step, single-layer ms, every stage time of the full-resolution
 # layer; with --levels the graph-replay time of every level of the stack instead (tools/profile_levels.py).
 set -u
-out=gpurun_out/$1; shift
+out=${SE3_OUT_DIR:-out}/$1; shift
 reps=3; levels=0; bargs="--no-cpu-baseline --no-extra --steps 30"
 while [ $# -gt 0 ]; do
   case "$1" in
@@ -37,7 +37,7 @@ for v in "$@"; do
   if [ $levels = 1 ]; then
     echo "[$v]: $(env $e timeout -k 10 200 python tools/profile_levels.py 2>/dev/null | grep 'graph replay' | sed 's/.*n *\([0-9]*\) rows.*graph replay \([0-9.]*\) ms.*/\1:\2/' | tr '\n' ' ')"
   else
-    echo "[$v]: $(env $e timeout -k 10 200 python bench.py $bargs 2>&1 | line)"
+    echo "[$v]: $(env $e timeout -k 10 200 python bench.py --full $bargs 2>&1 | line)"
   fi
 done
 done | tee $out/ab.log

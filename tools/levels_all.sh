@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-level stage times of every workload (SE3_OVERLAP_ROWS=0: branches back to back, so stage events are clean)
 set -u
-out=gpurun_out/${1:-levels}
+out=${SE3_OUT_DIR:-out}/${1:-levels}
 mkdir -p $out
 for w in headline dfaust_f2 dfaust_f4 scannet150k_f1; do
   echo "== $w" | tee -a $out/levels.txt

@@ -1,10 +1,10 @@
 #!/bin/bash
-# rocprofv3 counter passes for tools/profile_layer.py (run on the GPU box through gpurun).
+# rocprofv3 counter passes for tools/profile_layer.py (run on the GPU box; output: ${SE3_OUT_DIR:-out}/pmc_<tag>).
 # usage: tools/pmc_passes.sh <tag> [extra args for profile_layer.py]
 set -u
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-out=gpurun_out/pmc_$tag
+out=${SE3_OUT_DIR:-out}/pmc_$tag
 mkdir -p $out
 run() { # name, counters...
   local name=$1; shift

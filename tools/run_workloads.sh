@@ -1,10 +1,10 @@
 #!/bin/bash
 # bench.py on every workload of se3conv3d_amd/workloads.py (1 GPU): one summary line each.
 set -u
-out=gpurun_out/${1:-workloads}
+out=${SE3_OUT_DIR:-out}/${1:-workloads}
 mkdir -p $out
 for w in headline scannet150k_f1 dfaust_f2 dfaust_f4; do
-  timeout -k 10 400 python bench.py --workload $w --no-cpu-baseline --steps 20 --warmup 5 > $out/$w.json 2> $out/$w.err
+  timeout -k 10 400 python bench.py --full --workload $w --no-cpu-baseline --steps 20 --warmup 5 > $out/$w.json 2> $out/$w.err
   echo "[$w] rc=$? $(python -c "
 import json,sys
 try:

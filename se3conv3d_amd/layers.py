@@ -112,6 +112,7 @@ def _geometry_of(p_pc_in, p_pc_out, p_neighborhood) -> ops.ConvGeometry:
     key = (id(p_pc_in), id(p_pc_out), nb32.data_ptr(), p_pc_in.local_frames_.data_ptr(),
            p_pc_out.local_frames_.data_ptr(), p_pc_in.pts_.data_ptr(), p_pc_out.pts_.data_ptr())
     if cache is not None and cache[0] == key:
+        _refresh_copies(cache[1], cache[2])
         return cache[1]
     geom = ops.ConvGeometry.build(p_pc_in.pts_, p_pc_out.pts_, p_pc_in.local_frames_, p_pc_out.local_frames_,
                                   nb32, p_neighborhood.start_ids_,
@@ -124,11 +125,30 @@ def _geometry_of(p_pc_in, p_pc_out, p_neighborhood) -> ops.ConvGeometry:
     # the clouds' packed geometry records: built once per cloud by whichever call meets them first, shared by every other
     geom.records_in = ops.prepared_records(p_pc_in)
     geom.records_out = geom.records_in if p_pc_out is p_pc_in else ops.prepared_records(p_pc_out)
+    sources = ((p_pc_in.pts_, geom.pts_in), (p_pc_out.pts_, geom.pts_out), (p_pc_in.local_frames_, geom.frames_in),
+               (p_pc_out.local_frames_, geom.frames_out))
+    # the tensors the geometry holds as converted COPIES (float64 points, non-contiguous frames, ...), with the version of
+    # the cloud's tensor they were made from: an in-place update of the cloud must reach them
+    copies = [[src, held, src._version] for src, held in sources if held.data_ptr() != src.data_ptr()]
     try:
-        p_neighborhood._se3_geom = (key, geom)
+        p_neighborhood._se3_geom = (key, geom, copies)
     except AttributeError:
         pass
     return geom
+
+
+def _refresh_copies(geom: ops.ConvGeometry, copies) -> None:
+    """Converts again, in place, what the cached geometry holds as a copy of a cloud tensor that has changed since (and,
+    inside a HIP graph capture, every such copy: a replay must convert what the cloud holds then).  The copy's own version
+    moves with it, so the records bound to it are rebuilt too."""
+    if not copies:
+        return
+    capturing = geom.pts_out.is_cuda and torch.cuda.is_current_stream_capturing()
+    for entry in copies:
+        src, held, version = entry
+        if capturing or src._version != version:
+            held.copy_(src.detach().reshape(held.shape))
+            entry[2] = src._version
 
 
 _ACTIVATIONS = {"mlp_gelu": torch.nn.functional.gelu, "mlp_relu": torch.relu, "mlp_sin": torch.sin, "mlp_linear": (lambda t: t),

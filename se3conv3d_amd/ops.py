@@ -228,22 +228,34 @@ class SourceGrids:
         self.grids = {}
         self.params = {}  # per radius: (shifted box minima, cell counts) of the grid (se3_ball_query_grid_from_box)
 
-    def slot(self, pts, batch_ids, radius, n_batches, nbytes):
-        """``(buffer, valid)`` for this radius; ``valid`` says the buffer already holds the grid (the call that gets
-        ``False`` builds it)."""
-        key = (pts.data_ptr(), pts._version, batch_ids.data_ptr(), batch_ids._version, int(pts.shape[0]), int(n_batches or 0),
-               str(pts.device))
+    @staticmethod
+    def key(pts, batch_ids, n_batches):
+        """What a grid is valid for: the cloud's OWN points and batch ids (storage and version), not converted copies -- a
+        temporary's address says nothing about the cloud and may be recycled by the next temporary."""
+        return (pts.data_ptr(), pts._version, batch_ids.data_ptr(), batch_ids._version, int(pts.shape[0]),
+                int(n_batches or 0), str(pts.device))
+
+    def slot(self, key, radius, nbytes, device):
+        """``(buffer, valid)`` for this radius; ``valid`` says the buffer already holds the grid of ``key``.  A buffer
+        handed out with ``False`` is the caller's to build the grid in: it is kept only once ``commit`` says the build has
+        been enqueued (a call that fails in between leaves no entry that claims a grid)."""
         hit = self.grids.get(float(radius))
         if hit is not None and hit[0] == key and hit[1].numel() >= nbytes:
             return hit[1], True
-        if len(self.grids) >= 8:  # (a cloud is searched with two or three radii; a sweep over many drops the oldest)
+        self.grids.pop(float(radius), None)
+        self.params.pop(float(radius), None)
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=device), False
+
+    def commit(self, key, radius, buf, params):
+        """Keep ``buf`` as the grid of ``key`` for this radius, with its grid parameters: after the library call that
+        builds it has returned."""
+        if len(self.grids) >= 8 and float(radius) not in self.grids:
+            # (a cloud is searched with two or three radii; a sweep over many drops the oldest)
             oldest = next(iter(self.grids))
             self.grids.pop(oldest)
             self.params.pop(oldest, None)
-        buf = torch.empty(int(nbytes), dtype=torch.uint8, device=pts.device)
         self.grids[float(radius)] = (key, buf)
-        self.params.pop(float(radius), None)
-        return buf, False
+        self.params[float(radius)] = params
 
 
 def source_grids(cloud) -> Optional["SourceGrids"]:
@@ -281,6 +293,7 @@ def ball_query_bounded(pts_src, pts_dst, batch_src, batch_dst, radius: float, ca
     ``grids``: the source cloud's ``SourceGrids`` -- its cell grid for this radius is then built once and shared by every
     query that passes the holder (not while a HIP graph is being captured: a replay must not depend on what ran before)."""
     lib = _lib.load()
+    src_own, batch_own = pts_src, batch_src  # (what a source grid is keyed on: the caller's tensors, not their conversions)
     pts_src = _as(pts_src, torch.float32)
     pts_dst = _as(pts_dst, torch.float32)
     if pts_src.dim() != 2 or pts_src.shape[1] != 3 or pts_dst.dim() != 2 or pts_dst.shape[1] != 3:
@@ -308,10 +321,11 @@ def ball_query_bounded(pts_src, pts_dst, batch_src, batch_dst, radius: float, ca
     if grids is not None and needs_grid and src_box is not None and SHARED_GRIDS and not torch.cuda.is_current_stream_capturing():
         # (src_box: the grid parameters are then a pure function of the cloud's cached boxes and the radius, so two calls
         # with the same key search the same cells -- and the parameters themselves are kept with the grid)
-        grid, valid = grids.slot(pts_src, bs, radius, n_batches, grid_bytes)
+        key = SourceGrids.key(src_own, batch_own, n_batches)
+        grid, valid = grids.slot(key, radius, grid_bytes, dev)
         params = grids.params.get(float(radius)) if valid else None
         if params is None:
-            params = grids.params[float(radius)] = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box)
+            valid, params = False, _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box)
         mn, nc = params
         _lib.check(lib.se3_ball_query_bounded_shared(
             _ptr(pts_src, f32, "pts_src"), _ptr(pts_dst, f32, "pts_dst", dev), _ptr(bs, i32, "batch_src", dev),
@@ -319,6 +333,8 @@ def ball_query_bounded(pts_src, pts_dst, batch_src, batch_dst, radius: float, ca
             n_dst, int(n_batches or 0), C.c_void_p(grid.data_ptr()), grid.numel(), int(valid), C.c_void_p(ws.data_ptr()),
             ws.numel(), int(capacity), _ptr(neighbors, i32, "neighbors"), _ptr(sources, i32, "sources"), _ptr(ends, i32, "ends"),
             _ptr(info, i32, "info"), _stream(dev)), "se3_ball_query_bounded_shared")
+        if not valid:
+            grids.commit(key, radius, grid, params)
         return (neighbors, ends, info, sources) if want_sources else (neighbors, ends, info)
     mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if needs_grid else (None, None)
     _lib.check(lib.se3_ball_query_bounded(
@@ -714,12 +730,14 @@ class PreparedRecords:
     """The packed 64-byte geometry records of one cloud (include/se3conv.h, struct se3conv_prepared): a function of the
     cloud's points and frames alone, so every convolution that touches the cloud -- forward and backward, every layer of a
     level -- shares one image.  The first call that meets an invalid holder fills it inside its own preparation launch.
-    Kept on the cloud object (``prepared_records``); re-validated against the tensors' storage and version counters."""
+    Kept on the cloud object (``prepared_records``); re-validated against the tensors' storage and version counters.
+    ``valid`` is for eager calls; inside a HIP graph capture the records count as filled only when a call of the SAME
+    capture filled them (``capture``: its id), and such a fill is not one for eager calls (it runs at replay)."""
 
-    __slots__ = ("tensor", "valid", "key")
+    __slots__ = ("tensor", "valid", "key", "capture")
 
     def __init__(self):
-        self.tensor, self.valid, self.key = None, False, None
+        self.tensor, self.valid, self.key, self.capture = None, False, None, None
 
     def bind(self, pts: torch.Tensor, frames: torch.Tensor) -> "PreparedRecords":
         key = (pts.data_ptr(), pts._version, frames.data_ptr(), frames._version, tuple(frames.shape), str(pts.device))
@@ -727,8 +745,18 @@ class PreparedRecords:
             rows = frames.shape[0] * frames.shape[1]
             if self.tensor is None or self.tensor.shape[0] != rows or self.tensor.device != pts.device:
                 self.tensor = torch.empty((rows, 16), dtype=torch.float32, device=pts.device)
-            self.key, self.valid = key, False
+            self.key, self.valid, self.capture = key, False, None
         return self
+
+    def filled_for(self, capture: Optional[int]) -> bool:
+        """Whether a call made outside a capture (``capture`` None) or inside capture ``capture`` may read the records."""
+        return self.valid if capture is None else self.capture == capture
+
+    def mark_filled(self, capture: Optional[int]) -> None:
+        if capture is None:
+            self.valid = True
+        else:
+            self.valid, self.capture = False, capture
 
 
 def prepared_records(cloud) -> Optional["PreparedRecords"]:
@@ -749,7 +777,31 @@ def invalidate_prepared(cloud) -> None:
     does implicitly by building new cloud objects; a benchmark that re-uses its clouds calls this once per step."""
     holder = getattr(cloud, "_se3_records_", None)
     if holder is not None:
-        holder.valid = False
+        holder.valid, holder.capture = False, None
+
+
+@functools.lru_cache(maxsize=1)
+def _hip_get_capture_info():
+    fn = C.CDLL("libamdhip64.so").hipStreamGetCaptureInfo  # the runtime torch has already loaded
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]
+    fn.restype = C.c_int
+    return fn
+
+
+def _stream_capture_id(device) -> int:
+    """Id of the capture sequence the current stream of ``device`` belongs to (``hipStreamGetCaptureInfo``)."""
+    status, cid = C.c_int(0), C.c_ulonglong(0)
+    err = _hip_get_capture_info()(_stream(device), C.byref(status), C.byref(cid))
+    if err != 0 or status.value != 1:  # hipStreamCaptureStatusActive
+        raise RuntimeError(f"hipStreamGetCaptureInfo: error {err}, capture status {status.value} on a capturing stream")
+    return int(cid.value)
+
+
+def _capture_id(device) -> Optional[int]:
+    """None outside a HIP graph capture; the capture's id while the current stream of ``device`` is being captured."""
+    if device.type != "cuda" or not torch.cuda.is_current_stream_capturing():
+        return None
+    return _stream_capture_id(device)
 
 
 @dataclass
@@ -824,26 +876,37 @@ def _geom_ptrs(g: ConvGeometry):
             _ptr(g.neighbors, i32, "neighbors", dev), _ptr(g.ends, i32, "ends", dev)]
 
 
+def _same_cloud(g: ConvGeometry) -> bool:
+    """The library's own test (api.hip, ``same_cloud``): one set of records serves both sides and ``geom_out`` is not
+    written -- whichever cloud objects, and hence holders, the two sides came from."""
+    return (g.pts_in.data_ptr() == g.pts_out.data_ptr() and g.frames_in.data_ptr() == g.frames_out.data_ptr()
+            and g.pts_in.shape[0] == g.pts_out.shape[0] and g.frames_in.shape[1] == g.frames_out.shape[1])
+
+
 def _prepared(geom: ConvGeometry, feat_words: Optional[torch.Tensor], feat_words_valid: bool):
-    """struct se3conv_prepared of a call (or None) + what to mark valid once the call has been enqueued."""
+    """struct se3conv_prepared of a call (or None), the holders the call fills, and the capture it is enqueued in (None
+    outside one): once the call has been enqueued, ``h.mark_filled(capture)`` for each holder."""
     r_in, r_out = geom.records_in, geom.records_out
     if r_in is None and r_out is None and feat_words is None:
-        return None, ()
+        return None, (), None
     p = _lib.Se3Prepared()
     filled = []
+    capture = _capture_id(geom.pts_out.device) if (r_in is not None or r_out is not None) else None
+    if _same_cloud(geom):
+        r_out = None  # (the library reads the in-side records for both sides and never writes geom_out)
     if r_in is not None:
         r_in.bind(geom.pts_in, geom.frames_in)
-        p.geom_in, p.geom_in_valid = r_in.tensor.data_ptr(), int(r_in.valid)
+        p.geom_in, p.geom_in_valid = r_in.tensor.data_ptr(), int(r_in.filled_for(capture))
         filled.append(r_in)
     if r_out is not None and r_out is not r_in:
         r_out.bind(geom.pts_out, geom.frames_out)
-        p.geom_out, p.geom_out_valid = r_out.tensor.data_ptr(), int(r_out.valid)
+        p.geom_out, p.geom_out_valid = r_out.tensor.data_ptr(), int(r_out.filled_for(capture))
         filled.append(r_out)
     elif r_out is r_in and r_in is not None:
         p.geom_out, p.geom_out_valid = p.geom_in, 1  # (ignored for a cloud against itself; valid by the time it is read otherwise)
     if feat_words is not None:
         p.feat_words, p.feat_words_valid = feat_words.data_ptr(), int(feat_words_valid)
-    return p, tuple(filled)
+    return p, tuple(filled), capture
 
 
 def _scalar(t, name, dev) -> torch.Tensor:
@@ -875,7 +938,7 @@ def se3conv_forward(geom: ConvGeometry, feat, proj_axes, proj_biases, conv_weigh
     t_save = torch.empty((rows, c_in, kb), dtype=f32, device=dev) if (save_t and kb == 32) else None
     ws = _workspace(lib.se3conv_fwd_workspace_bytes(C.byref(shp), 1 if save_t else 0), dev)
     rho_t, nu_t = _scalar(rho, "rho", dev), _scalar(nu, "nu", dev)
-    prep, filled = _prepared(geom, feat_words, False)
+    prep, filled, capture = _prepared(geom, feat_words, False)
     _lib.check(lib.se3conv_fwd_prepared(*_geom_ptrs(geom), _ptr(feat, f32, "features", dev), _ptr(a, f32, "proj_axes_", dev),
                                         _ptr(b, f32, "proj_biases_", dev), _ptr(w, f32, "conv_weights_", dev),
                                         _ptr(rho_t, f32, "norm_neigh_dist_"), _ptr(nu_t, f32, "norm_num_neighs_"),
@@ -883,7 +946,7 @@ def se3conv_forward(geom: ConvGeometry, feat, proj_axes, proj_biases, conv_weigh
                                         C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev),
                                         C.byref(prep) if prep is not None else None), "se3conv_fwd")
     for h in filled:
-        h.valid = True
+        h.mark_filled(capture)
     return out, t_save
 
 
@@ -908,7 +971,7 @@ def se3conv_backward(geom: ConvGeometry, feat, proj_axes, proj_biases, conv_weig
     ws = _workspace(lib.se3conv_bwd_workspace_bytes(C.byref(shp), int(want_feat), int(want_params),
                                                     int(t_save is not None)), dev)
     rho_t, nu_t = _scalar(rho, "rho", dev), _scalar(nu, "nu", dev)
-    prep, filled = _prepared(geom, feat_words, feat_words is not None)
+    prep, filled, capture = _prepared(geom, feat_words, feat_words is not None)
     _lib.check(lib.se3conv_bwd_prepared(*_geom_ptrs(geom), _ptr(t_samples, i32, "t_samples"), _ptr(t_ends, i32, "t_ends"),
                                         _ptr(geom._edge_ids if want_feat else None, i32, "t_edge_ids"),
                                         _ptr(feat, f32, "features", dev), _ptr(a, f32, "proj_axes_", dev),
@@ -919,7 +982,7 @@ def se3conv_backward(geom: ConvGeometry, feat, proj_axes, proj_biases, conv_weig
                                         _ptr(d_w, f32, "grad_weights"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev),
                                         C.byref(prep) if prep is not None else None), "se3conv_bwd")
     for h in filled:
-        h.valid = True
+        h.mark_filled(capture)
     return d_x, d_a, d_b, d_w
 
 

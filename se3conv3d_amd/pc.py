@@ -116,7 +116,8 @@ class Pointcloud(object):
         """Per-batch bounding boxes ``(min, max) [B,3]`` of the points, computed once per cloud (the reference recomputes
         them in every ball query, BallQuery.py:35-36; a cloud is the source of three or four queries per step)."""
         box = getattr(self, "_se3_aabb", None)
-        key = (self.pts_.data_ptr(), self.pts_._version)  # (points replaced or changed in place: new boxes)
+        # (points or batch ids replaced or changed in place: new boxes)
+        key = (self.pts_.data_ptr(), self.pts_._version, self.batch_ids_.data_ptr(), self.batch_ids_._version)
         if box is None or box[2] != key:
             mn, mx = ops.batch_aabb(self.pts_, self.batch_ids_, self.num_batches())
             box = (mn, mx, key)
@@ -205,13 +206,17 @@ class PointcloudRotEquiv(Pointcloud):
 
     def _self_knn_ids(self, k):
         """``[N, k]`` int32 ids of the cloud's self-k-NN (``ops.knn_query``), memoised per k; what KnnNeighborhood builds
-        its lists from."""
+        its lists from.  Not while a HIP graph is being captured: a table cached before would be baked into the graph, one
+        cached during the capture holds nothing until the first replay."""
+        grid = self.pts_.shape[0] >= ops.KNN_GRID_MIN_POINTS and k <= 32
+        query = lambda: ops.knn_query(self.pts_, self.batch_ids_, int(k), self.num_batches(), box=self.aabb() if grid else None)
+        if self.pts_.is_cuda and torch.cuda.is_current_stream_capturing():
+            return query()
         cache = self.__dict__.setdefault("_se3_knn_ids", {})
         key = (int(k), self.pts_.data_ptr(), self.pts_._version)
         if key not in cache:
-            grid = self.pts_.shape[0] >= ops.KNN_GRID_MIN_POINTS and k <= 32
             cache.clear()
-            cache[key] = ops.knn_query(self.pts_, self.batch_ids_, int(k), self.num_batches(), box=self.aabb() if grid else None)
+            cache[key] = query()
         return cache[key]
 
     @classmethod

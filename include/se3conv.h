@@ -14,23 +14,10 @@
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default
  *     stream) of the CURRENT device -- the library never switches devices -- and makes no hidden
  *     host synchronisation;
- *   - re-entrant: calls on different streams (or from different threads) share no events, streams
- *     or buffers.  Process-wide state, all of it listed here: (1) the profiling switch below;
- *     (2) se3conv_bwd keeps one internal side stream + fork/join event pair per (device, caller
- *     stream) it has been called on, for running its two branches side by side -- OPT-IN since round 5
- *     (SE3_OVERLAP / SE3_OVERLAP_ROWS / se3_set_overlap_rows: with the kernels as they are the fork loses at every size,
- *     and a fork from a stream that is itself a forked branch of a graph capture crashes this HIP runtime's
- *     hipStreamEndCapture, see se3_set_overlap_rows) --
- *     the side stream is always joined back into `stream` before the call returns, on error paths too.
- *     These objects are only ever created by a call whose stream is NOT being captured into a HIP graph:
- *     every eager se3conv_fwd / se3conv_bwd keeps two spare sets per device ready, a capturing stream that
- *     is new to the library takes a spare, and if there is none (no eager call happened before the capture)
- *     the backward pass does not fork -- same results, branches back to back (counted: se3_side_stream_stats).  At most 16
- *     caller streams per device own a set at a time: past that the least recently used set goes back to the spares
- *     and serves the next new caller stream (never rearranged while a capture is involved), so a process that makes
- *     a stream per request does not grow the table; (3) kernel-variant switches read ONCE from the environment at first
- *     use (A/B knobs, none changes results beyond rounding): listed in the appendix at the end of this header.  A
- *     side-stream set in use by a call is pinned: the cap never hands it to another caller.
+ *   - re-entrant: calls on different streams (or from different threads) share no buffers.  The library creates no
+ *     stream and no event: every kernel of a call runs on `stream`, in one order per call.  Process-wide state, all of
+ *     it listed here: (1) the profiling switch below; (2) kernel-variant switches read ONCE from the environment at
+ *     first use (none changes results beyond rounding): listed in the appendix at the end of this header.
  *     `t_save` written by se3conv_fwd must be consumed by se3conv_bwd in the same process (same switches);
  *   - graph capture: every entry point that takes a stream can be captured into a HIP graph (no host synchronisation,
  *     nothing allocated) except the two-phase se3_ball_query_count / _store pair.  The library issues NO hipMemsetAsync
@@ -116,7 +103,9 @@ typedef struct se3conv_shape {
 /* 5 = round 6: se3conv_fwd_prepared / se3conv_bwd_prepared (operands prepared once per step and shared between calls:
  * struct se3conv_prepared) added; the version also covers round 5's two additions, so that a binding that needs them
  * and meets an older library fails with the "rebuild" message instead of a missing symbol. */
-#define SE3_ABI_VERSION 5
+/* 6: se3_side_stream_stats and se3_set_overlap_rows removed with the two-stream backward pass (se3conv_bwd
+ * runs on `stream` only). */
+#define SE3_ABI_VERSION 6
 int se3_abi_version(void);
 const char* se3_error_string(int code);
 /* Bytes per element of the row-sized intermediates [rows, C, K] the operator moves through memory for this shape --
@@ -526,20 +515,6 @@ int se3_linear_wgrad(const float* grad_y, const float* x, int64_t rows, int32_t 
  * Off by default.
  * ------------------------------------------------------------------------------------------- */
 int se3_profile_enable(int on);
-/* Introspection of process-wide state (2) above, for tests of the capture contract and as the diagnostic of a graph
- * that was captured without an eager step in front of it.  stats[5]: [0] caller streams that own an internal side
- * stream, [1] spare (stream, events) sets ready on the current device, [2] sets created so far in this process, [3]
- * backward passes that wanted to fork inside a capture and could not (no set prepared: that graph replays its two
- * branches back to back -- the same results; with the fork opt-in since round 5 that is also the default schedule), [4] sets the 16-owner cap handed back to the
- * spares.  Sets are only created by calls whose stream is NOT being captured. */
-int se3_side_stream_stats(int32_t* stats);
-/* Process-wide switch of state (2): se3conv_bwd runs its feature branch on the internal side stream for layers of at most
- * `rows` output rows (and more than 4096; every size from 2^40 on).  0 = never (the default since round 5), < 0 = back to the
- * environment (SE3_OVERLAP=1 / SE3_OVERLAP_ROWS=n, read once).  Measured on MI355X the fork costs 0.4 - 2.3 % of a step on
- * every workload (profiles/r05_no_fork_ab.txt).  Do NOT turn it on for calls made on a stream that is itself a forked
- * branch of a graph capture: a fork from a forked stream makes hipStreamEndCapture segfault on the HIP runtime PyTorch
- * 2.10+rocm7.0 ships (tools/probes/nested_fork_capture.py reproduces it with torch streams and events alone). */
-int se3_set_overlap_rows(int64_t rows);
 int se3_profile_reset(void);
 int se3_profile_read(const char* tag, double* total_ms, int64_t* launches);
 int se3_profile_tags(char* buf, size_t len);
@@ -550,24 +525,22 @@ int se3_profile_tags(char* buf, size_t len);
 #endif /* SE3CONV_H_ */
 
 /*
- * Appendix: environment switches (process-wide state (3) above).  Each is read once, at first use; none changes results
- * beyond rounding; each is exercised by tests/test_gpu_variants.py.  What every switch measured: profiles/README.md,
- * "Ledger of lost A/Bs".
+ * Appendix: environment switches (process-wide state (2) above).  Each is read once, at first use; none changes results
+ * beyond rounding; each is set by the tests (tests/test_gpu_variants.py and the tests named below), mostly to reach the
+ * default kernels' forms on small shapes.  What every switch measured: profiles/README.md, "Ledger of lost A/Bs".
  *   SE3_NO_T24            T and U as packed hi/lo words instead of 3-byte rows
- *   SE3_OVERLAP, SE3_OVERLAP_ROWS   two-stream backward pass (see se3_set_overlap_rows; opt-in since round 5)
- *   SE3_BWD_BRANCH_ORDER  backward kernels branch by branch instead of writers first
- *   SE3_NO_PAIR, SE3_FC1  single-wavefront edge kernel instead of the wave pair / one frame per wavefront
+ *   SE3_NO_PAIR           single-wavefront edge kernel instead of the wave pair
  *   SE3_EDGE_STREAM       chunk-stream forms of the edge kernel (round 6: 64-channel rows with two frames per item, 32-channel
  *                         rows with two frames per item): n > 0 = from n items up (default 4096, 1 = every size), 0 = never
  *   SE3_SHARED_GRIDS      (Python host side, se3conv3d_amd/ops.py) =0: every bounded ball query sorts its source cloud itself
  *                         instead of sharing the grid per (cloud, radius) -- se3_ball_query_bounded_shared
- *   SE3_PG_SINGLE, SE3_PG_PAIR (+ _WGS, _C32)   forms of the parameter-gradient kernel
- *   SE3_NN_SPLITS         split-K count of the dense products (default: cost model)
- *   SE3_NN_KG             =2: two k groups per workgroup in the dense products over 3-byte rows of under-filled levels
- *   SE3_T16_GT            SE3_PRECISION_BF16X3_T16 only: grad_T in the block format too
+ *   SE3_PG_SINGLE         one frame per wavefront in the parameter-gradient kernel, whatever the frame count
  *   SE3_TR_MERGE_SORT     se3_csr_transpose*: the merge-sort form for every graph, same result
  *   SE3_DX_PATH           feature gradient edge-major: 1 wherever implemented, 0 never; default: the two-term cost model of
  *                         DESIGN.md section 4.11 (microseconds of either form; never above 20 edges per source row)
  * (Removed in round 6 with their code: SE3_SLICE_MB / SE3_SLICE_STREAMS, the row-sliced schedule of round 5 that lost every
  *  A/B -- profiles/r05_slice_ab.txt; SE3_PAIR_PERSIST / SE3_PAIR_OCC.)
+ * (Removed since with their code: SE3_OVERLAP / SE3_OVERLAP_ROWS, the two-stream backward pass; SE3_BWD_BRANCH_ORDER;
+ *  SE3_NN_KG, SE3_T16_GT, SE3_PG_PAIR_LEAN -- kernel forms that lost their A/Bs; SE3_NN_SPLITS, SE3_PG_PAIR, SE3_PG_PAIR_C32,
+ *  SE3_PG_PAIR_WGS, SE3_FC1 -- overrides of a constant.)
  */

@@ -11,7 +11,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", f"libse3conv_hip{os.environ.get('SE3_LIB_SUFFIX', '')}.so")  # suffix: variant builds, see build.py
 
 SE3_OK = 0
-ABI_VERSION = 5  # SE3_ABI_VERSION of include/se3conv.h these signatures were written against
+ABI_VERSION = 6  # SE3_ABI_VERSION of include/se3conv.h these signatures were written against
 PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x3_t16": 2}
 REL_ROT = {"6D": (0, 9), "matrix": (1, 12), "quaternion": (2, 7)}  # p_rel_rot -> (SE3_REL_ROT_*, descriptor dims)
 
@@ -101,8 +101,6 @@ SIGNATURES = {
     "se3_bias_gelu_bwd": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _SZ, _P]),
     "se3_linear_wgrad_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
     "se3_linear_wgrad": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
-    "se3_side_stream_stats": (C.c_int, [_P]),
-    "se3_set_overlap_rows": (C.c_int, [C.c_int64]),
     "se3_profile_enable": (C.c_int, [C.c_int]),
     "se3_profile_reset": (C.c_int, []),
     "se3_profile_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

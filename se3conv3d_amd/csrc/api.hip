@@ -1,5 +1,4 @@
 // extern "C" entry points of the fused operator + the API-parity ops (see include/se3conv.h).
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -261,7 +260,7 @@ FwdLayout fwd_layout(const se3conv_shape* s, int save_t) {
 struct BwdLayout {
   size_t axes_ext, wt, w2, big, t, param_partials, tn_partials, featpk, gpk, bt_hi, bt_lo, split, geom_in, geom_out, total;
   size_t dx_rows;  // edge-major feature gradient (use_edge_dx): D [edge rows * F_in, C_in] fp32
-  size_t big_u, bt2_hi, bt2_lo, split2;  // feature-gradient branch when it runs beside the parameter branch
+  size_t big_u, bt2_hi, bt2_lo, split2;  // U and the grad_X partials when both branches run: grad_T takes `big` meanwhile
   int n_param_partials, tn_splits;
 };
 // The feature gradient of a convolution with many more input rows than edges per row can carry (a down-convolution)
@@ -305,8 +304,7 @@ bool use_edge_dx(const se3conv_shape* s, bool want_feat, bool want_params) {
 bool dw_from_u_available(const se3conv_shape* s, bool want_feat, bool want_params) {
   if (!want_feat || !want_params || s->precision == SE3_PRECISION_FP32 || s->num_basis != kBasis) return false;
   if (s->n_in == 0 || s->n_out == 0 || s->c_in % 4 != 0 || s->c_out % 2 != 0) return false;
-  static const bool branch_order = getenv("SE3_BWD_BRANCH_ORDER") != nullptr;  // that order overwrites U before the product would read it
-  return !branch_order && !use_edge_dx(s, true, true);
+  return !use_edge_dx(s, true, true);
 }
 bool use_u_for_dw(const se3conv_shape* s, bool want_feat, bool want_params, bool have_t) {
   if (!dw_from_u_available(s, want_feat, want_params)) return false;
@@ -374,212 +372,6 @@ BwdLayout bwd_layout(const se3conv_shape* s, int want_feat, int want_params, int
   l.total = off;
   return l;
 }
-
-// Second stream for the backward pass: the parameter branch (grad_T GEMM -> edge_param_grad, weight-gradient GEMM)
-// and the feature branch (transposed edge kernel -> grad_X GEMM) are independent.  OFF by default since round 5: measured
-// on MI355X with the kernels as they are now (writers first, non-temporal producer stores), the fork loses at every size --
-// headline stack 2.437 -> 2.405 ms without it (its 18 k-row level 0.341 -> 0.330), dfaust_f2 1.918 -> 1.873, dfaust_f4
-// 6.97 -> 6.93, scannet150k_f1 2.572 -> 2.561 (profiles/r05_no_fork_ab.txt; at 131 k rows it always lost: 2.15 vs 2.07 ms
-// in round 1).  It also keeps the library out of a hazard of this HIP runtime: a fork FROM A FORKED STREAM inside a graph
-// capture segfaults in hipStreamEndCapture (tools/probes/nested_fork_capture.py: torch streams and events alone do it), which
-// is what a caller who captures the library on a side stream of its own would have triggered.  SE3_OVERLAP=1 (every size) /
-// SE3_OVERLAP_ROWS=n / se3_set_overlap_rows(n) turn it on for levels of MORE than kOverlapMinRows and at most n output rows;
-// smaller levels fork only when the limit is 2^40 or more (what SE3_OVERLAP=1 sets: "every size") -- below ~4 k rows the fork
-// and join cost more than the branches overlap.
-constexpr int kOverlapRows = 0, kOverlapMinRows = 4096;
-std::atomic<int64_t> g_overlap_rows{-1};  // se3_set_overlap_rows: >= 0 overrides the environment
-int64_t overlap_rows_limit() {
-  const int64_t v = g_overlap_rows.load(std::memory_order_relaxed);
-  if (v >= 0) return v;
-  static const int64_t env = [] {
-    if (getenv("SE3_OVERLAP") != nullptr) return (int64_t)1 << 62;
-    const char* e = getenv("SE3_OVERLAP_ROWS");
-    return e ? (int64_t)atoll(e) : (int64_t)kOverlapRows;
-  }();
-  return env;
-}
-// One side stream + fork / join event pair per (device, caller stream), kept for the life of the process: two backward
-// calls on two caller streams (or threads) never share events or a stream, and a caller stream on device 1 never gets a
-// side stream of device 0.  Two calls racing on the SAME caller stream are the caller's race anyway.  The table only
-// grows by the number of distinct streams the caller uses.
-// Nothing is CREATED while the caller's stream is being captured into a HIP graph (creating runtime objects in the middle
-// of a capture is what a capture should not have to survive): every eager call of se3conv_fwd / se3conv_bwd keeps a few
-// spare (stream, events) sets per device ready, a capturing caller stream that is new to the table takes one of those,
-// and when there is none -- the library was never called outside a capture in this process -- the backward pass simply
-// does not fork (same results, the two branches back to back).  INTEGRATION.md: warm up eagerly before capturing.
-struct SideStream {
-  hipStream_t stream = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-  bool ok = false;
-  uint64_t last_use = 0;  // SideTable::clock at the last fork (LRU order)
-  int pins = 0;           // calls between side_stream_for and release_side_stream on this set: never evicted while > 0
-};
-constexpr size_t kSpareSideStreams = 2;
-// At most this many caller streams own a side stream at a time.  A server that makes a stream per request would grow the
-// table without limit otherwise: beyond the cap the least recently used set goes back to the spares (the runtime objects
-// live on and are handed to the next new caller stream).  Never inside a capture -- neither when the caller's stream is
-// being captured (nothing is rearranged then) nor a set whose own stream is part of a capture in progress.
-constexpr size_t kMaxOwnedSideStreams = 16;
-struct SideTable {
-  std::mutex mu;
-  std::map<std::pair<int, hipStream_t>, SideStream> by_stream;
-  std::map<int, std::vector<SideStream>> spare;
-  uint64_t clock = 0;
-  int created = 0;             // (stream, events) sets made so far in this process
-  int unforked_in_capture = 0; // captured backward passes that wanted to fork and had no set to fork onto
-  int evicted = 0;             // sets taken back from a caller stream by the cap
-};
-SideTable& side_table() {
-  static SideTable t;
-  return t;
-}
-SideStream make_side_stream(SideTable& t) {  // t.mu held
-  SideStream v;
-  ++t.created;
-  v.ok = hipStreamCreateWithFlags(&v.stream, hipStreamNonBlocking) == hipSuccess &&
-         hipEventCreateWithFlags(&v.fork, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&v.join, hipEventDisableTiming) == hipSuccess;
-  return v;
-}
-bool stream_is_capturing(hipStream_t s) {
-  if (s == nullptr) return false;  // the legacy default stream cannot be captured (and must not be queried during a capture)
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &st) != hipSuccess) {
-    (void)hipGetLastError();
-    return true;  // cannot tell: behave as inside a capture (create nothing)
-  }
-  return st != hipStreamCaptureStatusNone;
-}
-// called by every eager se3conv_fwd / se3conv_bwd: the spares a later capture may need
-void keep_side_streams_ready(hipStream_t caller) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return;
-  SideTable& t = side_table();
-  {
-    std::lock_guard<std::mutex> lk(t.mu);
-    auto it = t.spare.find(dev);
-    if (it != t.spare.end() && it->second.size() >= kSpareSideStreams) return;
-  }
-  if (stream_is_capturing(caller)) return;
-  std::lock_guard<std::mutex> lk(t.mu);
-  auto& sp = t.spare[dev];
-  while (sp.size() < kSpareSideStreams) {
-    SideStream v = make_side_stream(t);
-    if (!v.ok) break;
-    sp.push_back(v);
-  }
-}
-// t.mu held, the caller's stream is not being captured: hand the least recently used sets of this device back to the spares
-// until the device owns at most kMaxOwnedSideStreams (sets that are part of a capture in progress stay where they are)
-void evict_side_streams(SideTable& t, int dev) {
-  for (;;) {
-    size_t owned = 0;
-    auto victim = t.by_stream.end();
-    for (auto it = t.by_stream.begin(); it != t.by_stream.end(); ++it) {
-      if (it->first.first != dev || !it->second.ok) continue;
-      ++owned;
-      if (it->second.pins > 0) continue;  // between fork and join of another thread's call: not a candidate
-      if (victim == t.by_stream.end() || it->second.last_use < victim->second.last_use) victim = it;
-    }
-    if (owned <= kMaxOwnedSideStreams || victim == t.by_stream.end()) return;
-    if (stream_is_capturing(victim->second.stream)) {  // forked into a capture that has not ended: not now
-      victim->second.last_use = ++t.clock;
-      bool any_idle = false;
-      for (auto& kv : t.by_stream)
-        if (kv.first.first == dev && kv.second.ok && kv.second.pins == 0 && !stream_is_capturing(kv.second.stream)) any_idle = true;
-      if (!any_idle) return;
-      continue;
-    }
-    t.spare[dev].push_back(victim->second);
-    t.by_stream.erase(victim);
-    ++t.evicted;
-  }
-}
-// Returns a COPY of the set (the table may hand the entry to another caller later; the runtime objects are never
-// destroyed), ok = false when there is nothing to fork onto.  A set that is returned ok is PINNED: the cap cannot hand
-// it to another caller stream until release_side_stream (ForkJoin's join / destructor) -- with more caller streams in
-// flight than the cap, two calls would otherwise record and wait on the same events.
-SideStream side_stream_for(hipStream_t caller) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return SideStream{};
-  SideTable& t = side_table();
-  {
-    std::lock_guard<std::mutex> lk(t.mu);
-    auto it = t.by_stream.find({dev, caller});
-    if (it != t.by_stream.end()) {
-      it->second.last_use = ++t.clock;
-      if (it->second.ok) ++it->second.pins;
-      return it->second;
-    }
-  }
-  const bool capturing = stream_is_capturing(caller);
-  std::lock_guard<std::mutex> lk(t.mu);
-  auto known = t.by_stream.find({dev, caller});  // another thread of this caller stream got here first
-  if (known != t.by_stream.end()) {
-    if (known->second.ok) ++known->second.pins;
-    return known->second;
-  }
-  SideStream v;
-  auto& sp = t.spare[dev];
-  if (capturing) {
-    if (sp.empty()) {  // nothing prepared outside the capture: no fork (run one eager step first)
-      ++t.unforked_in_capture;
-      return SideStream{};
-    }
-    v = sp.back();
-    sp.pop_back();
-  } else if (sp.size() > kSpareSideStreams) {  // sets the cap took back come first
-    v = sp.back();
-    sp.pop_back();
-  } else {
-    v = make_side_stream(t);
-  }
-  v.last_use = ++t.clock;
-  v.pins = v.ok ? 1 : 0;
-  t.by_stream.emplace(std::make_pair(dev, caller), v);
-  if (!capturing) evict_side_streams(t, dev);
-  return v;
-}
-// the call that pinned the set (side_stream_for returned ok) is done with its events
-void release_side_stream(hipStream_t caller) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return;
-  SideTable& t = side_table();
-  std::lock_guard<std::mutex> lk(t.mu);
-  auto it = t.by_stream.find({dev, caller});
-  if (it != t.by_stream.end() && it->second.pins > 0) --it->second.pins;
-}
-// Joins the forked side stream back into the caller's stream on EVERY exit path of se3conv_bwd once the fork has
-// happened (an early `return rc` would otherwise leave the side stream writing into buffers the caller is about to
-// free, and a stream capture with an unjoined fork).
-struct ForkJoin {
-  SideStream side;
-  hipStream_t main = nullptr;
-  bool forked = false, pinned = false;
-  // takes over the pin of a set side_stream_for returned ok (released on join / destruction, forked or not)
-  void adopt(const SideStream& s, hipStream_t m) { side = s, main = m, pinned = s.ok; }
-  int fork(const SideStream& s, hipStream_t m) {
-    if (!pinned) adopt(s, m);
-    if (hipEventRecord(s.fork, m) != hipSuccess || hipStreamWaitEvent(s.stream, s.fork, 0) != hipSuccess)
-      return SE3_ERR_LAUNCH;
-    forked = true;
-    return SE3_OK;
-  }
-  int join() {
-    int rc = SE3_OK;
-    if (forked) {
-      forked = false;
-      if (hipEventRecord(side.join, side.stream) != hipSuccess || hipStreamWaitEvent(main, side.join, 0) != hipSuccess)
-        rc = SE3_ERR_LAUNCH;
-    }
-    if (pinned) {
-      pinned = false;
-      release_side_stream(main);
-    }
-    return rc;
-  }
-  ~ForkJoin() { (void)join(); }
-};
 
 // ---- any number of basis functions on the K = 32 kernels (se3conv_fwd / se3conv_bwd with num_basis != 32) ---------------
 // The sum over k is separable: K basis functions are ceil(K / 32) slices of 32, the last one padded with basis functions
@@ -788,29 +580,13 @@ static int row_format(const se3conv_shape* s, const EdgeGeom& g, int channels, i
   return on && kBasis == 32 && channels % 2 == 0 && edge_t_bf16_t24_rows(g, channels) && tn_cols % 4 == 0 ? 1 : 0;
 }
 
-// grad_T in the T16 block format (SE3_PRECISION_BF16X3_T16): when the row-strip GEMM can write it (rows of whole mega tiles,
-// c_out <= 64) and the pair form of the parameter-gradient kernel reads it (two frames per point, 64-channel blocks)
-// OPT-IN (SE3_T16_GT=1): measured a net loss at the headline shape -- the strip GEMM gains 0.015 ms on 44 % fewer bytes
-// (its epilogue, not its stores, now sets its time) and the parameter-gradient kernel loses 0.04 ms to the decode in
-// front of every item's first chunk (profiles/r04_t16_ab.txt); T and U alone are the mode's default.
-static bool grad_t_t16(const se3conv_shape* s, const EdgeGeom& g) {
-  static const bool on = [] {
-    const char* e = getenv("SE3_T16_GT");
-    return e != nullptr && atoi(e) != 0;
-  }();
-  const int64_t rows_out = s->n_out * s->f_out;
-  return on && s->precision == SE3_PRECISION_BF16X3_T16 && s->num_basis == kBasis &&
-         gemm_strip_t16_applicable(rows_out, s->c_in * kBasis, s->c_out) && edge_param_grad_bf16_t16_rows(g, s->c_in);
-}
-
 // Bytes per element of the row-sized intermediates this shape would move (what a traffic model has to assume):
 // which = 0: T (forward, read again by the weight gradient), 1: U (feature gradient), 2: grad_T.  < 0: bad shape.
 // The T16 format's 2.25 bytes are reported as 2 here (an integer interface); se3conv_intermediate_row_bytes is exact.
 static int64_t intermediate_row_bytes(const se3conv_shape* s, int which) {
   const int64_t ck = (int64_t)(which == 1 ? s->c_out : s->c_in) * s->num_basis;
-  if (s->precision == SE3_PRECISION_FP32 || s->num_basis != kBasis) return ck * 4;
+  if (s->precision == SE3_PRECISION_FP32 || s->num_basis != kBasis || which == 2) return ck * 4;  // (grad_T: packed words)
   EdgeGeom g = forward_geom(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);
-  if (which == 2) return grad_t_t16(s, g) ? t16_row_bytes(s->c_in) : ck * 4;
   EdgeGeom gt{};
   gt.n_ctr = s->n_in, gt.f_ctr = s->f_in, gt.f_nb = s->f_out, gt.n_nb = s->n_out, gt.transposed = 1;
   const int fmt = which == 0 ? row_format(s, g, s->c_in, s->n_out * s->f_out, s->c_out)
@@ -883,7 +659,6 @@ extern "C" int se3conv_fwd_prepared(const float* pts_in, const float* pts_out, c
   const FwdLayout l = fwd_layout(s, t_save != nullptr);
   if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
-  keep_side_streams_ready(stream);  // what a later captured se3conv_bwd may fork onto (never created inside a capture)
   char* ws = (char*)workspace;
   float* axes_ext = (float*)(ws + l.axes_ext);
   float* t = t_save ? t_save : (float*)(ws + l.t);
@@ -925,8 +700,7 @@ extern "C" int se3conv_fwd_prepared(const float* pts_in, const float* pts_out, c
     if (int rc = pb.launch(stream)) return rc;
     g.ctr_geom = geom_out, g.nb_geom = geom_in;
   }
-  if (int rc = launch_edge_t_bf16("edge_t_fwd", g, featpk, s->c_in, s->n_in * s->f_in, axes_ext, rho, (uint32_t*)t, stream,
-                                  -1, -1, t24))
+  if (int rc = launch_edge_t_bf16("edge_t_fwd", g, featpk, s->c_in, s->n_in * s->f_in, axes_ext, rho, (uint32_t*)t, stream, t24))
     return rc;
   return launch_gemm_nn_bf16("gemm_out", (const uint32_t*)t, bt_hi, bt_lo, out, false, rows_out, s->c_out, ck,
                              (float*)(ws + l.split), nu, inv_phi, stream, t24);
@@ -1013,7 +787,6 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
   const BwdLayout l = bwd_layout(s, want_feat, want_params, t_save != nullptr);
   if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
-  keep_side_streams_ready(stream);
   char* ws = (char*)workspace;
   float* axes_ext = (float*)(ws + l.axes_ext);
   float* big = (float*)(ws + l.big);
@@ -1098,13 +871,13 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
   const bool have_featpk = prep && prep->feat_words && prep->feat_words_valid;
   uint32_t* featpk = prep && prep->feat_words ? prep->feat_words : (uint32_t*)(ws + l.featpk);
   uint32_t* bigw = (uint32_t*)big;
+  uint32_t* big_u = (uint32_t*)(ws + l.big_u);  // U when both branches run (grad_T takes `big`)
   const float inv_phi = inv_fin / kGeluOut;  // T and U hold kGeluOut * (the reference's values), see gelu_scaled
   const bool feat_branch = want_feat && rows_in > 0;
   const int t24_t = row_format(s, g, s->c_in, rows_out, s->c_out);  // as se3conv_fwd
   const int t24_u = feat_branch ? row_format(s, gt, s->c_out, rows_in, 0) : 0;
   const bool strip_t = gemm_strip_bf16_applicable(rows_out, ck, s->c_out);            // grad_T = g W^T
   const bool edge_dx = use_edge_dx(s, want_feat, want_params) && feat_branch;         // feature gradient edge-major (edge_dx.hip)
-  const bool gt16 = strip_t && !edge_dx && grad_t_t16(s, g);                          // ... written as T16 rows
   {  // one launch: [A; beta] table, packed geometry records, packed words of g and f, weight planes
     const bool same_cloud = pts_in == pts_out && frames_in == frames_out && s->n_in == s->n_out && s->f_in == s->f_out;
     const PreparedGeometry pg = prepared_geometry(prep, same_cloud, (float*)(ws + l.geom_in), (float*)(ws + l.geom_out));
@@ -1119,7 +892,7 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
     if (want_params && !have_featpk) pb.split(feat, featpk, rows_in * s->c_in);
     if (want_params || edge_dx)
       // alpha = nu/F_in is folded into these weights (one multiply per weight instead of one per grad_T element)
-      pb.weights(conv_weights, s->c_in, kb, s->c_out, 1, bt_hi, bt_lo, nu, inv_fin, strip_t, 0, gt16);
+      pb.weights(conv_weights, s->c_in, kb, s->c_out, 1, bt_hi, bt_lo, nu, inv_fin, strip_t);
     if (int rc = pb.launch(stream)) return rc;
     g.ctr_geom = geom_out, g.nb_geom = geom_in;
     gt.ctr_geom = geom_in, gt.nb_geom = geom_out;
@@ -1128,32 +901,33 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
   // per-workgroup partials of d[A; beta] -- write final outputs nobody in this call reads: one launch folds them all
   ReduceBatch final_sums;
   const bool dw_u = grad_weights != nullptr && feat_branch && !edge_dx && use_u_for_dw(s, want_feat, want_params, t_save != nullptr);
-  const uint32_t* u_rows = nullptr;  // where the transposed pass wrote U (set by whoever launches it)
-  auto weight_gradient = [&](hipStream_t st) -> int {
+  // grad_T[m,(i,k)] = sum_o g[m,o] W'[i,k,o] into `big`
+  auto grad_t = [&]() -> int {
+    if (strip_t) return launch_gemm_strip_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, rows_out, ck, s->c_out, stream);
+    return launch_gemm_nn_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, true, rows_out, ck, s->c_out, (float*)(ws + l.split),
+                               nullptr, 1.0f, stream);
+  };
+  auto weight_gradient = [&]() -> int {
     if (!grad_weights) return SE3_OK;
-    if (dw_u) {
-      if (!u_rows) return SE3_ERR_LAUNCH;  // (a schedule that has not produced U yet: a bug, not an input error)
-      // C'[(o,k), i] = sum_p U[p,(o,k)] f[p,i]; the batched reduction stores it as dW[i,k,o]
-      return launch_gemm_tn_bf16("gemm_gradW", u_rows, featpk, grad_weights, tn_partials, l.tn_splits, rows_in, s->c_out * kb,
-                                 s->c_in, nu, inv_phi, st, t24_u, &final_sums, true);
-    }
+    if (dw_u)  // C'[(o,k), i] = sum_p U[p,(o,k)] f[p,i]; the batched reduction stores it as dW[i,k,o]
+      return launch_gemm_tn_bf16("gemm_gradW", big_u, featpk, grad_weights, tn_partials, l.tn_splits, rows_in, s->c_out * kb,
+                                 s->c_in, nu, inv_phi, stream, t24_u, &final_sums, true);
     const uint32_t* t = (const uint32_t*)t_save;
     if (!t) {
       uint32_t* tt = (uint32_t*)(ws + l.t);
-      if (int rc = launch_edge_t_bf16("edge_t_recompute", g, featpk, s->c_in, rows_in, axes_ext, rho, tt, st, -1, -1, t24_t))
-        return rc;
+      if (int rc = launch_edge_t_bf16("edge_t_recompute", g, featpk, s->c_in, rows_in, axes_ext, rho, tt, stream, t24_t)) return rc;
       t = tt;
     }
     return launch_gemm_tn_bf16("gemm_gradW", t, gpk, grad_weights, tn_partials, l.tn_splits, rows_out, ck, s->c_out, nu,
-                               inv_phi, st, t24_t, &final_sums);
+                               inv_phi, stream, t24_t, &final_sums);
   };
   // d[A; beta]: per-workgroup partial sums; their fixed-order reduction joins the batch (the bf16 kernels accumulate with
   // 2 GELU', gelu_scaled_grad: the 0.5 is applied there)
-  auto param_gradients = [&](hipStream_t st) -> int {
+  auto param_gradients = [&]() -> int {
     if (!grad_axes && !grad_biases) return SE3_OK;
     int n_part = 0;
     if (int rc = launch_edge_param_grad_bf16("edge_param_grad", g, featpk, s->c_in, rows_in, axes_ext, rho, bigw, partials,
-                                             l.n_param_partials, &n_part, st, gt16))
+                                             l.n_param_partials, &n_part, stream))
       return rc;
     final_sums.params(partials, n_part, grad_axes, grad_biases, 0.5f);
     return SE3_OK;
@@ -1161,89 +935,42 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
 
   if (edge_dx) {
     // grad_T first (both branches read it), then the edge-major feature gradient and its per-source sums, then the
-    // parameter branch -- one stream: at these sizes (a sixth of a level's edges) nothing is worth a fork
-    if (strip_t) {
-      if (int rc = launch_gemm_strip_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, rows_out, ck, s->c_out, stream, false)) return rc;
-    } else if (int rc = launch_gemm_nn_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, true, rows_out, ck, s->c_out,
-                                            (float*)(ws + l.split), nullptr, 1.0f, stream)) {
-      return rc;
-    }
+    // parameter branch
+    if (int rc = grad_t()) return rc;
     float* d_rows = (float*)(ws + l.dx_rows);
     if (int rc = launch_edge_dx_bf16("edge_dx", g, axes_ext, rho, bigw, s->c_in, d_rows, stream)) return rc;
     if (int rc = launch_dx_gather_sum("dx_gather", d_rows, neighbors, ends, t_samples, t_ends, t_edge_ids, s->n_in, s->f_in * s->c_in,
                                       1.0f / kGeluOut, grad_feat, stream))
       return rc;
     if (want_params) {
-      if (int rc = param_gradients(stream)) return rc;
-      if (int rc = weight_gradient(stream)) return rc;
+      if (int rc = param_gradients()) return rc;
+      if (int rc = weight_gradient()) return rc;
     }
-    return final_sums.launch(stream);
-  }
-  bool branch_forked = false;
-  ForkJoin fj;  // joins on every exit path from here on
-  if (feat_branch) {
-    // feature branch: on the side stream when there is a parameter branch to overlap with (SE3_OVERLAP)
-    hipStream_t fs = stream;
-    uint32_t* ubuf = bigw;
-    float* fsplit = (float*)(ws + l.split);
-    // opt-in (see kOverlapRows): the two branches side by side
-    const int64_t overlap_rows = overlap_rows_limit();
-    SideStream side;
-    if (want_params && l.big_u != 0 && rows_out <= overlap_rows && (rows_out > kOverlapMinRows || overlap_rows >= ((int64_t)1 << 40)) &&
-        (side = side_stream_for(stream)).ok) {
-      if (int rc = fj.fork(side, stream)) return rc;
-      fs = side.stream;
-      ubuf = (uint32_t*)(ws + l.big_u);
-      fsplit = (float*)(ws + l.split2);
-      branch_forked = true;
-    }
-    // One stream: the two kernels that write a row-sized tensor (U, grad_T) go first, their readers after them.
-    // Whatever runs right behind a ~1 GB writer is slowed while the caches drain (a memory-bound reader by 15-30 %,
-    // whichever tensor it reads): in the order  U-writer, grad_X GEMM, grad_T writer, parameter gradients  two readers
-    // sit in that position, here only one does (gemm_gradX 0.221 -> 0.187 ms at the headline shape).
-    // SE3_BWD_BRANCH_ORDER=1 restores branch-by-branch order.
-    static const bool branch_order = getenv("SE3_BWD_BRANCH_ORDER") != nullptr;
-    if (!branch_order && !branch_forked && want_params && l.big_u != 0) {
-      ubuf = (uint32_t*)(ws + l.big_u);
-      fsplit = (float*)(ws + l.split2);
-      u_rows = ubuf;
-      if (int rc = launch_edge_t_bf16("edge_t_transposed", gt, gpk, s->c_out, rows_out, axes_ext, rho, ubuf, fs, -1, -1, t24_u))
-        return rc;
-      if (strip_t) {
-        if (int rc = launch_gemm_strip_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, rows_out, ck, s->c_out, stream, gt16)) return rc;
-      } else if (int rc = launch_gemm_nn_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, true, rows_out, ck, s->c_out,
-                                              (float*)(ws + l.split), nullptr, 1.0f, stream)) {
-        return rc;
-      }
-      if (int rc = param_gradients(stream)) return rc;
-      if (int rc = launch_gemm_nn_bf16("gemm_gradX", ubuf, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
-                                       fsplit, nu, inv_phi, fs, t24_u, &final_sums))
-        return rc;
-      if (int rc = weight_gradient(stream)) return rc;
-      return final_sums.launch(stream);
-    }
-    if (int rc = launch_edge_t_bf16("edge_t_transposed", gt, gpk, s->c_out, rows_out, axes_ext, rho, ubuf, fs, -1, -1, t24_u))
+  } else if (feat_branch && want_params) {
+    // Both branches, writers first: the two kernels that write a row-sized tensor (U, grad_T) go first, their readers
+    // after them.  Whatever runs right behind a ~1 GB writer is slowed while the caches drain (a memory-bound reader by
+    // 15-30 %, whichever tensor it reads): in the order  U-writer, grad_X GEMM, grad_T writer, parameter gradients  two
+    // readers sit in that position, here only one does (gemm_gradX 0.221 -> 0.187 ms at the headline shape).
+    if (int rc = launch_edge_t_bf16("edge_t_transposed", gt, gpk, s->c_out, rows_out, axes_ext, rho, big_u, stream, t24_u))
       return rc;
-    if (int rc = launch_gemm_nn_bf16("gemm_gradX", ubuf, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
-                                     fsplit, nu, inv_phi, fs, t24_u, &final_sums))
+    if (int rc = grad_t()) return rc;
+    if (int rc = param_gradients()) return rc;
+    if (int rc = launch_gemm_nn_bf16("gemm_gradX", big_u, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
+                                     (float*)(ws + l.split2), nu, inv_phi, stream, t24_u, &final_sums))
       return rc;
-    if (dw_u) {  // the weight gradient reads U: on the stream that wrote it, before the parameter branch reuses `big`
-      u_rows = ubuf;
-      if (int rc = weight_gradient(fs)) return rc;
-    }
-  }
-  if (want_params) {
-    if (strip_t) {
-      if (int rc = launch_gemm_strip_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, rows_out, ck, s->c_out, stream, gt16)) return rc;
-    } else if (int rc = launch_gemm_nn_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, true, rows_out, ck, s->c_out,
-                                            (float*)(ws + l.split), nullptr, 1.0f, stream)) {
+    if (int rc = weight_gradient()) return rc;
+  } else if (feat_branch) {
+    // feature gradient only: U into `big`, then the grad_X GEMM
+    if (int rc = launch_edge_t_bf16("edge_t_transposed", gt, gpk, s->c_out, rows_out, axes_ext, rho, bigw, stream, t24_u))
       return rc;
-    }
-    if (int rc = param_gradients(stream)) return rc;
-    if (!(dw_u && feat_branch))
-      if (int rc = weight_gradient(stream)) return rc;
+    if (int rc = launch_gemm_nn_bf16("gemm_gradX", bigw, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
+                                     (float*)(ws + l.split), nu, inv_phi, stream, t24_u, &final_sums))
+      return rc;
+  } else if (want_params) {
+    if (int rc = grad_t()) return rc;
+    if (int rc = param_gradients()) return rc;
+    if (int rc = weight_gradient()) return rc;
   }
-  if (int rc = fj.join()) return rc;  // the side stream's grad_X partials are complete before they are folded
   return final_sums.launch(stream);
 }
 
@@ -1291,26 +1018,6 @@ void prof_end(hipStream_t stream) {
   g_prof_open = nullptr;
 }
 }  // namespace se3
-
-extern "C" int se3_side_stream_stats(int32_t* stats) {
-  if (!stats) return SE3_ERR_INVALID_ARGUMENT;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return SE3_ERR_LAUNCH;
-  se3::SideTable& t = se3::side_table();
-  std::lock_guard<std::mutex> lk(t.mu);
-  stats[0] = (int32_t)t.by_stream.size();
-  auto it = t.spare.find(dev);
-  stats[1] = it == t.spare.end() ? 0 : (int32_t)it->second.size();
-  stats[2] = t.created;
-  stats[3] = t.unforked_in_capture;
-  stats[4] = t.evicted;
-  return SE3_OK;
-}
-
-extern "C" int se3_set_overlap_rows(int64_t rows) {
-  se3::g_overlap_rows.store(rows < 0 ? -1 : rows, std::memory_order_relaxed);
-  return SE3_OK;
-}
 
 extern "C" int se3_profile_enable(int on) {
   std::lock_guard<std::mutex> lk(se3::g_prof_mu);

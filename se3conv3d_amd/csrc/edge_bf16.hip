@@ -196,10 +196,6 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : (FC == 1 ? 3 : 2)) void edge_t_b
 // (The ablation builds of rounds 2 - 5 -- SE3_PAIR_ABLATE, SE3_PG_ABLATE, SE3_ABLATE: kernels with one ingredient taken out,
 // wrong results, for the "what bounds them" tables of profiles/README.md -- were removed in round 6 with the questions they
 // answered; the commits that produced a table hold the code that produced it.)
-#ifndef SE3_PAIR_PIN
-#define SE3_PAIR_PIN 1  // centre record passed through an empty asm at the top of every chunk: nothing derived from it is hoisted out
-                        // of the loop (fewer live registers, another schedule).  Measured -2 % (0.366 / 0.360 -> 0.359 / 0.353 ms)
-#endif
 // POW2: fnb_shift >= 0 is known (no division path, no branch on it).  TR: 0 forward, 1 transposed pass, -1 decided by
 // g.transposed at run time (both descriptor paths in the loop)
 template <int CT, bool FULL, int NF, bool POW2 = false, int TR = -1>
@@ -281,13 +277,12 @@ __global__ __launch_bounds__(128, CT == 1 ? (POW2 ? SE3_PAIR_WAVES : 3) : (FULL 
       // rows past the end of the neighbour list read out of bounds (buffer loads return 0): their phi needs no mask
       const int qoff = c0 + kcol < n_total ? q_a * row_bytes : kOobOffset;
       float xn[3], rn[9], d[9];
-      // SE3_PAIR_PIN: the centre's record stays the 12 values it is -- nothing derived from it leaves the loop
-#if SE3_PAIR_PIN
+      // the centre's record passes through an empty asm: it stays the 12 values it is -- nothing derived from it is hoisted
+      // out of the loop (fewer live registers, another schedule; measured -2 %: 0.366 / 0.360 -> 0.359 / 0.353 ms)
 #pragma unroll
       for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(yc[i]));
 #pragma unroll
       for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(rc[i]));
-#endif
 #pragma unroll
       for (int i = 0; i < 3; ++i) xn[i] = xn_nx[i];
 #pragma unroll
@@ -1014,15 +1009,9 @@ __global__ __launch_bounds__(256) void edge_param_grad_bf16_kernel(EdgeGeom g, c
 // a wave-private LDS image (CH16 * 4 KB per wavefront; in registers they cost CH16 * 16 VGPRs and spilled),
 // hence 512-thread blocks: 8 wavefronts share the CU's LDS at the same 2 waves/SIMD as before.
 // ------------------------------------------------------------------------------------------------
-#ifndef SE3_PG_PAIR_LEAN
-#define SE3_PG_PAIR_LEAN 0  // 1: pair form on 19 KB of LDS (8 workgroups = 4 wavefronts per SIMD): MLP weights in registers, ONE
-#endif                      // descriptor image per wavefront used by the two frames in turn, centre record re-read per chunk, next
-                            // geometry fetched between the frames -- what it takes to fit 128 VGPRs.  Measured (r02_param_grad_lean_ab):
-                            // 0.454 ms at 8 per CU against 0.446 for the 26 KB form at 6; at equal occupancy (6) the lean chunk is
-                            // 18 % slower (0.528), which the fourth wavefront only just buys back.  Parity-green, off.
 #ifndef SE3_PG_PAIR_WAVES
-#define SE3_PG_PAIR_WAVES (SE3_PG_PAIR_LEAN ? 4 : 3)  // wavefronts per SIMD the pair form's register budget is set for
-#endif
+#define SE3_PG_PAIR_WAVES 3  // wavefronts per SIMD the pair form's register budget is set for.  (A lean form at 4 -- 19 KB of LDS,
+#endif                       // MLP weights in registers, one descriptor image per wavefront -- was 2 % slower: r02_param_grad_lean_ab.)
 #ifndef SE3_PG_SINGLE_WAVES
 #define SE3_PG_SINGLE_WAVES 3  // one frame per wavefront (odd F).  4 (40 KB of LDS per 4-wave workgroup = 4 per CU) was measured:
 #endif                         // at 128 VGPRs the 64-channel form spills 11 registers and runs 0.65 instead of 0.47 ms (ScanNet-like)
@@ -1031,10 +1020,7 @@ __global__ __launch_bounds__(256) void edge_param_grad_bf16_kernel(EdgeGeom g, c
 // wavefront v builds the image of frame v (32 of the 64 row loads) and takes the chunks v, v + 2, ... of the item for
 // both frames; two workgroup barriers per item (image built / image free), partial sums folded per workgroup.
 // POW2: the neighbour cloud's frame count is a power of two (fnb_shift >= 0) -- no division path, no branch on it
-// GT16: grad_T rows come in the T16 block format (common.h; pair form, 64-channel blocks): a lane's 8 channels of a k-step
-// are two blocks of its basis function -- two 8-byte mantissa loads + the exponent line's 8-byte group per k-step instead
-// of eight dword loads, decoded to the same fragment image (t16_unpack2).
-template <int CH16, int NFR, bool PAIR = false, bool POW2 = false, bool GT16 = false>  // NFR = frames per wavefront: 2 (even F) or 1 (odd F: both lane halves hold the frame)
+template <int CH16, int NFR, bool PAIR = false, bool POW2 = false>  // NFR = frames per wavefront: 2 (even F) or 1 (odd F: both lane halves hold the frame)
 __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_PAIR_WAVES : (NFR == 2 ? 2 : (CH16 == 3 ? 3 : SE3_PG_SINGLE_WAVES))) void edge_param_grad_bf16_v2_kernel(EdgeGeom g, const uint32_t* __restrict__ feat,
                                                                          int row_ch, int64_t feat_rows,
                                                                          const float* __restrict__ axes_ext,
@@ -1047,17 +1033,15 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
   // row recomputes the descriptors and GELU').  row_ch = channels per row (a multiple of 16).
   // wavefronts per block: the gT images (8 KB per frame and wavefront) bound the occupancy
   static_assert(!PAIR || NFR == 2, "the pair form shares the two frames of a point");
-  static_assert(!GT16 || (PAIR && CH16 == 4), "T16 grad_T rows: pair form on whole 64-channel blocks");
-  constexpr bool LEAN = PAIR && SE3_PG_PAIR_LEAN;
   constexpr int NW = PAIR ? 2 : (NFR == 2 ? 8 : 4);
   constexpr int NIMG = PAIR ? 1 : NW;        // grad_T images per workgroup
   constexpr int CSTEP = PAIR ? 64 : 32;      // frame-edges between two chunks of one wavefront
   const int c_off = 64 * (int)blockIdx.y;
   const int row_bytes = row_ch * 4;
-  __shared__ __attribute__((aligned(16))) uint32_t lds_w[LEAN ? 1 : NFR][LEAN ? 1 : 2][LEAN ? 1 : 64][4];  // LEAN: in registers
+  __shared__ __attribute__((aligned(16))) uint32_t lds_w[NFR][2][64][4];
   // descriptor image for the d[A;beta] product: hi / lo bf16 planes, row = frame-edge, 12 columns ([desc(9), 1, 0, 0]).
   // Its MFMA fragments have the K index over the rows: read with ds_read_b64_tr_b16 (common.h), 4 per (frame, k-step).
-  __shared__ __attribute__((aligned(16))) uint16_t lds_desc[NW][LEAN ? 1 : NFR][2][32][12];
+  __shared__ __attribute__((aligned(16))) uint16_t lds_desc[NW][NFR][2][32][12];
   __shared__ __attribute__((aligned(16))) uint32_t lds_gt[NIMG][NFR][CH16][2][64][4];  // [wave][row][step][hi/lo][lane]
   // the final block reduction reuses the gT image (NW * 10 * 32 floats <= NIMG * NFR * CH16 * 512 words)
   float(*lds_red)[kDescExt][kBasis] = reinterpret_cast<float(*)[kDescExt][kBasis]>(&lds_gt[0][0][0][0][0][0]);
@@ -1067,15 +1051,9 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
   TL(__shared__ uint32_t tl_lds[NW][32]; uint32_t* tl_rec = tl_lds[wave]; if (lane < 32) tl_rec[lane] = 0u; uint32_t tl_prev = tl_now(); tl_rec[18] = tl_prev;)
   const int img = PAIR ? 0 : wave;  // which grad_T image this wavefront reads
   const int kcol = lane & 31, h = lane >> 5;
-  // MLP weights [A; beta] as the MFMA B operand.  LEAN: arrangement 0 (lane half 0 holds descriptor dims 0..7, half 1
-  // dims 8, 9) lives in 8 registers; frame 1 wants the halves exchanged, one v_permlane32_swap per register and chunk
-  u32x4 w_hi = {0u, 0u, 0u, 0u}, w_lo = {0u, 0u, 0u, 0u};
-  if (LEAN) {
-    load_mlp_weights(axes_ext, kcol, h, w_hi, w_lo);
-  } else {
-    if (threadIdx.x < 64) mlp_weights_to_lds<NFR>(reinterpret_cast<uint32_t(*)[2][64][4]>(&lds_w[0][0][0][0]), axes_ext, threadIdx.x);
-    __syncthreads();
-  }
+  // MLP weights [A; beta] as the MFMA B operand
+  if (threadIdx.x < 64) mlp_weights_to_lds<NFR>(reinterpret_cast<uint32_t(*)[2][64][4]>(&lds_w[0][0][0][0]), axes_ext, threadIdx.x);
+  __syncthreads();
   const float rho = *rho_p;
   const __amdgpu_buffer_rsrc_t feat_rs = buffer_of(feat, feat_rows * row_bytes);
   const __amdgpu_buffer_rsrc_t nbg_rs = buffer_of(g.nb_geom, g.n_nb * g.f_nb * 64);
@@ -1145,7 +1123,7 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
     return false;
   };
   auto issue_item_loads = [&]() {
-    if (!LEAN) load_geom_record(ctrg_rs, ctr_row, yc, rc);  // LEAN: fetched again per chunk (a cache hit; 12 registers)
+    load_geom_record(ctrg_rs, ctr_row, yc, rc);
     nb_a = nbr_of(c_first);
     nb_b = nbr_of(c_first + CSTEP);
   };
@@ -1154,45 +1132,25 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
   // 0.41 -> 0.475 ms)
   auto issue_image_loads = [&]() {
     // gT fragments (MFMA B operand) of the item's two rows: lane (k = kcol, h) holds channels 16*st + 8h + j
-      // (pair form: this wavefront fetches and builds the image of frame `wave` only)
-      if constexpr (GT16) {
-        // row `wave` of the item: mantissas of channel quad cq = c_off / 4 + 4 st + 2 h + jj at (cq * 32 + kcol) * 8; the
-        // exponents of both jj sit in one 8-byte group of the row's exponent plane (t16_exp_pos: mega tile = cq >> 1, piece
-        // = (kcol >> 1) & 7; byte (2 jj + (kcol >> 4)) * 2 + (kcol & 1))
-        const int64_t rbytes = t16_row_bytes(row_ch);
-        const uint64_t gt_addr = reinterpret_cast<uint64_t>(reinterpret_cast<const char*>(grad_t) + (item * NFR + wave) * rbytes);
-        const uint64_t gt_base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(gt_addr >> 32)) << 32) |
-                                 (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)gt_addr);
-        const __amdgpu_buffer_rsrc_t gt_rs = buffer_of(reinterpret_cast<const void*>(gt_base), rbytes);
-        const int cq0 = (c_off >> 2) + 2 * h;
-        const int e_off = row_ch * 64 + ((kcol >> 1) & 7) * 8, e_sh = 8 * ((kcol >> 4) * 2 + (kcol & 1));
+    // (pair form: this wavefront fetches and builds the image of frame `wave` only)
 #pragma unroll
-        for (int st = 0; st < CH16; ++st) {
-          const auto m0 = __builtin_amdgcn_raw_buffer_load_b64(gt_rs, ((cq0 + 4 * st) * kBasis + kcol) * 8, 0, 0);
-          const auto m1 = __builtin_amdgcn_raw_buffer_load_b64(gt_rs, ((cq0 + 4 * st + 1) * kBasis + kcol) * 8, 0, 0);
-          const auto eg = __builtin_amdgcn_raw_buffer_load_b64(gt_rs, e_off + ((cq0 + 4 * st) >> 1) * 64, 0, 0);
-          gw[0][st][0] = m0[0], gw[0][st][1] = m0[1], gw[0][st][2] = m1[0], gw[0][st][3] = m1[1];
-          gw[0][st][4] = (eg[0] >> e_sh) & 0xffu, gw[0][st][5] = (eg[1] >> e_sh) & 0xffu;
-        }
-      } else
+    for (int ab = 0; ab < NBUILD; ++ab) {
+      const int a = PAIR ? wave : ab;
+      const uint32_t* gt_row = grad_t + ((item * NFR + a) * (int64_t)row_ch + c_off) * kBasis;
+      // one buffer per row (its base is wave-uniform): channels past the row read as zeros through the bounds check of
+      // the buffer load -- a guarded global load per element compiled into a branch per load
+      const int row_left = min(row_ch - c_off, 16 * CH16);
+      // (`wave` is uniform but the compiler cannot know: without readfirstlane every load becomes a waterfall loop)
+      const uint64_t gt_addr = reinterpret_cast<uint64_t>(gt_row);
+      const uint64_t gt_base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(gt_addr >> 32)) << 32) |
+                               (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)gt_addr);  // (the builtin returns int)
+      const __amdgpu_buffer_rsrc_t gt_rs = buffer_of(reinterpret_cast<const void*>(gt_base), (int64_t)row_left * kBasis * 4);
 #pragma unroll
-      for (int ab = 0; ab < NBUILD; ++ab) {
-        const int a = PAIR ? wave : ab;
-        const uint32_t* gt_row = grad_t + ((item * NFR + a) * (int64_t)row_ch + c_off) * kBasis;
-        // one buffer per row (its base is wave-uniform): channels past the row read as zeros through the bounds check of
-        // the buffer load -- a guarded global load per element compiled into a branch per load
-        const int row_left = min(row_ch - c_off, 16 * CH16);
-        // (`wave` is uniform but the compiler cannot know: without readfirstlane every load becomes a waterfall loop)
-        const uint64_t gt_addr = reinterpret_cast<uint64_t>(gt_row);
-        const uint64_t gt_base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(gt_addr >> 32)) << 32) |
-                                 (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)gt_addr);  // (the builtin returns int)
-        const __amdgpu_buffer_rsrc_t gt_rs = buffer_of(reinterpret_cast<const void*>(gt_base), (int64_t)row_left * kBasis * 4);
+      for (int st = 0; st < CH16; ++st)
 #pragma unroll
-        for (int st = 0; st < CH16; ++st)
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            gw[ab][st][j] = __builtin_amdgcn_raw_buffer_load_b32(gt_rs, (8 * h * kBasis + kcol) * 4, (16 * st + j) * kBasis * 4, 0);
-      }
+        for (int j = 0; j < 8; ++j)
+          gw[ab][st][j] = __builtin_amdgcn_raw_buffer_load_b32(gt_rs, (8 * h * kBasis + kcol) * 4, (16 * st + j) * kBasis * 4, 0);
+    }
   };
   int prio_step = wave_slot_id();
   bool have = find_item();
@@ -1212,14 +1170,6 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
       for (int st = 0; st < CH16; ++st) {
         const int a = PAIR ? wave : ab;
         u32x4 f_hi, f_lo;
-        if constexpr (GT16) {
-          const float sc0 = t16_scale(gw[ab][st][4]), sc1 = t16_scale(gw[ab][st][5]);
-          uint32_t hw, lw;
-          t16_unpack2(gw[ab][st][0], sc0, hw, lw), f_hi[0] = hw, f_lo[0] = lw;
-          t16_unpack2(gw[ab][st][1], sc0, hw, lw), f_hi[1] = hw, f_lo[1] = lw;
-          t16_unpack2(gw[ab][st][2], sc1, hw, lw), f_hi[2] = hw, f_lo[2] = lw;
-          t16_unpack2(gw[ab][st][3], sc1, hw, lw), f_hi[3] = hw, f_lo[3] = lw;
-        } else
         frags_from_words(gw[ab][st], f_hi, f_lo);
         *reinterpret_cast<u32x4*>(&lds_gt[img][a][st][0][lane][0]) = f_hi;
         *reinterpret_cast<u32x4*>(&lds_gt[img][a][st][1][lane][0]) = f_lo;
@@ -1248,7 +1198,6 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
         fw[st][0] = v0[0], fw[st][1] = v0[1], fw[st][2] = v0[2], fw[st][3] = v0[3];
         fw[st][4] = v1[0], fw[st][5] = v1[1], fw[st][6] = v1[2], fw[st][7] = v1[3];
       }
-      if (LEAN) load_geom_record(ctrg_rs, ctr_row, yc, rc);
       q_a = q_b;
       TL(tl_seg(tl_rec, tl_prev, 8); tl_pin(xn_nx[0]); tl_pin(rn_nx[7]); tl_pin(rn_nx[8]); tl_seg(tl_rec, tl_prev, 9); tl_rec[17] += 1;)  // 8: gathers issued, 9: this chunk's record in
 
@@ -1258,7 +1207,7 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
         edge_descriptor(yc, rc, xn_nx, rn_nx, rho, d);
       // the next chunk's record goes out once this chunk's has been consumed (issuing it only at the
       // end of the chunk body -- measured slower, 0.434 vs 0.419 ms)
-      if (!LEAN) load_geom_record(nbg_rs, q_b, xn_nx, rn_nx);
+      load_geom_record(nbg_rs, q_b, xn_nx, rn_nx);
 
       u32x4 own_hi, own_lo, oth_hi = {0u, 0u, 0u, 0u}, oth_lo = {0u, 0u, 0u, 0u};
       frags_from_floats(d, own_hi, own_lo);
@@ -1276,8 +1225,8 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
         *reinterpret_cast<u32x2v*>(dl + 4) = u32x2v{own_lo[2], own_lo[3]};
         *reinterpret_cast<u32x2v*>(dl + 8) = u32x2v{own8_lo, 0u};
       };
-      if (!LEAN && (NFR == 2 || h == 0)) write_desc_rows(NFR == 2 ? h : 0);
-      if (!LEAN) {
+      if (NFR == 2 || h == 0) write_desc_rows(NFR == 2 ? h : 0);
+      {
         float d8 = d[8];
         if (NFR == 2) {  // dims 8, 9 of frame a come from the half that did not build frame a's descriptor
           const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(d8), __float_as_uint(d8), false, false);
@@ -1298,38 +1247,14 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
       auto gelu_grad_of_frame = [&](int a, float (&dy)[16]) {
         const bool dims07 = NFR == 2 ? h == a : h == 0;
         u32x4 a_hi, a_lo;
-        u32x4 wb_hi, wb_lo;
-        if (LEAN) {
-          // one weight arrangement (lane half 0: dims 0..7, half 1: dims 8, 9) for both frames; the descriptor of
-          // frame a was built by lane half a, so one of the two operand parts crosses the halves (v_permlane32_swap)
-          wb_hi = w_hi, wb_lo = w_lo;
-          auto other_half = [&](uint32_t v) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-            return h ? sw[0] : sw[1];
-          };
-          uint32_t d8_hi = own8_hi, d8_lo = own8_lo;
-          u32x4 r_hi = own_hi, r_lo = own_lo;
-          if (a == 0) {
-            d8_hi = other_half(own8_hi), d8_lo = other_half(own8_lo);
-          } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) r_hi[i] = other_half(own_hi[i]), r_lo[i] = other_half(own_lo[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            a_hi[i] = h == 0 ? r_hi[i] : (i == 0 ? d8_hi : 0u);
-            a_lo[i] = h == 0 ? r_lo[i] : (i == 0 ? d8_lo : 0u);
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            a_hi[i] = dims07 ? own_hi[i] : oth_hi[i];
-            a_lo[i] = dims07 ? own_lo[i] : oth_lo[i];
-          }
-          const auto* wl = reinterpret_cast<const uint32_t(*)[2][64][4]>(&lds_w[0][0][0][0]);
-          wb_hi = *reinterpret_cast<const u32x4*>(&wl[a][0][lane][0]);
-          wb_lo = *reinterpret_cast<const u32x4*>(&wl[a][1][lane][0]);
+        for (int i = 0; i < 4; ++i) {
+          a_hi[i] = dims07 ? own_hi[i] : oth_hi[i];
+          a_lo[i] = dims07 ? own_lo[i] : oth_lo[i];
         }
+        const auto* wl = reinterpret_cast<const uint32_t(*)[2][64][4]>(&lds_w[0][0][0][0]);
+        const u32x4 wb_hi = *reinterpret_cast<const u32x4*>(&wl[a][0][lane][0]);
+        const u32x4 wb_lo = *reinterpret_cast<const u32x4*>(&wl[a][1][lane][0]);
         const f32x16 pre = mfma_bf16x3(a_hi, a_lo, wb_hi, wb_lo, zero16());
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1355,38 +1280,13 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
             frags_from_floats(gp, ga_hi, ga_lo);
             // K slot (h, j) of this k-step is frame-edge acc_row(8 s + j, h) = 16 s + 4 h + (j & 3) + 8 (j >> 2)
             const int r0 = 16 * s + 4 * h + tr_row;
-            const int slot = LEAN ? 0 : a;
-            const u32x4 db_hi = lds_frag_tr16(&lds_desc[wave][slot][0][r0][tr_col], &lds_desc[wave][slot][0][r0 + 8][tr_col]);
-            const u32x4 db_lo = lds_frag_tr16(&lds_desc[wave][slot][1][r0][tr_col], &lds_desc[wave][slot][1][r0 + 8][tr_col]);
+            const u32x4 db_hi = lds_frag_tr16(&lds_desc[wave][a][0][r0][tr_col], &lds_desc[wave][a][0][r0 + 8][tr_col]);
+            const u32x4 db_lo = lds_frag_tr16(&lds_desc[wave][a][1][r0][tr_col], &lds_desc[wave][a][1][r0 + 8][tr_col]);
             dacc = mfma_bf16x3(ga_hi, ga_lo, db_hi, db_lo, dacc);
           }
         }
       };
       u32x4 fa_hi[CH16], fa_lo[CH16];
-      if (LEAN) {
-        // one descriptor image per wavefront: frame a's lane half writes its rows, the frame is accumulated, then the
-        // other half takes the image over (two wavefront barriers per frame instead of one per chunk)
-#pragma unroll
-        for (int a = 0; a < NFR; ++a) {
-          float dy[16];
-          gelu_grad_of_frame(a, dy);  // pure VALU in front of the first use of the gathered words
-          if (h == a) write_desc_rows(0);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          if (a == 0) {
-#pragma unroll
-            for (int st = 0; st < CH16; ++st) frags_from_words(fw[st], fa_hi[st], fa_lo[st]);
-          }
-          accumulate_frame(a, fa_hi, fa_lo, dy);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          // the next chunk's geometry goes out between the frames: 12 registers that would not fit next to frame 0's
-          // fragments, and frame 1's work still covers the latency
-          if (a == 0) load_geom_record(nbg_rs, q_b, xn_nx, rn_nx);
-        }
-        continue;
-      }
       // GELU' of both frames first (pure VALU, covers the gather latency) ...
       TL(tl_seg(tl_rec, tl_prev, 10);)  // 10: descriptor, splits, descriptor image
       float dyv[NFR][16];
@@ -1482,9 +1382,6 @@ static bool edge_t_bf16_uses_pair(const EdgeGeom& g, int channels) {
   return channels >= 64 && getenv("SE3_NO_PAIR") == nullptr && !(channels == 64 && g.f_ctr % 2 == 1);
 }
 
-// row ranges (producer / consumer interleaving over slices of the rows): every form (multiples of the rows per item)
-bool edge_t_bf16_row_ranges(const EdgeGeom& g, int channels) { return true; }
-
 // Which launches can write their rows in the 3-byte format: the wave-pair kernel, and the single-wavefront kernel at one
 // or two channels per lane (rows of up to 32 channels, and the 64-channel rows it takes), where the two channels of a
 // pair are values of one lane
@@ -1499,9 +1396,6 @@ bool edge_t_bf16_t16_rows(const EdgeGeom& g, int channels) {
   return channels % 64 == 0 && edge_t_bf16_uses_pair(g, channels);
 }
 
-#ifndef SE3_STREAM1
-#define SE3_STREAM1 1  // 0: diagnostic build without the single-wavefront chunk-stream kernel (A/B against the one-item form)
-#endif
 // items below which the chunk-stream kernels are not used (SE3_EDGE_STREAM=n: n items; 0: never)
 static int edge_stream_min_items() {
   static const int v = [] {
@@ -1522,23 +1416,18 @@ static int device_cu_count() {  // of the current device (the resident grids are
   return n_cu;
 }
 
-// row_lo / row_hi (multiples of 2 for even F; < 0: everything): only the rows in that range are produced -- the
-// wave-pair kernel supports it (edge_t_bf16_row_ranges), which lets the caller interleave producer and consumer
-// launches over slices of the rows
 int launch_edge_t_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat, int channels, int64_t feat_rows,
-                       const float* axes_ext, const float* rho, uint32_t* t_out, hipStream_t stream, int64_t row_lo,
-                       int64_t row_hi, int rowfmt) {
+                       const float* axes_ext, const float* rho, uint32_t* t_out, hipStream_t stream, int rowfmt) {
   const bool t24 = rowfmt == 1;
   const int64_t rows = g.n_ctr * g.f_ctr;
   if (rows == 0) return SE3_OK;
-  if (row_lo >= 0 && !edge_t_bf16_row_ranges(g, channels)) return SE3_ERR_UNSUPPORTED;
   if (t24 && !edge_t_bf16_t24_rows(g, channels)) return SE3_ERR_UNSUPPORTED;
   if (rowfmt == 2 && !edge_t_bf16_t16_rows(g, channels)) return SE3_ERR_UNSUPPORTED;
   // 32-bit byte offsets into the gathered operand; kOobOffset must lie beyond it
   if (feat_rows * (int64_t)channels * 4 >= (int64_t)kOobOffset) return SE3_ERR_UNSUPPORTED;
   ProfScope prof(tag, stream);
   // two frames per wavefront share the gather; with 4 channel tiles per frame that would spill, so VW = 4 stays at 1
-  const int fc = (getenv("SE3_FC1") == nullptr && g.f_ctr % 2 == 0 && channels % 128 != 0) ? 2 : 1;
+  const int fc = g.f_ctr % 2 == 0 && channels % 128 != 0 ? 2 : 1;
   const int64_t items = rows / fc;
   int shift = -1;
   for (int sft = 0; sft < 8; ++sft)
@@ -1548,33 +1437,28 @@ int launch_edge_t_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat,
     // a 128-thread workgroup per two frames of a point (even F) or per single row (odd F)
     const bool two = g.f_ctr % 2 == 0;
     const int64_t pair_items = two ? rows / 2 : rows;
-    const int per = two ? 2 : 1;
-    const int64_t item_lo = row_lo >= 0 ? row_lo / per : 0;
-    const int64_t item_hi = row_lo >= 0 ? row_hi / per : pair_items;
-    const int64_t n_range = item_hi - item_lo;
-    if (n_range <= 0) return SE3_OK;
     // chunk-stream form (resident workgroups, the chunk pipeline running across item boundaries): 64-channel rows, two
     // frames per item, power-of-two neighbour frame count, 3-byte rows; SE3_EDGE_STREAM=0 keeps the one-item workgroups
-    if (channels == 64 && two && shift >= 0 && rowfmt == 1 && n_range >= edge_stream_min_items() && g.n_edges > 0 &&
-        g.n_edges * g.nbr_stride * 4 < (int64_t)kOobOffset && item_hi < (1ll << 31)) {
+    if (channels == 64 && two && shift >= 0 && rowfmt == 1 && pair_items >= edge_stream_min_items() && g.n_edges > 0 &&
+        g.n_edges * g.nbr_stride * 4 < (int64_t)kOobOffset && pair_items < (1ll << 31)) {
       const int n_cu = device_cu_count();
       if (n_cu <= 0) return SE3_ERR_LAUNCH;
       constexpr int per_cu = 2 * SE3_PAIR_WAVES;  // 18 KB of LDS and <= 128 VGPRs: eight two-wavefront workgroups per CU
       int64_t wgs = (int64_t)n_cu * per_cu;  // resident workgroups only, whatever the level's size (windows of 64 items inside)
-      if (wgs > n_range) wgs = n_range;
+      if (wgs > pair_items) wgs = pair_items;
       const dim3 sgrid((unsigned)wgs), sblock(128);
       if (g.transposed)
         hipLaunchKernelGGL((edge_t_stream_bf16_kernel<1>), sgrid, sblock, 0, stream, g, feat, feat_rows, axes_ext, rho,
-                           reinterpret_cast<char*>(t_out), (uint32_t)item_lo, (uint32_t)item_hi, shift);
+                           reinterpret_cast<char*>(t_out), 0u, (uint32_t)pair_items, shift);
       else
         hipLaunchKernelGGL((edge_t_stream_bf16_kernel<0>), sgrid, sblock, 0, stream, g, feat, feat_rows, axes_ext, rho,
-                           reinterpret_cast<char*>(t_out), (uint32_t)item_lo, (uint32_t)item_hi, shift);
+                           reinterpret_cast<char*>(t_out), 0u, (uint32_t)pair_items, shift);
       return check_launch();
     }
-    const dim3 pgrid((unsigned)n_range), pblock(128);
+    const dim3 pgrid((unsigned)pair_items), pblock(128);
 #define SE3_PAIR_T(CT, FULL, NF, P2, TR)                                                                                \
   hipLaunchKernelGGL((edge_t_pair_bf16_kernel<CT, FULL, NF, P2, TR>), pgrid, pblock, 0, stream, g, feat, channels, feat_rows, \
-                     axes_ext, rho, t_out, item_lo, item_hi, shift, rowfmt)
+                     axes_ext, rho, t_out, 0, pair_items, shift, rowfmt)
 #define SE3_PAIR_L(CT, FULL, NF, P2)                 \
   do {                                               \
     if (!(P2)) SE3_PAIR_T(CT, FULL, NF, P2, -1);     \
@@ -1596,34 +1480,31 @@ int launch_edge_t_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat,
 #undef SE3_PAIR_T
     return check_launch();
   }
-  // row range: items of fc rows each
-  const int64_t s_item_lo = row_lo >= 0 ? row_lo / fc : 0, s_item_hi = row_lo >= 0 ? row_hi / fc : items;
-  if (s_item_hi <= s_item_lo) return SE3_OK;
   // chunk-stream form of the single-wavefront kernel: rows of 32 channels, two frames per item.  Measured per form
   // (profiles/r06_edge_stream1_ab.txt): <1, 2> -8 % at two frames (items of ~2 chunks: dfaust_f2 0.191 -> 0.177 ms), -1 % at
   // four; <2, 1> (64-channel rows at one frame, the ScanNet scene: items of ONE chunk, so every chunk ends in its stores
   // and there is no pipeline to carry across) +1 %, and +6 % when squeezed to four wavefronts per SIMD (7 spilled
   // registers) -- those rows keep the one-item form.
-  if (SE3_STREAM1 && t24 && shift >= 0 && channels == 32 && fc == 2 && s_item_hi - s_item_lo >= edge_stream_min_items() &&
-      g.n_edges > 0 && g.n_edges * g.nbr_stride * 4 < (int64_t)kOobOffset && s_item_hi < (1ll << 31)) {
+  if (t24 && shift >= 0 && channels == 32 && fc == 2 && items >= edge_stream_min_items() && g.n_edges > 0 &&
+      g.n_edges * g.nbr_stride * 4 < (int64_t)kOobOffset && items < (1ll << 31)) {
     const int n_cu = device_cu_count();
     if (n_cu <= 0) return SE3_ERR_LAUNCH;
     constexpr int per_cu = 3;  // = the kernel's launch bounds: resident workgroups only
     int64_t wgs = (int64_t)n_cu * per_cu;
-    if (wgs > (s_item_hi - s_item_lo + 3) / 4) wgs = (s_item_hi - s_item_lo + 3) / 4;
+    if (wgs > (items + 3) / 4) wgs = (items + 3) / 4;
     const dim3 sgrid((unsigned)wgs);
     if (g.transposed)
       hipLaunchKernelGGL((edge_t_stream1_bf16_kernel<1, 2, 1>), sgrid, block, 0, stream, g, feat, feat_rows, axes_ext, rho,
-                         reinterpret_cast<char*>(t_out), (uint32_t)s_item_lo, (uint32_t)s_item_hi, shift);
+                         reinterpret_cast<char*>(t_out), 0u, (uint32_t)items, shift);
     else
       hipLaunchKernelGGL((edge_t_stream1_bf16_kernel<1, 2, 0>), sgrid, block, 0, stream, g, feat, feat_rows, axes_ext, rho,
-                         reinterpret_cast<char*>(t_out), (uint32_t)s_item_lo, (uint32_t)s_item_hi, shift);
+                         reinterpret_cast<char*>(t_out), 0u, (uint32_t)items, shift);
     return check_launch();
   }
-  const dim3 grid((unsigned)((s_item_hi - s_item_lo + 3) / 4));
+  const dim3 grid((unsigned)((items + 3) / 4));
 #define SE3_LAUNCH(VW, FC, FULL, T24)                                                                                 \
   hipLaunchKernelGGL((edge_t_bf16_kernel<VW, FC, FULL, T24>), grid, block, 0, stream, g, feat, channels, feat_rows,     \
-                     axes_ext, rho, t_out, s_item_hi, shift, s_item_lo)
+                     axes_ext, rho, t_out, items, shift, 0)
 #define SE3_LAUNCH_T(VW, FC, FULL)                   \
   do {                                               \
     if (t24) SE3_LAUNCH(VW, FC, FULL, true);         \
@@ -1643,36 +1524,14 @@ int launch_edge_t_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat,
   return check_launch();
 }
 
-// grad_T rows in the T16 block format: the pair form (two frames per point) on whole 64-channel blocks
-bool edge_param_grad_bf16_t16_rows(const EdgeGeom& g, int channels) {
-  static const bool pair_on = [] {
-    const char* e = getenv("SE3_PG_PAIR");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return pair_on && getenv("SE3_PG_SINGLE") == nullptr && g.f_ctr % 2 == 0 && channels % 64 == 0 && channels >= 64;
-}
-
-// row ranges (slices of the rows): every form for rows of a multiple of 16 channels
-bool edge_param_grad_bf16_row_ranges(const EdgeGeom& g, int channels) {
-  static const bool pair_on = [] {
-    const char* e = getenv("SE3_PG_PAIR");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  (void)pair_on;
-  return channels % 16 == 0 && channels > 0;  // every MFMA form of the kernel walks an item range
-}
-
 // partials: room for n_partials x edge_param_grad_bf16_channel_blocks(channels) slots of 320 floats; *n_used = slots written
 int edge_param_grad_bf16_channel_blocks(int channels) { return channels > 64 && channels % 16 == 0 ? (channels + 63) / 64 : 1; }
 
 int launch_edge_param_grad_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat, int channels,
                                 int64_t feat_rows, const float* axes_ext, const float* rho, const uint32_t* grad_t,
-                                float* partials, int n_partials, int* n_used, hipStream_t stream, bool gt16, int64_t row_lo,
-                                int64_t row_hi) {
+                                float* partials, int n_partials, int* n_used, hipStream_t stream) {
   const int64_t rows = g.n_ctr * g.f_ctr;
-  if (row_lo >= 0 && !edge_param_grad_bf16_row_ranges(g, channels)) return SE3_ERR_UNSUPPORTED;
   if (feat_rows * (int64_t)channels * 4 >= (int64_t)kOobOffset) return SE3_ERR_UNSUPPORTED;
-  if (gt16 && !edge_param_grad_bf16_t16_rows(g, channels)) return SE3_ERR_UNSUPPORTED;
   ProfScope prof(tag, stream);
   *n_used = n_partials;
   // Rows of fewer than 16 channels (the networks' first layers: C_in = 1 for DFaust, 3 for ScanNet colours) take the MFMA
@@ -1689,63 +1548,42 @@ int launch_edge_param_grad_bf16(const char* tag, const EdgeGeom& g, const uint32
     static const bool force_single = getenv("SE3_PG_SINGLE") != nullptr;
     const bool two = g.f_ctr % 2 == 0 && !force_single;
     const int64_t items = two ? rows / 2 : rows;
-    // row range (slices of the rows, api.hip): items item_lo .. item_lo + n_range - 1 only
-    const int64_t item_lo = row_lo >= 0 ? row_lo / (two ? 2 : 1) : 0;
-    const int64_t n_range = row_lo >= 0 ? row_hi / (two ? 2 : 1) - item_lo : items;
-    if (n_range <= 0) {
+    if (items <= 0) {
       *n_used = 0;
       return SE3_OK;
     }
     const int blocks_y = edge_param_grad_bf16_channel_blocks(channels);
-    // pair form (two wavefronts share an item and its grad_T image, 3 wavefronts per SIMD): SE3_PG_PAIR=0 turns it off
-    static const bool pair_on = [] {
-      const char* e = getenv("SE3_PG_PAIR");
-      return e == nullptr || atoi(e) != 0;
-    }();
-    // 32-channel rows (DFaust's first level) take the pair form too, with half the grad_T image (CH16 = 2): 0.258 against
-    // 0.284 ms on the DFaust F = 2 batch (profiles/r03_c32_pair_forms_ab.txt); SE3_PG_PAIR_C32=0 keeps the 512-thread form.
-    // (The same idea for the edge_t kernel -- a split-K wave pair for 32-channel rows -- measured 7-10 % SLOWER than the
-    // single-wavefront kernel and is not kept, same file.)
-    static const bool pair32_on = [] {
-      const char* e = getenv("SE3_PG_PAIR_C32");
-      return e == nullptr || atoi(e) != 0;
-    }();
-    if (pair_on && two && (channels >= 64 || (channels == 32 && pair32_on))) {
+    // pair form (two wavefronts share an item and its grad_T image, 3 wavefronts per SIMD).  32-channel rows (DFaust's
+    // first level) take it too, with half the grad_T image (CH16 = 2): 0.258 against 0.284 ms for the 512-thread form on
+    // the DFaust F = 2 batch (profiles/r03_c32_pair_forms_ab.txt).  (The same idea for the edge_t kernel -- a split-K wave
+    // pair for 32-channel rows -- measured 7-10 % SLOWER than the single-wavefront kernel and is not kept, same file.)
+    if (two && (channels >= 64 || channels == 32)) {
       const int n_cu = device_cu_count();
       if (n_cu <= 0) return SE3_ERR_LAUNCH;
-      static const int per_cu = [] {
-        const char* e = getenv("SE3_PG_PAIR_WGS");
-        return e ? atoi(e) : (SE3_PG_PAIR_LEAN ? 8 : 6);  // 19 KB / 26 KB of LDS per workgroup
-      }();
+      constexpr int per_cu = 6;  // 26 KB of LDS per workgroup
       int64_t wgs = (int64_t)n_cu * per_cu;
       // extents in lane registers (pipe) where a resident workgroup walks at most 64 items; the per-item extent loads
       // otherwise -- never more workgroups than the chip holds at once for the registers' sake: 3 450 workgroups of 64 items
       // on dfaust_f4's level 0 ran as 2.25 rounds of 1 536 and took 1.52 instead of 1.23 ms, and the extent loads were never
       // what the kernel waited on (profiles/r06_param_grad_pipeline_ab.txt)
       if (wgs > n_partials) wgs = n_partials;
-      if (wgs > n_range) wgs = n_range;
+      if (wgs > items) wgs = items;
       if (wgs < 1) wgs = 1;
-      const int pipe = (n_range + wgs - 1) / wgs <= 64 && item_lo + n_range < (1ll << 31) ? 1 : 0;
+      const int pipe = (items + wgs - 1) / wgs <= 64 && items < (1ll << 31) ? 1 : 0;
       *n_used = (int)wgs * blocks_y;
       const dim3 pgrid((unsigned)wgs, (unsigned)blocks_y);
       if (channels == 32 && shift >= 0)
         hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<2, 2, true, true>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, n_range, shift, item_lo, pipe);
+                           feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe);
       else if (channels == 32)
         hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<2, 2, true, false>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, n_range, shift, item_lo, pipe);
-      else if (gt16 && shift >= 0)
-        hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<4, 2, true, true, true>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, n_range, shift, item_lo, pipe);
-      else if (gt16)
-        hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<4, 2, true, false, true>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, n_range, shift, item_lo, pipe);
+                           feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe);
       else if (shift >= 0)
         hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<4, 2, true, true>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, n_range, shift, item_lo, pipe);
+                           feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe);
       else
         hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<4, 2, true, false>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, n_range, shift, item_lo, pipe);
+                           feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe);
       return check_launch();
     }
     const int n_blocks = n_partials < 512 ? n_partials : 512;  // the 512-thread form: one workgroup per CU and round
@@ -1753,21 +1591,27 @@ int launch_edge_param_grad_bf16(const char* tag, const EdgeGeom& g, const uint32
     const dim3 grid((unsigned)n_blocks, (unsigned)blocks_y);
 #define SE3_PG_L(CH16, NFR, P2, THREADS)                                                                                  \
   hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<CH16, NFR, false, P2>), grid, dim3(THREADS), 0, stream, g, feat, channels, \
-                     feat_rows, axes_ext, rho, grad_t, partials, n_range, shift, item_lo)
+                     feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0)
+#define SE3_PG1(CH16)                                      \
+  do {                                                     \
+    if (shift >= 0) SE3_PG_L(CH16, 1, true, 256);          \
+    else SE3_PG_L(CH16, 1, false, 256);                    \
+  } while (0)
 #define SE3_PG(CH16)                                       \
   do {                                                     \
     if (two && shift >= 0) SE3_PG_L(CH16, 2, true, 512);   \
     else if (two) SE3_PG_L(CH16, 2, false, 512);           \
-    else if (shift >= 0) SE3_PG_L(CH16, 1, true, 256);     \
-    else SE3_PG_L(CH16, 1, false, 256);                    \
+    else SE3_PG1(CH16);                                    \
   } while (0)
+    // (two frames of 32 and of >= 64 channels took the pair form above: those widths have one-frame forms only)
     switch (channels >= 64 ? 4 : (channels + 15) / 16) {
       case 1: SE3_PG(1); break;
-      case 2: SE3_PG(2); break;
+      case 2: SE3_PG1(2); break;
       case 3: SE3_PG(3); break;
-      default: SE3_PG(4); break;
+      default: SE3_PG1(4); break;
     }
 #undef SE3_PG
+#undef SE3_PG1
 #undef SE3_PG_L
     return check_launch();
   }

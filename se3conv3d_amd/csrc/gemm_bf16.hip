@@ -234,13 +234,10 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
 // (256-row workgroups -- 8 wavefronts, the weight planes fetched from L2 half as often -- were measured in round 3:
 // nothing at the headline shape, 15 % slower on a 150 k-row scene whose 586 workgroups no longer divide into full rounds:
 // profiles/r03_gemm_256row_ab.txt.)
-// KG = k groups per workgroup (round 5): 1 -- four wavefronts walk the workgroup's super tiles -- or 2 -- eight wavefronts,
-// group g walks half of them with LDS tiles of its own and the two partial tiles are added through LDS at the end.  For
-// products whose row blocks cannot fill the chip (levels of 4 k - 40 k rows: fewer workgroups than CUs x 2): a workgroup
-// alone on its CU is bound by its own chain of loads, barriers and MFMAs (~0.75 us per 32-k tile whatever is in flight), so
-// two chains side by side halve its time without the partial-sum round trip and the reduction launch a split over grid.z costs.
-template <int OUT_MODE, int NB, int KG = 1>
-__global__ __launch_bounds__(256 * KG) void gemm_nn_t24_kernel(const uint8_t* __restrict__ a,
+// (Two k groups per workgroup -- eight wavefronts, each group walking half of the super tiles, the partial tiles added
+// through LDS -- were measured in round 5 against the split over grid.z: no faster, profiles/r05_nn_kgroups_ab.txt.)
+template <int OUT_MODE, int NB>
+__global__ __launch_bounds__(256) void gemm_nn_t24_kernel(const uint8_t* __restrict__ a,
                                                           const uint16_t* __restrict__ bt_hi,
                                                           const uint16_t* __restrict__ bt_lo, void* __restrict__ c,
                                                           int64_t m, int n, int k, int st_per_split,
@@ -251,23 +248,21 @@ __global__ __launch_bounds__(256 * KG) void gemm_nn_t24_kernel(const uint8_t* __
   constexpr int RPL = 64;          // rows one load pass of the lo plane covers (4 threads per row): 2 passes = RB rows
   constexpr int CP = 32;           // weight columns one load pass covers: 2 * NB passes per plane
   constexpr int NBP = 2 * NB;
-  // one block of LDS, carved: per k group the four tile images; the partial tile of group 1 reuses group 0's images at the end
+  // one block of LDS, carved into the four tile images
   constexpr int kAsh = 2 * RB * (BK + 8) * 2, kAsl = 2 * RB * (BK + 16), kBs = 2 * BNW * B_LD * 2;
-  constexpr int kGroup = kAsh + kAsl + 2 * kBs;
-  static_assert(KG == 1 || RB * BNW * 4 <= kGroup, "the partial tile must fit the tile images it reuses");
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // KG * kGroup bytes (gemm_nn_t24_lds_bytes): 52 / 104 / 72 / 144 KB
-  const int grp = KG == 1 ? 0 : (int)(threadIdx.x >> 8);
-  auto ash = reinterpret_cast<uint16_t(*)[RB][BK + 8]>(smem + grp * kGroup);                    // [2][RB][BK + 8], 80-byte pitch
-  auto asl = reinterpret_cast<uint8_t(*)[RB][BK + 16]>(smem + grp * kGroup + kAsh);             // [2][RB][BK + 16], 48-byte pitch
-  auto bsh = reinterpret_cast<uint16_t(*)[BNW][B_LD]>(smem + grp * kGroup + kAsh + kAsl);       // [2][BNW][B_LD]
-  auto bsl = reinterpret_cast<uint16_t(*)[BNW][B_LD]>(smem + grp * kGroup + kAsh + kAsl + kBs);
-  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;  // thread / wavefront inside the k group
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // gemm_nn_t24_lds_bytes: 52 / 72 KB
+  auto ash = reinterpret_cast<uint16_t(*)[RB][BK + 8]>(smem);                    // [2][RB][BK + 8], 80-byte pitch
+  auto asl = reinterpret_cast<uint8_t(*)[RB][BK + 16]>(smem + kAsh);             // [2][RB][BK + 16], 48-byte pitch
+  auto bsh = reinterpret_cast<uint16_t(*)[BNW][B_LD]>(smem + kAsh + kAsl);       // [2][BNW][B_LD]
+  auto bsl = reinterpret_cast<uint16_t(*)[BNW][B_LD]>(smem + kAsh + kAsl + kBs);
+  // (`& 255` changes no value at 256 threads, but without it the compiler allocates registers differently: kept, so that
+  // the kernel stays the code that was measured)
+  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
   const int rl = lane & 31, h = lane >> 5;
   const int64_t m0 = (int64_t)blockIdx.x * RB;
   const int n0 = blockIdx.y * BNW;
-  const int ns_wg = min(k / 64 - (int)blockIdx.z * st_per_split, st_per_split);  // super tiles of this workgroup (> 0 by construction)
-  const int ns = KG == 1 ? ns_wg : ns_wg / 2;                                    // ... of this k group (the host keeps ns_wg even)
-  const int st_begin = blockIdx.z * st_per_split + grp * ns;
+  const int ns = min(k / 64 - (int)blockIdx.z * st_per_split, st_per_split);  // super tiles of this workgroup (> 0 by construction)
+  const int st_begin = blockIdx.z * st_per_split;
 
   struct Super { u32x4 ah[4], al[2], bh[NBP], bl[NBP]; };
   const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -337,8 +332,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_nn_t24_kernel(const uint8_t* __
   };
   // Two super tiles in registers (= the 4 k-tiles in flight of the kernel above).  Step A computes the first half
   // while the second goes to LDS buffer 1; step B computes the second half, stores the next super tile's first half
-  // to buffer 0 and refills the register set that just emptied.  (KG = 2: both k groups run the same number of steps, so
-  // the workgroup barriers line up.)
+  // to buffer 0 and refills the register set that just emptied.
   Super t0, t1;
   load_super(t0, 0);
   if (ns > 1) load_super(t1, 1);
@@ -376,23 +370,6 @@ __global__ __launch_bounds__(256 * KG) void gemm_nn_t24_kernel(const uint8_t* __
 #undef SE3_T24_STEP
 #undef SE3_T24_STEP_FULL
 
-  if constexpr (KG == 2) {
-    // group 1's partial tile -> LDS (over the tile images, which nobody reads any more: the loop ended on a barrier),
-    // group 0 adds it to its own.  [row][column] floats, column fastest: conflict-free both ways.
-    float* red = reinterpret_cast<float*>(smem);
-    if (grp == 1) {
-#pragma unroll
-      for (int ct = 0; ct < 2 * NB; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[(wave * 32 + acc_row(r, h)) * BNW + 32 * ct + rl] = acc[ct][r];
-    }
-    __syncthreads();
-    if (grp == 1) return;
-#pragma unroll
-    for (int ct = 0; ct < 2 * NB; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ct][r] += red[(wave * 32 + acc_row(r, h)) * BNW + 32 * ct + rl];
-  }
   const float alpha = OUT_MODE == 2 ? 1.0f : (alpha_num ? *alpha_num : 1.0f) * alpha_scale;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -413,8 +390,8 @@ __global__ __launch_bounds__(256 * KG) void gemm_nn_t24_kernel(const uint8_t* __
   }
 }
 
-constexpr int gemm_nn_t24_lds_bytes(int nb, int kg) {
-  return kg * (2 * BM * (BK + 8) * 2 + 2 * BM * (BK + 16) + 2 * (2 * BN * nb * B_LD * 2));
+constexpr int gemm_nn_t24_lds_bytes(int nb) {
+  return 2 * BM * (BK + 8) * 2 + 2 * BM * (BK + 16) + 2 * (2 * BN * nb * B_LD * 2);
 }
 
 // NN GEMM over A rows in the 2.25-byte block format (common.h, T16; k a multiple of 256 = one mega tile of the exponent
@@ -736,130 +713,6 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : 2) void gemm_strip_bf16_kernel(c
 #undef SE3_WAIT_B
 }
 
-// The row-strip GEMM writing C (= grad_T) in the T16 block format (common.h): 2.25 instead of 4 bytes per element leave
-// the kernel, which is bound by its stores.  Column n of C is position n of the T16 row (the weights are prepared in that
-// order), so a 32-column tile = one channel quad x 8 basis functions x 4 channels: a block (4 channels of one basis
-// function) is four ADJACENT LANES of one accumulator register -- its maximum takes two DPP steps.  Mantissas and exponent
-// bytes go through wave-private LDS staging so that every store instruction writes 16 bytes per lane: a tile's 32 rows x
-// 64 B of mantissas as two stores, the 64 exponent bytes per row of a mega tile (8 column tiles) as two stores per mega tile
-// (2 + 1/4 store instructions per tile; the packed-word kernel issues 16).
-template <int KS>
-__global__ __launch_bounds__(256, 4) void gemm_strip_t16_kernel(const uint32_t* __restrict__ a,
-                                                                const uint16_t* __restrict__ bt_hi,
-                                                                const uint16_t* __restrict__ bt_lo,
-                                                                uint8_t* __restrict__ c, int64_t m, int n, int k) {
-  constexpr int KP = KS * 16;
-  __shared__ __attribute__((aligned(16))) uint16_t st_m[4][32][32 + 8];  // [wave][row][column], 80-byte pitch
-  __shared__ __attribute__((aligned(16))) uint8_t st_e[4][32][64 + 16];  // [wave][row][byte of the mega tile's exponent line]
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int rl = lane & 31, h = lane >> 5;
-  const int64_t row0 = (int64_t)blockIdx.x * 128 + wave * 32;
-  if (row0 >= m) return;
-  const __amdgpu_buffer_rsrc_t a_rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a), (short)0, (int)(uint32_t)(m * k * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t bh_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(bt_hi), (short)0, (int)(uint32_t)((int64_t)n * KP * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t bl_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(bt_lo), (short)0, (int)(uint32_t)((int64_t)n * KP * 2), 0x00020000);
-  u32x4 a_hi[KS], a_lo[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const int kk = 16 * ks + 8 * h;
-    uint32_t w[8];
-    const uint32_t off = kk < k ? (uint32_t)(((row0 + rl) * k + kk) * 4) : 0xfffffff0u;  // k % 8 == 0 (host)
-    const auto v0 = __builtin_amdgcn_raw_buffer_load_b128(a_rs, off, 0, 0);
-    const auto v1 = __builtin_amdgcn_raw_buffer_load_b128(a_rs, kk < k ? off + 16 : 0xfffffff0u, 0, 0);
-    w[0] = v0[0], w[1] = v0[1], w[2] = v0[2], w[3] = v0[3], w[4] = v1[0], w[5] = v1[1], w[6] = v1[2], w[7] = v1[3];
-    frags_from_words(w, a_hi[ks], a_lo[ks]);
-  }
-  // weight fragments of the next tile through inline asm + counted waits, as in gemm_strip_bf16_kernel: vmcnt retires
-  // loads and stores in order, so "at most S outstanding" behind the S stores of a tile means the older loads have landed
-  static_assert(KS == 2 || KS == 4, "operand lists of SE3_WAIT_B16");
-  u32x4 bh[KS], bl[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) bh[ks] = bl[ks] = u32x4{0u, 0u, 0u, 0u};
-  auto load_b = [&](int tile) {
-    const uint32_t off = (uint32_t)((tile * KS * 64 + lane) * 16);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "+v"(bh[ks]) : "v"(off), "s"(bh_rs), "n"(1024 * ks) : "memory");
-      asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "+v"(bl[ks]) : "v"(off), "s"(bl_rs), "n"(1024 * ks) : "memory");
-    }
-  };
-#define SE3_WAIT_B16(CNT)                                                                                          \
-  do {                                                                                                             \
-    if constexpr (KS == 2)                                                                                         \
-      asm volatile("s_waitcnt vmcnt(" #CNT ")" : "+v"(bh[0]), "+v"(bh[1]), "+v"(bl[0]), "+v"(bl[1])::"memory");    \
-    else                                                                                                           \
-      asm volatile("s_waitcnt vmcnt(" #CNT ")"                                                                     \
-                   : "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[KS - 2]), "+v"(bh[KS - 1]), "+v"(bl[0]), "+v"(bl[1]),       \
-                     "+v"(bl[KS - 2]), "+v"(bl[KS - 1])::"memory");                                                \
-  } while (0)
-  // rows of C: 72 bytes per channel (n = channels * 32 columns); rows >= m fall outside the buffer and are dropped
-  const int64_t rb = (int64_t)n / 32 * 72;
-  const int64_t c_bytes = (m - row0) * rb;
-  const __amdgpu_buffer_rsrc_t c_rs = __builtin_amdgcn_make_buffer_rsrc(
-      c + row0 * rb, (short)0, (int)(uint32_t)(c_bytes > 0xffffffffll ? 0xffffffffll : c_bytes), 0x00020000);
-  // blockIdx.y selects a contiguous range of mega tiles; the mega tiles of a strip are walked from a rotated start
-  const int n_mega_all = n / 256;
-  const int per = (n_mega_all + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int mega_lo = (int)blockIdx.y * per;
-  const int n_mega = min(per, n_mega_all - mega_lo);
-  if (n_mega <= 0) return;
-  int mg = mega_lo + (int)(((blockIdx.x * 4 + wave) * 5u) % (unsigned)n_mega);
-  // store-side lane roles: lane l writes 16 bytes of row (l >> 2) + 16 i, piece l & 3
-  const int s_row = lane >> 2, s_pc = lane & 3;
-  load_b(mg * 8);
-  SE3_WAIT_B16(0);
-  for (int it = 0; it < n_mega; ++it) {
-    const int mg_next = mg + 1 < mega_lo + n_mega ? mg + 1 : mega_lo;
-#pragma unroll
-    for (int tl = 0; tl < 8; ++tl) {
-      const int tile = mg * 8 + tl;
-      f32x16 acc = zero16();
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) acc = mfma_bf16x3(a_hi[ks], a_lo[ks], bh[ks], bl[ks], acc);
-      load_b(tl < 7 ? tile + 1 : mg_next * 8);  // in flight during the epilogue (after the last tile: one unused fetch)
-      // block = 4 adjacent lanes of one register: maximum by two DPP steps, exponent, mantissa
-      const int blk = (tile & 7) * 8 + (rl >> 2);  // block index inside the mega tile: (channel quad & 1) * 32 + basis function
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float mx = fabsf(acc[r]);
-        mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, mx), 0xb1, 0xf, 0xf, true)));  // quad_perm [1,0,3,2]
-        mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, mx), 0x4e, 0xf, 0xf, true)));  // quad_perm [2,3,0,1]
-        int e = __builtin_amdgcn_frexp_expf(mx);
-        e = e < -kT16ExpBias ? -kT16ExpBias : (e > 127 ? 127 : e);
-        typedef short s16x2 __attribute__((ext_vector_type(2)));
-        const s16x2 q = __builtin_amdgcn_cvt_pknorm_i16(__builtin_ldexpf(acc[r], -e), 0.f);
-        st_m[wave][acc_row(r, h)][rl] = (uint16_t)q[0];
-        if ((rl & 3) == 0) st_e[wave][acc_row(r, h)][t16_exp_pos(blk) & 63] = (uint8_t)(e + kT16ExpBias);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(&st_m[wave][s_row + 16 * i][s_pc * 8]);
-        __builtin_amdgcn_raw_buffer_store_b128(v, c_rs, (int)((s_row + 16 * i) * rb + s_pc * 16), tile * 64, 0);
-      }
-      if (tl == 7) {  // the mega tile's exponent line of every row: 64 bytes
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const u32x4 v = *reinterpret_cast<const u32x4*>(&st_e[wave][s_row + 16 * i][s_pc * 16]);
-          __builtin_amdgcn_raw_buffer_store_b128(v, c_rs, (int)((s_row + 16 * i) * rb + s_pc * 16), n * 2 + mg * 64, 0);
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();  // the staging rows are free for the next tile
-      if (tl == 7) SE3_WAIT_B16(4);     // the loads are older than this tile's 2 (+ 2 exponent) stores
-      else SE3_WAIT_B16(2);
-    }
-    mg = mg_next;
-  }
-#undef SE3_WAIT_B16
-}
-
 // out = alpha * sum_z partials[z]  (fp32 or packed words)
 template <bool OUT_PACKED>
 __global__ void reduce_splits_kernel(const float* __restrict__ partials, void* __restrict__ out, int64_t count,
@@ -1163,38 +1016,17 @@ int launch_prep_weights(const float* w, int c_in, int kb, int c_out, int mode, u
 // short-k, wide-n products (grad_T beyond the strip kernel's k <= 64) the narrow tile keeps more blocks in flight
 int gemm_nn_bf16_col_blocks(int n, int k) { return n > BN && k >= 512 ? 2 : 1; }
 
-// k groups per workgroup of the 3-byte-row kernel (gemm_nn_t24_kernel, KG).  OPT-IN (SE3_NN_KG=2: two groups when the
-// output tiles alone leave the chip under-filled and the super tiles of a workgroup divide evenly): measured in round 5
-// against the split over grid.z it was meant to replace (profiles/r05_nn_kgroups_ab.txt) -- the 18 k-row level of the
-// headline stack 0.327 -> 0.336 ms, its 254-row level 0.069 -> 0.074, the stack +0.8 %, scannet150k_f1 +0.6 %, dfaust_f2
-// -0.9 %: eight wavefronts sharing one CU's LDS pipe and barriers buy no more than the reduction launch they save.
-int gemm_nn_t24_k_groups(int64_t m, int n, int k) {
-  static const int forced = [] {
-    const char* e = getenv("SE3_NN_KG");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced != 2 || k % 128 != 0) return 1;
-  const int bnw = BN * gemm_nn_bf16_col_blocks(n, k);
-  const int64_t tiles = ((m + BM - 1) / BM) * ((n + bnw - 1) / bnw);
-  return tiles > 0 && tiles <= 384 ? 2 : 1;  // beyond 1.5 workgroups per CU the plain form covers its own latencies
-}
-
-int gemm_nn_bf16_splits(int64_t m, int n, int k, int kg) {
+int gemm_nn_bf16_splits(int64_t m, int n, int k) {
   const int bnw = BN * gemm_nn_bf16_col_blocks(n, k);
   const int64_t tiles = ((m + BM - 1) / BM) * ((n + bnw - 1) / bnw);
   const int nkt = (k + BK - 1) / BK;
-  const int target = 512 / kg;  // workgroups aimed at (two per CU; one of eight wavefronts); 1024 and 256 measured slower on the 9 k-point level
+  const int target = 512;  // workgroups aimed at (two per CU); 1024 and 256 measured slower on the 9 k-point level
   if (tiles < 1 || tiles >= target / 2 || nkt < 8) return 1;  // (tiles = 0: an empty cloud)
   // at most `target` workgroups (one more split than fits starts a second, nearly empty round: 144 tiles x 4 splits =
   // 576 on 512 slots took as long as two full rounds), at least 4 k-tiles per split
   int64_t s_max = target / tiles;
-  if (s_max > nkt / (4 * kg)) s_max = nkt / (4 * kg);
+  if (s_max > nkt / 4) s_max = nkt / 4;
   if (s_max < 1) s_max = 1;
-  static const int forced = [] {  // A/B knob: SE3_NN_SPLITS=n forces the split count (clamped to what the shape allows)
-    const char* e = getenv("SE3_NN_SPLITS");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced > 0) return (int)(forced < s_max ? forced : s_max);
   // Cost model in microseconds, fitted to the stage times of the small and mid-sized levels (profiles/r03_nn_split_sweep.txt:
   // forced split counts on the 18 k-row headline level and the 4 k-row / 128-channel DFaust level): a block's k loop is
   // serial at ~0.75 us per 32-k tile (1.1 us with 128-column tiles); the A stream (~3.5 bytes per element) runs at the
@@ -1211,7 +1043,7 @@ int gemm_nn_bf16_splits(int64_t m, int n, int k, int kg) {
     const int per = (int)((nkt + s - 1) / s);
     const int s_eff = (nkt + per - 1) / per;
     const double fill = (double)(tiles * s_eff) / (double)target;
-    const double t_loop = per * t_tile / kg, t_stream = a_bytes / (rate * (fill < 1.0 ? fill : 1.0));
+    const double t_loop = per * t_tile, t_stream = a_bytes / (rate * (fill < 1.0 ? fill : 1.0));
     const double cost = (t_loop > t_stream ? t_loop : t_stream) + (s_eff > 1 ? 12.0 + s_eff * out_bytes * 0.5e-6 : 0.0);
     if (cost < best_cost) best_cost = cost, best = s_eff;
   }
@@ -1225,31 +1057,11 @@ bool gemm_strip_bf16_applicable(int64_t m, int n, int k) {
          (m + 128) * (int64_t)k * 4 < (1ll << 32) - 64 && (int64_t)(n + 64) * kp * 2 < (1ll << 32) - 64;
 }
 
-// T16 output: whole mega tiles of 256 columns, k of one or two 32-steps, rows addressed with 32-bit byte offsets
-bool gemm_strip_t16_applicable(int64_t m, int n, int k) {
-  const int kp = (k + 31) / 32 * 32;
-  return gemm_strip_bf16_applicable(m, n, k) && (kp == 32 || kp == 64) && k % 8 == 0 && n % 256 == 0 &&
-         (m + 128) * ((int64_t)n / 32 * 72) < (1ll << 32) - 64;
-}
-
 int launch_gemm_strip_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, uint32_t* c,
-                           int64_t m, int n, int k, hipStream_t stream, bool out_t16) {
+                           int64_t m, int n, int k, hipStream_t stream) {
   if (m == 0 || n == 0) return SE3_OK;
   if (!gemm_strip_bf16_applicable(m, n, k)) return SE3_ERR_UNSUPPORTED;
   ProfScope prof(tag, stream);
-  if (out_t16) {
-    if (!gemm_strip_t16_applicable(m, n, k)) return SE3_ERR_UNSUPPORTED;
-    const int64_t rbk = (m + 127) / 128;
-    int split = rbk >= 1024 ? 1 : (int)(1024 / rbk);  // <= 1024 workgroups = one resident round
-    const int n_mega = n / 256;
-    if (split > n_mega) split = n_mega;
-    const dim3 g16((unsigned)rbk, (unsigned)split);
-    if ((k + 31) / 32 * 32 == 32)
-      hipLaunchKernelGGL(gemm_strip_t16_kernel<2>, g16, dim3(256), 0, stream, a, bt_hi, bt_lo, (uint8_t*)c, m, n, k);
-    else
-      hipLaunchKernelGGL(gemm_strip_t16_kernel<4>, g16, dim3(256), 0, stream, a, bt_hi, bt_lo, (uint8_t*)c, m, n, k);
-    return check_launch();
-  }
   const int64_t row_blocks = (m + 127) / 128;
   int n_split = row_blocks >= 1024 ? 1 : (int)(1024 / row_blocks);  // <= 1024 workgroups = one resident round (4 per CU)
   const int n_tiles = n / 32;
@@ -1271,8 +1083,7 @@ static int gemm_nn_bf16_rows(const uint32_t* a, const uint16_t* bt_hi, const uin
   const bool a24 = afmt == 1, a16 = afmt == 2;  // A rows: 0 packed words, 1 3-byte rows, 2 T16 (common.h)
   const int kp = (k + 31) / 32 * 32;
   const int nkt = kp / BK;
-  const int kg = a24 ? gemm_nn_t24_k_groups(m, n, k) : 1;
-  int splits = split_ws ? gemm_nn_bf16_splits(m, n, k, kg) : 1;
+  int splits = split_ws ? gemm_nn_bf16_splits(m, n, k) : 1;
   const int per = (nkt + splits - 1) / splits;
   splits = (nkt + per - 1) / per;
   const int nbw = gemm_nn_bf16_col_blocks(n, k);
@@ -1285,15 +1096,14 @@ static int gemm_nn_bf16_rows(const uint32_t* a, const uint16_t* bt_hi, const uin
     return SE3_ERR_UNSUPPORTED;
   int st_per = (per + 1) / 2;  // 3-byte / T16 rows: the kernels walk super tiles of 64 k
   if (a16) st_per = (st_per + 3) / 4 * 4;  // whole mega tiles per split
-  if (kg == 2) st_per = (st_per + 1) / 2 * 2;  // two k groups: an even number of super tiles per workgroup (k % 128 == 0)
   if (a24 || a16) splits = (k / 64 + st_per - 1) / st_per;
   const dim3 grid24((unsigned)((m + BM - 1) / BM), grid.y, (unsigned)splits);
 #define SE3_NN_LAUNCH(MODE, F, NBV, OUT)                                                                              \
   hipLaunchKernelGGL((gemm_nn_bf16_kernel<MODE, F, NBV>), grid, dim3(256), 0, stream, a, bt_hi, bt_lo, (void*)(OUT), m, n, \
                      k, kp, per, alpha_num, alpha_scale)
-#define SE3_NN_LAUNCH24_KG(MODE, NBV, KGV, OUT)                                                                       \
+#define SE3_NN_LAUNCH24(MODE, NBV, OUT)                                                                               \
   do {                                                                                                                \
-    constexpr int lds_bytes = gemm_nn_t24_lds_bytes(NBV, KGV);                                                         \
+    constexpr int lds_bytes = gemm_nn_t24_lds_bytes(NBV);                                                              \
     if (lds_bytes > 64 * 1024) {  /* beyond the default dynamic-LDS limit: raised once per (device, instantiation) -- a \
                                      runtime that keeps the attribute per device must see it on every device the      \
                                      process uses; a failure is not cached */                                          \
@@ -1302,19 +1112,14 @@ static int gemm_nn_bf16_rows(const uint32_t* a, const uint16_t* bt_hi, const uin
       if (hipGetDevice(&dev_) != hipSuccess) return SE3_ERR_LAUNCH;                                                   \
       const uint64_t bit_ = 1ull << (dev_ & 63);                                                                      \
       if (!(raised.load(std::memory_order_relaxed) & bit_)) {                                                         \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nn_t24_kernel<MODE, NBV, KGV>),                   \
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nn_t24_kernel<MODE, NBV>),                        \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)                 \
           return SE3_ERR_LAUNCH;                                                                                      \
         raised.fetch_or(bit_, std::memory_order_relaxed);                                                             \
       }                                                                                                               \
     }                                                                                                                 \
-    hipLaunchKernelGGL((gemm_nn_t24_kernel<MODE, NBV, KGV>), grid24, dim3(256 * KGV), lds_bytes, stream, (const uint8_t*)a, \
+    hipLaunchKernelGGL((gemm_nn_t24_kernel<MODE, NBV>), grid24, dim3(256), lds_bytes, stream, (const uint8_t*)a,       \
                        bt_hi, bt_lo, (void*)(OUT), m, n, k, st_per, alpha_num, alpha_scale);                          \
-  } while (0)
-#define SE3_NN_LAUNCH24(MODE, NBV, OUT)                    \
-  do {                                                     \
-    if (kg == 2) SE3_NN_LAUNCH24_KG(MODE, NBV, 2, OUT);    \
-    else SE3_NN_LAUNCH24_KG(MODE, NBV, 1, OUT);            \
   } while (0)
 #define SE3_NN_LAUNCH16(MODE, NBV, OUT)                                                                               \
   hipLaunchKernelGGL((gemm_nn_t16_kernel<MODE, NBV>), grid24, dim3(256), 0, stream, (const uint8_t*)a, bt_hi, bt_lo,   \
@@ -1350,7 +1155,6 @@ static int gemm_nn_bf16_rows(const uint32_t* a, const uint16_t* bt_hi, const uin
 #undef SE3_NN
 #undef SE3_NN_LAUNCH
 #undef SE3_NN_LAUNCH24
-#undef SE3_NN_LAUNCH24_KG
 #undef SE3_NN_LAUNCH16
   return check_launch();
 }
@@ -1378,9 +1182,7 @@ int launch_gemm_nn_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_h
 }
 
 size_t gemm_nn_bf16_split_bytes(int64_t m, int n, int k) {
-  // the caller does not know the row format yet: room for whichever form (one or two k groups) splits further
-  const int s1 = gemm_nn_bf16_splits(m, n, k, 1), s2 = gemm_nn_bf16_splits(m, n, k, gemm_nn_t24_k_groups(m, n, k));
-  const int s = s1 > s2 ? s1 : s2;  // (rounding the super tiles per split up to an even count can only remove a split)
+  const int s = gemm_nn_bf16_splits(m, n, k);
   return s > 1 ? (size_t)s * m * n * 4 : 0;
 }
 

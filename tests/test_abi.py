@@ -80,7 +80,7 @@ def test_intermediate_format_query(built_library):
     rb = lambda shp, which: lib.se3conv_intermediate_row_bytes(C.byref(shp), which)
     assert [rb(headline, w) for w in range(3)] == [64 * 32 * 3, 64 * 32 * 3, 64 * 32 * 4]
     t16 = _lib.Se3Shape(65536, 65536, 2_000_000, 2, 2, 64, 64, 32, _lib.PRECISIONS["bf16x3_t16"])
-    assert [rb(t16, w) for w in range(3)] == [64 * 72, 64 * 72, 64 * 32 * 4] and [q(t16, w) for w in range(3)] == [2, 2, 4]   # grad_T: opt-in (SE3_T16_GT)
+    assert [rb(t16, w) for w in range(3)] == [64 * 72, 64 * 72, 64 * 32 * 4] and [q(t16, w) for w in range(3)] == [2, 2, 4]   # grad_T: packed words
     wide16 = _lib.Se3Shape(4096, 4096, 60_000, 2, 2, 128, 256, 32, _lib.PRECISIONS["bf16x3_t16"])   # c_out = 256: grad_T by the tiled GEMM, packed words
     assert [rb(wide16, w) for w in range(3)] == [128 * 72, 256 * 72, 128 * 32 * 4]
     wide16b = _lib.Se3Shape(4096, 4096, 60_000, 2, 2, 128, 64, 32, _lib.PRECISIONS["bf16x3_t16"])

@@ -7,7 +7,7 @@ out=gpurun_out/trace_$tag
 mkdir -p $out
 for wl_lv in $*; do
   wl=${wl_lv%%:*}; lv=${wl_lv##*:}
-  SE3_OVERLAP_ROWS=0 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ${wl}_l${lv} -- python3 tools/profile_small_levels.py $wl $lv 20 > $out/${wl}_l${lv}.log 2>&1 || echo "rc=$? $wl_lv"
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ${wl}_l${lv} -- python3 tools/profile_small_levels.py $wl $lv 20 > $out/${wl}_l${lv}.log 2>&1 || echo "rc=$? $wl_lv"
   f=$(find $out -name "${wl}_l${lv}_kernel_stats.csv" | head -1)
   echo "== $wl level $lv"; tail -1 $out/${wl}_l${lv}.log
   python3 - "$f" <<'PY'

@@ -84,8 +84,14 @@ def _as(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return t.detach().to(dtype).contiguous()
 
 
+# every buffer the library writes -- results, saved tensors, cached operands -- is allocated through these two names and
+# `_workspace` (tests/hostile_memory.py swaps all three for guard-banded, 0xFF-filled allocations)
+_empty = torch.empty
+_empty_like = torch.empty_like
+
+
 def _workspace(nbytes: int, device) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    return _empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
 # ----------------------------------------------------------------------------- grid keys (a10, f-2)
@@ -97,7 +103,7 @@ def compute_keys(pts, batch_ids, aabb_min, num_cells, cell_size) -> torch.Tensor
         raise ValueError("compute_keys: only 3-D points are supported")
     dev = pts.device
     n = pts.shape[0]
-    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    keys = _empty(n, dtype=torch.int64, device=dev)
     b = _as(batch_ids, torch.int32)
     mn = _as(aabb_min, torch.float32)
     nc = _as(num_cells, torch.int32).to(dev)
@@ -130,8 +136,8 @@ def batch_aabb(pts, batch_ids, n_batches: Optional[int] = None) -> Tuple[torch.T
     if n_batches is None:
         # one tiny sync, the same one the reference pays with `torch::amax(...).item()` (ball_query.cu:46)
         n_batches = int(b.max().item()) + 1 if b.numel() else 1
-    mn = torch.empty((n_batches, 3), dtype=torch.float32, device=pts.device)
-    mx = torch.empty((n_batches, 3), dtype=torch.float32, device=pts.device)
+    mn = _empty((n_batches, 3), dtype=torch.float32, device=pts.device)
+    mx = _empty((n_batches, 3), dtype=torch.float32, device=pts.device)
     _lib.check(lib.se3_batch_aabb(_ptr(pts, torch.float32, "pts"), _ptr(b, torch.int32, "batch_ids", pts.device),
                                   pts.shape[0], n_batches, _ptr(mn, torch.float32, "aabb_min"),
                                   _ptr(mx, torch.float32, "aabb_max"), _stream(pts.device)), "se3_batch_aabb")
@@ -161,15 +167,15 @@ def _batch_aabb_min_and_cells(pts_src, batch_src, radius: float, n_batches: Opti
         n_batches = int(batch_src.max().item()) + 1 if batch_src.numel() else 1
     dev = pts_src.device
     if box is not None and box[0].shape == (n_batches, 3) and box[0].device == dev:
-        mn = torch.empty((n_batches, 3), dtype=torch.float32, device=dev)
-        num_cells = torch.empty(3, dtype=torch.int32, device=dev)
+        mn = _empty((n_batches, 3), dtype=torch.float32, device=dev)
+        num_cells = _empty(3, dtype=torch.int32, device=dev)
         _lib.check(lib.se3_ball_query_grid_from_box(_ptr(box[0], torch.float32, "box_min", dev), _ptr(box[1], torch.float32, "box_max", dev),
                                                     n_batches, float(radius), _ptr(mn, torch.float32, "aabb_min"),
                                                     _ptr(num_cells, torch.int32, "num_cells"), _stream(dev)),
                    "se3_ball_query_grid_from_box")
         return mn, num_cells
-    box = torch.empty((2, n_batches, 3), dtype=torch.float32, device=dev)  # [0] = shifted minimum, [1] = scratch
-    num_cells = torch.empty(3, dtype=torch.int32, device=dev)
+    box = _empty((2, n_batches, 3), dtype=torch.float32, device=dev)  # [0] = shifted minimum, [1] = scratch
+    num_cells = _empty(3, dtype=torch.int32, device=dev)
     _lib.check(lib.se3_ball_query_grid(
         _ptr(pts_src, torch.float32, "pts_src"), _ptr(batch_src, torch.int32, "batch_src", dev), pts_src.shape[0],
         n_batches, float(radius), C.c_void_p(box[0].data_ptr()), C.c_void_p(box[1].data_ptr()),
@@ -194,7 +200,7 @@ def ball_query(pts_src, pts_dst, batch_src, batch_dst, radius: float,
     n_src, n_dst = pts_src.shape[0], pts_dst.shape[0]
     if n_dst == 0 or n_src == 0:
         return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(n_dst, dtype=torch.int32, device=dev)
-    ends = torch.empty(n_dst, dtype=torch.int32, device=dev)  # every entry is written by the count phase
+    ends = _empty(n_dst, dtype=torch.int32, device=dev)  # every entry is written by the count phase
     # small source sets are searched all-pairs by the library: no boxes / cell grid to prepare
     mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if lib.se3_ball_query_needs_grid(n_src) else (None, None)
     nbytes = lib.se3_ball_query_workspace_bytes(n_src, n_dst)
@@ -206,7 +212,7 @@ def ball_query(pts_src, pts_dst, batch_src, batch_dst, radius: float,
         n_src, n_dst, C.c_void_p(ws.data_ptr()), ws.numel(), _ptr(ends, i32, "ends"), _stream(dev)),
         "se3_ball_query_count")
     n_edges = int(ends[-1].item())
-    neighbors = torch.empty((n_edges, 2), dtype=torch.int32, device=dev)
+    neighbors = _empty((n_edges, 2), dtype=torch.int32, device=dev)
     _lib.check(lib.se3_ball_query_store(
         _ptr(pts_dst, f32, "pts_dst"), _ptr(bd, i32, "batch_dst"), float(radius), n_src, n_dst,
         C.c_void_p(ws.data_ptr()), ws.numel(), _ptr(ends, i32, "ends"), n_edges,
@@ -244,7 +250,7 @@ class SourceGrids:
             return hit[1], True
         self.grids.pop(float(radius), None)
         self.params.pop(float(radius), None)
-        return torch.empty(int(nbytes), dtype=torch.uint8, device=device), False
+        return _empty(int(nbytes), dtype=torch.uint8, device=device), False
 
     def commit(self, key, radius, buf, params):
         """Keep ``buf`` as the grid of ``key`` for this radius, with its grid parameters: after the library call that
@@ -309,13 +315,13 @@ def ball_query_bounded(pts_src, pts_dst, batch_src, batch_dst, radius: float, ca
             raise ValueError(f"neighbors_out must be a contiguous int32 [{int(capacity)}, 2] tensor")
         neighbors = neighbors_out
     else:
-        neighbors = torch.empty((int(capacity), 2), dtype=i32, device=dev)
-    sources = torch.empty(int(capacity), dtype=i32, device=dev) if want_sources else None
-    ends = torch.empty(n_dst, dtype=i32, device=dev)
+        neighbors = _empty((int(capacity), 2), dtype=i32, device=dev)
+    sources = _empty(int(capacity), dtype=i32, device=dev) if want_sources else None
+    ends = _empty(n_dst, dtype=i32, device=dev)
     if n_dst == 0:
         info = torch.zeros(2, dtype=i32, device=dev)
         return (neighbors, ends, info, sources) if want_sources else (neighbors, ends, info)
-    info = torch.empty(2, dtype=i32, device=dev)  # both words are written by the store pass
+    info = _empty(2, dtype=i32, device=dev)  # both words are written by the store pass
     needs_grid, ws_bytes, grid_bytes = _ball_query_sizes(n_src, n_dst)
     ws = _workspace(ws_bytes, dev)
     if grids is not None and needs_grid and src_box is not None and SHARED_GRIDS and not torch.cuda.is_current_stream_capturing():
@@ -373,9 +379,9 @@ def csr_transpose(neighbors_i32: torch.Tensor, n_src: int, n_valid: Optional[tor
     lib = _lib.load()
     dev = neighbors_i32.device
     e = neighbors_i32.shape[0]
-    t_samples = torch.empty(e, dtype=torch.int32, device=dev)
-    t_ends = torch.empty(n_src, dtype=torch.int32, device=dev)  # every entry is written by the library
-    t_ids = torch.empty(e, dtype=torch.int32, device=dev) if want_edge_ids else None
+    t_samples = _empty(e, dtype=torch.int32, device=dev)
+    t_ends = _empty(n_src, dtype=torch.int32, device=dev)  # every entry is written by the library
+    t_ids = _empty(e, dtype=torch.int32, device=dev) if want_edge_ids else None
     ws = _workspace(lib.se3_csr_transpose_workspace_bytes(e), dev)
     _lib.check(lib.se3_csr_transpose_bounded(_ptr(neighbors_i32, torch.int32, "neighbors"), e,
                                              _ptr(n_valid, torch.int32, "n_valid", dev), n_src, C.c_void_p(ws.data_ptr()),
@@ -411,12 +417,12 @@ def grid_subsample(pts, batch_ids, cell_size: float, n_batches: Optional[int] = 
     if n_batches is None:
         n_batches = int(b.max().item()) + 1 if n else 1
     i32 = torch.int32
-    cell_ids = torch.empty(n, dtype=i32, device=dev)
-    sorted_ids = torch.empty(n, dtype=i32, device=dev)
-    cell_ends = torch.empty(n, dtype=i32, device=dev)
+    cell_ids = _empty(n, dtype=i32, device=dev)
+    sorted_ids = _empty(n, dtype=i32, device=dev)
+    cell_ends = _empty(n, dtype=i32, device=dev)
     n_cells = torch.zeros(1, dtype=i32, device=dev)
-    cell_pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    cell_bid = torch.empty(n, dtype=i32, device=dev)
+    cell_pts = _empty((n, 3), dtype=torch.float32, device=dev)
+    cell_bid = _empty(n, dtype=i32, device=dev)
     ws = _workspace(lib.se3_grid_subsample_workspace_bytes(n, n_batches), dev)
     _lib.check(lib.se3_grid_subsample(
         _ptr(pts, torch.float32, "pts"), _ptr(b, i32, "batch_ids", dev), n, n_batches, float(cell_size),
@@ -434,8 +440,8 @@ def _rows2d(t):
 def _segment_pool(cells: GridCells, x2, mode: int, want_arg: bool):
     lib = _lib.load()
     c = x2.shape[1]
-    out = torch.empty((cells.n_cells, c), dtype=torch.float32, device=x2.device)
-    arg = torch.empty((cells.n_cells, c), dtype=torch.int32, device=x2.device) if want_arg else None
+    out = _empty((cells.n_cells, c), dtype=torch.float32, device=x2.device)
+    arg = _empty((cells.n_cells, c), dtype=torch.int32, device=x2.device) if want_arg else None
     _lib.check(lib.se3_segment_pool(_ptr(x2, torch.float32, "src"), _ptr(cells.sorted_ids, torch.int32, "sorted_ids"),
                                     _ptr(cells.cell_ends, torch.int32, "cell_ends"), cells.n_cells, c, mode,
                                     _ptr(out, torch.float32, "out"), _ptr(arg, torch.int32, "arg"), _stream(x2.device)),
@@ -446,7 +452,7 @@ def _segment_pool(cells: GridCells, x2, mode: int, want_arg: bool):
 def _segment_unpool(cells: GridCells, v2, arg, mode: int):
     lib = _lib.load()
     n, c = cells.cell_ids.shape[0], v2.shape[1]
-    out = torch.empty((n, c), dtype=torch.float32, device=v2.device)
+    out = _empty((n, c), dtype=torch.float32, device=v2.device)
     _lib.check(lib.se3_segment_unpool(_ptr(v2, torch.float32, "cell_vals"), _ptr(cells.cell_ids, torch.int32, "cell_ids"),
                                       _ptr(cells.cell_ends, torch.int32, "cell_ends"), _ptr(arg, torch.int32, "arg"),
                                       n, c, mode, _ptr(out, torch.float32, "out"), _stream(v2.device)), "se3_segment_unpool")
@@ -466,8 +472,8 @@ def grid_pick(cells: GridCells, u: Optional[torch.Tensor] = None) -> Tuple[torch
     if u.shape != (cells.n_cells,):
         raise ValueError(f"grid_pick: {tuple(u.shape)} random numbers for {cells.n_cells} cells")
     i32 = torch.int32
-    ids = torch.empty(cells.n_cells, dtype=i32, device=dev)
-    picked = torch.empty(cells.n_cells, dtype=i32, device=dev)
+    ids = _empty(cells.n_cells, dtype=i32, device=dev)
+    picked = _empty(cells.n_cells, dtype=i32, device=dev)
     _lib.check(lib.se3_grid_pick(_ptr(cells.cell_ends, i32, "cell_ends", dev), _ptr(cells.sorted_ids, i32, "sorted_ids"),
                                  _ptr(u, torch.float32, "u"), cells.n_cells, _ptr(ids, i32, "ids"),
                                  _ptr(picked, i32, "picked"), _stream(dev)), "se3_grid_pick")
@@ -485,7 +491,7 @@ def rows_gather(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     if not src.is_cuda:
         raise ValueError("rows_gather: expected a GPU tensor (the HIP path has no CPU fallback)")
     src = src.detach().contiguous()
-    out = torch.empty((idx.shape[0],) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    out = _empty((idx.shape[0],) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
     if idx.shape[0] and out.numel():
         _rows_move(_lib.load().se3_rows_gather, "se3_rows_gather", src, idx, out)
     return out
@@ -575,8 +581,8 @@ class FramePool(torch.autograd.Function):
         if x2.shape[0] % n_frames:
             raise ValueError("feature_pooling: rows are not a multiple of the frame count")
         n, c = x2.shape[0] // n_frames, x2.shape[1]
-        out = torch.empty((n, c), dtype=torch.float32, device=x2.device)
-        arg = torch.empty((n, c), dtype=torch.int32, device=x2.device) if mode in (1, 2) else None
+        out = _empty((n, c), dtype=torch.float32, device=x2.device)
+        arg = _empty((n, c), dtype=torch.int32, device=x2.device) if mode in (1, 2) else None
         _lib.check(lib.se3_frame_pool(_ptr(x2, torch.float32, "x"), n, n_frames, c, mode, _ptr(out, torch.float32, "out"),
                                       _ptr(arg, torch.int32, "arg"), _stream(x2.device)), "se3_frame_pool")
         ctx.mode, ctx.arg, ctx.f, ctx.shape = mode, arg, n_frames, x.shape
@@ -587,7 +593,7 @@ class FramePool(torch.autograd.Function):
         lib = _lib.load()
         g2 = _rows2d(_as(g, torch.float32))
         n, c = g2.shape
-        gx = torch.empty((n * ctx.f, c), dtype=torch.float32, device=g2.device)
+        gx = _empty((n * ctx.f, c), dtype=torch.float32, device=g2.device)
         _lib.check(lib.se3_frame_unpool(_ptr(g2, torch.float32, "grad_out"), _ptr(ctx.arg, torch.int32, "arg"), n, ctx.f, c,
                                         ctx.mode, _ptr(gx, torch.float32, "grad_x"), _stream(g2.device)), "se3_frame_unpool")
         return gx.reshape(ctx.shape), None, None
@@ -625,7 +631,7 @@ def knn_query(pts, batch_ids, k: int, n_batches: Optional[int] = None, method: s
     if method not in ("auto", "grid", "scan"):
         raise ValueError(f"knn_query: unknown method {method!r}")
     n, dev = pts.shape[0], pts.device
-    out = torch.empty((n, int(k)), dtype=torch.int32, device=dev)
+    out = _empty((n, int(k)), dtype=torch.int32, device=dev)
     f32, i32 = torch.float32, torch.int32
     if not 1 <= int(k) <= 64:
         raise ValueError(f"knn_query: k = {k}; the kernels keep at most 64 neighbours per point (the reference's own "
@@ -640,9 +646,9 @@ def knn_query(pts, batch_ids, k: int, n_batches: Optional[int] = None, method: s
     # lines of BallQuery.py:34-38 compute -- as a dozen torch calls and a bincount they cost more than the search)
     box_mn, mx = box if box is not None else batch_aabb(pts, b, n_batches)
     nb = box_mn.shape[0]
-    mn = torch.empty((nb, 3), dtype=f32, device=dev)
-    num_cells = torch.empty(3, dtype=i32, device=dev)
-    cell3 = torch.empty(3, dtype=f32, device=dev)
+    mn = _empty((nb, 3), dtype=f32, device=dev)
+    num_cells = _empty(3, dtype=i32, device=dev)
+    cell3 = _empty(3, dtype=f32, device=dev)
     _lib.check(lib.se3_knn_grid_params(_ptr(b, i32, "batch_ids", dev), n, _ptr(box_mn, f32, "box_min", dev),
                                        _ptr(mx, f32, "box_max", dev), nb, int(k), float(KNN_CELL_FACTOR), _ptr(mn, f32, "aabb_min"),
                                        _ptr(num_cells, i32, "num_cells"), _ptr(cell3, f32, "cell_size"), _stream(dev)),
@@ -668,7 +674,7 @@ def knn_query_pair(pts_src, batch_src, pts_q, batch_q, k: int) -> torch.Tensor:
     if not 1 <= int(k) <= 64:
         raise ValueError(f"knn_query_pair: k = {k}; at most 64 neighbours per point")
     dev = pq.device
-    out = torch.empty((pq.shape[0], int(k)), dtype=i32, device=dev)
+    out = _empty((pq.shape[0], int(k)), dtype=i32, device=dev)
     _lib.check(lib.se3_knn_query_pair(_ptr(ps, f32, "pts_src", dev), _ptr(bs, i32, "batch_src", dev), ps.shape[0],
                                       _ptr(pq, f32, "pts_q"), _ptr(bq, i32, "batch_q", dev), pq.shape[0], int(k),
                                       _ptr(out, i32, "out"), _stream(dev)), "se3_knn_query_pair")
@@ -698,7 +704,7 @@ def pca_frames(pts, knn_ids, axis_fixed=None) -> torch.Tensor:
     if axis not in (-1, 1, 2):
         raise ValueError(f"axis_fixed = {axis_fixed}")
     nf = 4 if axis < 0 else 2
-    frames = torch.empty((n, nf, 9), dtype=torch.float32, device=pts.device)
+    frames = _empty((n, nf, 9), dtype=torch.float32, device=pts.device)
     _lib.check(lib.se3_pca_frames(_ptr(pts, torch.float32, "pts"), _ptr(ids, torch.int32, "knn", pts.device), n, k, axis,
                                   _ptr(frames, torch.float32, "frames"), _stream(pts.device)), "se3_pca_frames")
     return frames
@@ -717,7 +723,7 @@ def shuffle_frames(all_frames, n_frames: int, draws=None) -> torch.Tensor:
     draws = _as(draws, torch.float32)
     if tuple(draws.shape) != (n, n_all):
         raise ValueError(f"shuffle_frames: draws {tuple(draws.shape)}, expected {(n, n_all)}")
-    out = torch.empty((n, int(n_frames), all_frames.shape[2]), dtype=torch.float32, device=dev)
+    out = _empty((n, int(n_frames), all_frames.shape[2]), dtype=torch.float32, device=dev)
     if all_frames.shape[2] != 9:
         raise ValueError("shuffle_frames: frames are [N, n_all, 9]")
     _lib.check(lib.se3_shuffle_frames(_ptr(all_frames, torch.float32, "all_frames"), _ptr(draws, torch.float32, "draws", dev), n,
@@ -744,7 +750,7 @@ class PreparedRecords:
         if key != self.key:
             rows = frames.shape[0] * frames.shape[1]
             if self.tensor is None or self.tensor.shape[0] != rows or self.tensor.device != pts.device:
-                self.tensor = torch.empty((rows, 16), dtype=torch.float32, device=pts.device)
+                self.tensor = _empty((rows, 16), dtype=torch.float32, device=pts.device)
             self.key, self.valid, self.capture = key, False, None
         return self
 
@@ -932,10 +938,10 @@ def se3conv_forward(geom: ConvGeometry, feat, proj_axes, proj_biases, conv_weigh
                          f"({geom.pts_in.shape[0] * geom.frames_in.shape[1]}, {c_in})")
     shp = geom.shape(c_in, c_out, kb, precision)
     rows = geom.pts_out.shape[0] * geom.frames_out.shape[1]
-    out = torch.empty((rows, c_out), dtype=f32, device=dev)
+    out = _empty((rows, c_out), dtype=f32, device=dev)
     # T is kept for the weight gradient only on the K = 32 kernels' own layout; other K run as slices of 32 inside the
     # library, which recomputes T in backward (include/se3conv.h)
-    t_save = torch.empty((rows, c_in, kb), dtype=f32, device=dev) if (save_t and kb == 32) else None
+    t_save = _empty((rows, c_in, kb), dtype=f32, device=dev) if (save_t and kb == 32) else None
     ws = _workspace(lib.se3conv_fwd_workspace_bytes(C.byref(shp), 1 if save_t else 0), dev)
     rho_t, nu_t = _scalar(rho, "rho", dev), _scalar(nu, "nu", dev)
     prep, filled, capture = _prepared(geom, feat_words, False)
@@ -963,10 +969,10 @@ def se3conv_backward(geom: ConvGeometry, feat, proj_axes, proj_biases, conv_weig
     g = _as(grad_out, f32)
     c_in, kb, c_out = w.shape
     shp = geom.shape(c_in, c_out, kb, precision)
-    d_x = torch.empty_like(feat) if want_feat else None
-    d_a = torch.empty_like(a) if want_params else None
-    d_b = torch.empty_like(b) if want_params else None
-    d_w = torch.empty_like(w) if want_params else None
+    d_x = _empty_like(feat) if want_feat else None
+    d_a = _empty_like(a) if want_params else None
+    d_b = _empty_like(b) if want_params else None
+    d_w = _empty_like(w) if want_params else None
     t_samples, t_ends = geom.transpose() if want_feat else (None, None)
     ws = _workspace(lib.se3conv_bwd_workspace_bytes(C.byref(shp), int(want_feat), int(want_params),
                                                     int(t_save is not None)), dev)
@@ -1007,7 +1013,7 @@ class SE3ConvFunction(torch.autograd.Function):
         # them again): one split per step instead of two, for one more word per feature kept
         fw = None
         if need_params and ctx.precision != "fp32" and conv_weights.shape[1] == 32 and feat.is_cuda:
-            fw = torch.empty(feat.numel(), dtype=torch.int32, device=feat.device)
+            fw = _empty(feat.numel(), dtype=torch.int32, device=feat.device)
         out, t_save = se3conv_forward(geom, feat, proj_axes, proj_biases, conv_weights, rho, nu,
                                       save_t=save_t, precision=ctx.precision, feat_words=fw)
         ctx.geom = geom
@@ -1046,8 +1052,8 @@ def rot_tensors(geom: ConvGeometry, rho, rel_rot: str = "6D"):
     shp = geom.shape(1, 1, 32)
     ff = shp.f_in * shp.f_out
     e2 = geom.neighbors.shape[0] * ff
-    desc = torch.empty((e2, dims), dtype=torch.float32, device=dev)
-    fe_nb = torch.empty((e2, 2), dtype=torch.int32, device=dev)
+    desc = _empty((e2, dims), dtype=torch.float32, device=dev)
+    fe_nb = _empty((e2, 2), dtype=torch.int32, device=dev)
     fe_ends = torch.zeros(geom.pts_out.shape[0] * shp.f_out, dtype=torch.int32, device=dev)
     rho_t = _scalar(rho, "rho", dev)
     _lib.check(lib.se3_rot_tensors_rel(*_geom_ptrs(geom), _ptr(rho_t, torch.float32, "rho"), C.byref(shp), mode,
@@ -1069,7 +1075,7 @@ class FeatBasisProj(torch.autograd.Function):
         p_ctx.dtypes = (p_pt_basis.dtype, p_pt_features.dtype)
         dev = feat.device
         rows, ch, kb = ends.shape[0], feat.shape[1], basis.shape[1]
-        out = torch.empty((rows, ch, kb), dtype=f32, device=dev)
+        out = _empty((rows, ch, kb), dtype=f32, device=dev)
         _lib.check(lib.se3_feat_basis_proj(_ptr(basis, f32, "pt_basis", dev), _ptr(feat, f32, "pt_features"),
                                            _ptr(nb, i32, "neighbors", dev), _ptr(ends, i32, "start_ids", dev),
                                            nb.shape[0], rows, feat.shape[0], ch, kb, _ptr(out, f32, "out"),
@@ -1083,8 +1089,8 @@ class FeatBasisProj(torch.autograd.Function):
         basis, feat, nb, ends = p_ctx.saved_tensors
         g = _as(p_grads, f32)
         dev = feat.device
-        g_feat = torch.empty_like(feat)
-        g_basis = torch.empty_like(basis)
+        g_feat = _empty_like(feat)
+        g_basis = _empty_like(basis)
         _lib.check(lib.se3_feat_basis_proj_grad(
             _ptr(basis, f32, "pt_basis", dev), _ptr(feat, f32, "pt_features"), _ptr(nb, i32, "neighbors"),
             _ptr(ends, i32, "start_ids"), _ptr(g, f32, "grads", dev), nb.shape[0], ends.shape[0], feat.shape[0],
@@ -1111,9 +1117,9 @@ class BatchNormTrain(torch.autograd.Function):
             raise ValueError("BatchNormTrain: expected [rows, C] features")
         rows, c = x2.shape
         dev = x2.device
-        y = torch.empty_like(x2)
-        mean = torch.empty(c, dtype=f32, device=dev)
-        invstd = torch.empty(c, dtype=f32, device=dev)
+        y = _empty_like(x2)
+        mean = _empty(c, dtype=f32, device=dev)
+        invstd = _empty(c, dtype=f32, device=dev)
         w = _as(weight, f32) if weight is not None else None
         b = _as(bias, f32) if bias is not None else None
         ws = _glue_ws(c, dev)
@@ -1137,9 +1143,9 @@ class BatchNormTrain(torch.autograd.Function):
         g2 = _as(g, f32)
         rows, c = x2.shape
         dev = x2.device
-        dx = torch.empty_like(x2)
-        dgamma = torch.empty(c, dtype=f32, device=dev)
-        dbeta = torch.empty(c, dtype=f32, device=dev)
+        dx = _empty_like(x2)
+        dgamma = _empty(c, dtype=f32, device=dev)
+        dbeta = _empty(c, dtype=f32, device=dev)
         ws = _glue_ws(c, dev)
         _lib.check(lib.se3_bn_bwd(_ptr(g2, f32, "dy", dev), _ptr(x2, f32, "x"), _ptr(mean, f32, "mean"),
                                   _ptr(invstd, f32, "invstd"), _ptr(w if ctx.has_w else None, f32, "weight"), rows, c,
@@ -1169,7 +1175,7 @@ class SkipDropPath(torch.autograd.Function):
         rb = _as(row_batch, i32) if gate is not None else None
         if gt is not None and rb.shape[0] != rows:
             raise ValueError("SkipDropPath: one batch id per row expected")
-        out = torch.empty_like(x2)
+        out = _empty_like(x2)
         _lib.check(lib.se3_skip_fwd(_ptr(x2, f32, "x"), _ptr(y2, f32, "y", dev), _ptr(ga, f32, "gamma", dev),
                                     _ptr(gt, f32, "gate", dev), float(gate_keep), _ptr(rb, i32, "row_batch", dev), rows, c,
                                     _ptr(out, f32, "out"), _stream(dev)), "se3_skip_fwd")
@@ -1187,8 +1193,8 @@ class SkipDropPath(torch.autograd.Function):
         rows, c = x2.shape
         dev = x2.device
         ng = ctx.needs_input_grad
-        dx = torch.empty_like(x2) if ng[0] else None
-        dgamma = torch.empty(c, dtype=f32, device=dev)
+        dx = _empty_like(x2) if ng[0] else None
+        dgamma = _empty(c, dtype=f32, device=dev)
         ws = _glue_ws(c, dev)
         _lib.check(lib.se3_skip_bwd(_ptr(g2, f32, "g", dev), _ptr(x2, f32, "x"), _ptr(ga, f32, "gamma"),
                                     _ptr(gt if ctx.gated else None, f32, "gate"), ctx.gate_keep,
@@ -1209,7 +1215,7 @@ class BiasGelu(torch.autograd.Function):
         rows, c = z2.shape
         dev = z2.device
         b = _as(bias, f32) if bias is not None else None
-        out = torch.empty_like(z2)
+        out = _empty_like(z2)
         _lib.check(lib.se3_affine_act(_ptr(z2, f32, "z"), C.c_void_p(0), C.c_void_p(0), _ptr(b, f32, "bias", dev), rows, c, 1,
                                       _ptr(out, f32, "out"), _stream(dev)), "se3_affine_act")
         ctx.save_for_backward(z2, b if b is not None else torch.empty(0, device=dev))
@@ -1224,8 +1230,8 @@ class BiasGelu(torch.autograd.Function):
         g2 = _as(g, f32)
         rows, c = z2.shape
         dev = z2.device
-        dz = torch.empty_like(z2)
-        db = torch.empty(c, dtype=f32, device=dev)
+        dz = _empty_like(z2)
+        db = _empty(c, dtype=f32, device=dev)
         ws = _glue_ws(c, dev)
         _lib.check(lib.se3_bias_gelu_bwd(_ptr(g2, f32, "g", dev), _ptr(z2, f32, "z"), _ptr(b if ctx.has_b else None, f32, "bias"),
                                          rows, c, _ptr(dz, f32, "dz"), _ptr(db, f32, "dbias"), C.c_void_p(ws.data_ptr()),
@@ -1260,7 +1266,7 @@ class Linear(torch.autograd.Function):
             rows, n_in = x2.shape
             n_out = weight.shape[0]
             dev = x2.device
-            gw = torch.empty(n_out, n_in, dtype=f32, device=dev)
+            gw = _empty(n_out, n_in, dtype=f32, device=dev)
             ws = _workspace(lib.se3_linear_wgrad_workspace_bytes(rows, n_out, n_in), dev)
             _lib.check(lib.se3_linear_wgrad(_ptr(g2, f32, "grad_y", dev), _ptr(x2, f32, "x"), rows, n_out, n_in,
                                             _ptr(gw, f32, "grad_w"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)),

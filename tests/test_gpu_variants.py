@@ -19,7 +19,8 @@ measurements -- profiles/r02_levels_fused.txt, r02_stream_kernel_ab.txt, r03_mer
 removed in round 3; so were round 3's in-kernel reductions, profiles/r03_in_kernel_reduction_ab.txt.)
 
 One child at a time; each child is an ordinary `pytest -m gpu` run over the golden / random-shape / headline
-tests of tests/test_gpu_parity.py.
+tests of tests/test_gpu_parity.py and over the fused-operator cases of tests/test_gpu_hostile_memory.py (0xFF-filled,
+guard-banded buffers; their names carry `random_shapes`, so the same slice expression selects them).
 """
 import os
 import subprocess
@@ -43,7 +44,8 @@ def test_variant_passes_parity_slice(var):
         name, _, value = part.partition("=")
         env[name] = value or "1"
     proc = subprocess.run(
-        [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-x", "-q",
+        [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"),
+         os.path.join(ROOT, "tests", "test_gpu_hostile_memory.py"), "-m", "gpu", "-x", "-q",
          "-k", SLICE, "-p", "no:cacheprovider"],
         cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     tail = (proc.stdout + proc.stderr)[-2000:]

@@ -107,6 +107,14 @@ SIGNATURES = {
     "se3_profile_tags": (C.c_int, [C.c_char_p, _SZ]),
 }
 
+# the capped ball query, declared in include/se3conv_capped.h (additions inside ABI version 6: the table above and
+# include/se3conv.h stay as they are); must list every symbol that header declares
+CAPPED_SIGNATURES = {
+    "se3_ball_query_capped_workspace_bytes": (_SZ, [_I64, _I64]),
+    "se3_ball_query_capped": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I64, _I64, _I32, _P, _SZ, _I32, _P, _SZ, _I64, _P, _P, _P, _P,
+                                        _P, _I32, C.c_uint32, _P, _P]),
+}
+
 _lib = None
 
 
@@ -124,7 +132,7 @@ def load() -> C.CDLL:
     if lib.se3_abi_version() != ABI_VERSION:  # (checked before the symbols: an older library lacks some of them)
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so

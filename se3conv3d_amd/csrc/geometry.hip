@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "../../include/se3conv_capped.h"
 
 namespace se3 {
 
@@ -153,24 +154,119 @@ __global__ void find_ranges32_kernel(const float* __restrict__ pts_dst, const in
   }
 }
 
+// The predicate of every ball query: length((s - p) * invR) < 1 in fp32, every operation rounded on its own, so that it is
+// bit-identical to the CPU oracle.  The __f*_rn intrinsics do not give that: this toolchain defines __fmul_rn / __fadd_rn
+// as plain `*` / `+`, which the default -ffp-contract=fast fuses (the kernels held two v_fmac_f32), and __fsqrt_rn as the
+// native 1-ulp v_sqrt_f32 -- about one edge in 10^5 differed from the CPU oracle at degrees of 50 and up.  Hence the pragma,
+// and no square root at all: for fp32 d2, sqrt correctly rounded is < 1 iff d2 < 1 (d2 >= 1 gives a root >= 1; the largest
+// d2 below 1 is 1 - 2^-24, whose root 1 - 2^-25 - 2^-51... lies below the midpoint 1 - 2^-25 and rounds to 1 - 2^-24).
+__device__ __forceinline__ bool within_ball(float sx, float sy, float sz, const float4& p, float inv_r) {
+#pragma clang fp contract(off)
+  const float dx = (sx - p.x) * inv_r;
+  const float dy = (sy - p.y) * inv_r;
+  const float dz = (sz - p.z) * inv_r;
+  const float d2 = (dx * dx + dy * dy) + dz * dz;
+  return d2 < 1.0f;
+}
+
+// ---- capped ball query (include/se3conv_capped.h): which of a sample's hits survive a cap of m ------------------------
+// key(s, p) = (h << 32) | p with h = mix(mix(seed ^ mix(s)) + p * 0x9E3779B9), mix = the murmur3 finaliser: the m smallest
+// keys of a sample's hits are kept.  A pure function of (seed, s, p): no order of evaluation enters it.
+__device__ __forceinline__ uint32_t cap_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x85ebca6bu;
+  x ^= x >> 13;
+  x *= 0xc2b2ae35u;
+  x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ uint32_t cap_sample_hash(uint32_t seed, const uint32_t* __restrict__ seed_device, int64_t s) {
+  return cap_mix((seed + (seed_device ? *seed_device : 0u)) ^ cap_mix((uint32_t)s));
+}
+__device__ __forceinline__ uint64_t cap_key(uint32_t sample_hash, int p) {
+  return ((uint64_t)cap_mix(sample_hash + (uint32_t)p * 0x9E3779B9u) << 32) | (uint32_t)p;
+}
+constexpr uint64_t kCapNoKey = ~0ull;  // above every key of a hit (p < 2^31): "not a hit", and the threshold of an uncapped sample
+constexpr int kCapMax = 64;            // one kept key per lane
+
+// The m <= 64 smallest keys a wavefront has seen, ascending across its lanes (lane i: the i-th smallest).
+struct CapKept {
+  uint64_t key, tau;  // tau = key of lane m - 1, wave-uniform: the m-th smallest so far
+  __device__ __forceinline__ void init() { key = tau = kCapNoKey; }
+  // 64 more keys, one per lane (kCapNoKey where the lane has none)
+  __device__ __forceinline__ void add(uint64_t k, int lane, int m) {
+    if (!__any(k < tau)) return;  // nothing of this chunk enters the kept list
+    // bitonic sort of the chunk across the lanes, DESCENDING ...
+#pragma unroll
+    for (int span = 2; span <= 64; span <<= 1) {
+#pragma unroll
+      for (int j = span >> 1; j > 0; j >>= 1) {
+        const uint64_t o = __shfl_xor(k, j);
+        const bool down = (lane & span) == 0;  // (the last span: every lane)
+        const bool take_max = ((lane & j) == 0) == down;
+        k = (take_max == (o > k)) ? o : k;
+      }
+    }
+    // ... so that min(kept ascending, chunk descending) is a bitonic sequence that holds the 64 smallest of the 128 ...
+    key = k < key ? k : key;
+    // ... which six merge stages put in ascending order
+#pragma unroll
+    for (int j = 32; j > 0; j >>= 1) {
+      const uint64_t o = __shfl_xor(key, j);
+      const bool take_min = (lane & j) == 0;
+      key = (take_min == (o < key)) ? o : key;
+    }
+    tau = __shfl(key, m - 1);
+  }
+};
+
 // One wavefront per sample.  MODE 0: counts[s] = #hits.  MODE 1: neighbors[base + j] = (s, source id) for the j-th hit
 // in candidate order, base from the inclusive offsets `ends`.  MODE 2 (capacity-bounded call): the same, slots at or
 // beyond `limit` dropped, the sample's own offset clamped to `limit` in place (its neighbour reads ends[s-1] either
 // way and clamps what it reads), the last sample records the true total and the overflow flag in `info`, and
 // `sources` (optional) receives the source ids alone -- the source-major list of a cloud against itself.
-template <int MODE>
+// CAPPED (store modes of se3_ball_query_capped): a hit is stored iff its key is at most tau[s], the sample's threshold
+// from the threshold pass (kCapNoKey for a sample under the cap); `counts` / `ends` then already hold the capped degrees.
+// MODE 4 (CAPPED only) is that threshold pass: after the count pass it writes degrees[s] = c (optional), and for c > m
+// finds the m smallest keys of the sample's hits, leaves the m-th in tau[s] and replaces counts[s] by m.
+struct CapArgs {
+  int m;
+  uint32_t seed;
+  const uint32_t* seed_device;
+  uint64_t* tau;
+  int32_t* degrees;
+};
+template <int MODE, bool CAPPED = false>
 __global__ __launch_bounds__(256) void scan_candidates_kernel(const float* __restrict__ pts_dst, float inv_r,
                                                               const float4* __restrict__ spts,
                                                               const int2* __restrict__ ranges, int64_t n_dst,
                                                               int32_t* __restrict__ counts, int32_t* __restrict__ ends,
                                                               int32_t* __restrict__ neighbors, int limit,
                                                               int32_t* __restrict__ sources, int32_t* __restrict__ info,
-                                                              const int32_t* __restrict__ order) {
-  constexpr bool STORE = MODE != 0;
+                                                              const int32_t* __restrict__ order, CapArgs cap = CapArgs{}) {
+  static_assert(MODE != 4 || CAPPED, "the threshold pass belongs to the capped query");
+  constexpr bool STORE = MODE != 0 && MODE != 4;
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= n_dst) return;
   const int64_t s = order ? order[w] : w;  // the wavefronts of a workgroup then share their candidate windows
+  uint32_t sample_hash = 0;
+  uint64_t tau = kCapNoKey;
+  CapKept kept;
+  if (CAPPED) {
+    sample_hash = cap_sample_hash(cap.seed, cap.seed_device, s);
+    if (MODE == 4) {
+      const int c = counts[s];
+      if (lane == 0) {
+        if (cap.degrees) cap.degrees[s] = c;
+        if (c <= cap.m) cap.tau[s] = kCapNoKey;
+      }
+      if (c <= cap.m) return;
+      kept.init();
+    } else {
+      tau = cap.tau[s];
+    }
+  }
   const float sx = pts_dst[s * 3], sy = pts_dst[s * 3 + 1], sz = pts_dst[s * 3 + 2];
   int lo[9], pre[10];
   pre[0] = 0;
@@ -205,14 +301,14 @@ __global__ __launch_bounds__(256) void scan_candidates_kernel(const float* __res
       for (int t = 0; t < 9; ++t)
         if (t == o) pos = lo[t] + (c - pre[t]);
       const float4 p = spts[pos];
-      // length((s - p) * invR) < 1, un-fused so that it is bit-identical to the CPU oracle
-      const float dx = __fmul_rn(__fsub_rn(sx, p.x), inv_r);
-      const float dy = __fmul_rn(__fsub_rn(sy, p.y), inv_r);
-      const float dz = __fmul_rn(__fsub_rn(sz, p.z), inv_r);
-      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-      hit = __fsqrt_rn(d2) < 1.0f;
+      hit = within_ball(sx, sy, sz, p, inv_r);
       id = __float_as_int(p.w);
     }
+    if (CAPPED && MODE == 4) {
+      kept.add(hit ? cap_key(sample_hash, id) : kCapNoKey, lane, cap.m);
+      continue;
+    }
+    if (CAPPED) hit = hit && cap_key(sample_hash, id) <= tau;
     const unsigned long long mask = __ballot(hit);
     if (STORE && hit) {
       const int slot = base + found + __popcll(mask & ((1ull << lane) - 1ull));
@@ -223,6 +319,10 @@ __global__ __launch_bounds__(256) void scan_candidates_kernel(const float* __res
       }
     }
     found += __popcll(mask);
+  }
+  if (CAPPED && MODE == 4) {
+    if (lane == 0) cap.tau[s] = kept.tau, counts[s] = cap.m;
+    return;
   }
   if (!STORE && lane == 0) counts[s] = found;
 }
@@ -236,17 +336,20 @@ constexpr int64_t kBqScanAllMax = 2048;
 // the same with clamping / info / sources as scan_candidates_kernel<2>.  MODE 3 (bounded call, few samples): no scan
 // launch at all -- every wavefront sums the counts in front of its sample itself (n_dst / 64 loads per lane), writes the
 // sample's clamped inclusive offset, stores, and the last sample records total + overflow flag.
+// CAPPED / MODE 4: as in scan_candidates_kernel.
 constexpr int64_t kBqInlinePrefixMax = 4096;
-template <int MODE>
+template <int MODE, bool CAPPED = false>
 __global__ __launch_bounds__(256) void scan_all_kernel(const float* __restrict__ pts_src, const int32_t* __restrict__ batch_src,
                                                        float4* __restrict__ recs, const float* __restrict__ pts_dst,
                                                        const int32_t* __restrict__ batch_dst, float inv_r, int n_src,
                                                        int64_t n_dst, int32_t* __restrict__ counts,
                                                        int32_t* __restrict__ ends, int32_t* __restrict__ neighbors,
-                                                       int limit, int32_t* __restrict__ sources, int32_t* __restrict__ info) {
-  constexpr bool STORE = MODE != 0;
+                                                       int limit, int32_t* __restrict__ sources, int32_t* __restrict__ info,
+                                                       CapArgs cap = CapArgs{}) {
+  static_assert(MODE != 4 || CAPPED, "the threshold pass belongs to the capped query");
+  constexpr bool STORE = MODE != 0 && MODE != 4;
   const int lane = threadIdx.x & 63;
-  if (!STORE) {
+  if (MODE == 0) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n_src) recs[t] = make_float4(pts_src[t * 3], pts_src[t * 3 + 1], pts_src[t * 3 + 2], __int_as_float(batch_src[t]));
   }
@@ -254,6 +357,23 @@ __global__ __launch_bounds__(256) void scan_all_kernel(const float* __restrict__
   if (s >= n_dst) return;
   const float sx = pts_dst[s * 3], sy = pts_dst[s * 3 + 1], sz = pts_dst[s * 3 + 2];
   const int sb = batch_dst[s];
+  uint32_t sample_hash = 0;
+  uint64_t tau = kCapNoKey;
+  CapKept kept;
+  if (CAPPED) {
+    sample_hash = cap_sample_hash(cap.seed, cap.seed_device, s);
+    if (MODE == 4) {
+      const int c = counts[s];
+      if (lane == 0) {
+        if (cap.degrees) cap.degrees[s] = c;
+        if (c <= cap.m) cap.tau[s] = kCapNoKey;
+      }
+      if (c <= cap.m) return;
+      kept.init();
+    } else {
+      tau = cap.tau[s];
+    }
+  }
   int found = 0;
   int base = 0;
   if (MODE == 1 || MODE == 2) base = s > 0 ? ends[s - 1] : 0;
@@ -282,15 +402,16 @@ __global__ __launch_bounds__(256) void scan_all_kernel(const float* __restrict__
     bool hit = false;
     if (id < n_src) {
       float4 p;
-      if (STORE) p = recs[id];
+      if (STORE || MODE == 4) p = recs[id];
       else p = make_float4(pts_src[(int64_t)id * 3], pts_src[(int64_t)id * 3 + 1], pts_src[(int64_t)id * 3 + 2],
                            __int_as_float(batch_src[id]));
-      const float dx = __fmul_rn(__fsub_rn(sx, p.x), inv_r);
-      const float dy = __fmul_rn(__fsub_rn(sy, p.y), inv_r);
-      const float dz = __fmul_rn(__fsub_rn(sz, p.z), inv_r);
-      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-      hit = __float_as_int(p.w) == sb && __fsqrt_rn(d2) < 1.0f;
+      hit = __float_as_int(p.w) == sb && within_ball(sx, sy, sz, p, inv_r);
     }
+    if (CAPPED && MODE == 4) {
+      kept.add(hit ? cap_key(sample_hash, id) : kCapNoKey, lane, cap.m);
+      continue;
+    }
+    if (CAPPED) hit = hit && cap_key(sample_hash, id) <= tau;
     const unsigned long long mask = __ballot(hit);
     if (STORE && hit) {
       const int slot = base + found + __popcll(mask & ((1ull << lane) - 1ull));
@@ -301,6 +422,10 @@ __global__ __launch_bounds__(256) void scan_all_kernel(const float* __restrict__
       }
     }
     found += __popcll(mask);
+  }
+  if (CAPPED && MODE == 4) {
+    if (lane == 0) cap.tau[s] = kept.tau, counts[s] = cap.m;
+    return;
   }
   if (!STORE && lane == 0) counts[s] = found;
 }
@@ -833,11 +958,13 @@ extern "C" size_t se3_ball_query_workspace_bytes(int64_t n_src, int64_t n_dst) {
 // in a buffer of its own that outlives the call; grid_valid: it already holds this source cloud's grid for this radius
 // (built by an earlier call with the same pts_src / batch_src / aabb_min / num_cells / radius / key width), so the key,
 // sort and gather launches are skipped.
+// cap (capped call, may be NULL): the threshold pass runs between the count pass and the scan, so that every offset formed
+// afterwards -- by the scan or by the inline prefix of the store pass -- is a capped one.
 static int ball_query_count_impl(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
                                  const int32_t* batch_dst, const float* aabb_min, const int32_t* num_cells,
                                  float radius, int64_t n_src, int64_t n_dst, void* workspace,
                                  size_t workspace_bytes, int32_t* ends, bool skip_scan, int key_bits, void* stream_,
-                                 void* grid = nullptr, bool grid_valid = false) {
+                                 void* grid = nullptr, bool grid_valid = false, const CapArgs* cap = nullptr) {
   if (n_src < 0 || n_dst < 0 || !(radius > 0.f)) return SE3_ERR_INVALID_ARGUMENT;
   if (n_src >= (1ll << 31) || n_dst >= (1ll << 31) / 9) return SE3_ERR_UNSUPPORTED;
   if (n_dst == 0) return SE3_OK;
@@ -857,6 +984,11 @@ static int ball_query_count_impl(const float* pts_src, const float* pts_dst, con
     hipLaunchKernelGGL(scan_all_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, stream, pts_src, batch_src,
                        (float4*)(gws + l.spts), pts_dst, batch_dst, 1.0f / radius, (int)n_src, n_dst, counts,
                        (int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr, (int32_t*)nullptr);
+    if (cap)
+      hipLaunchKernelGGL((scan_all_kernel<4, true>), dim3((unsigned)((n_dst + 3) / 4)), dim3(256), 0, stream,
+                         (const float*)nullptr, (const int32_t*)nullptr, (float4*)(gws + l.spts), pts_dst, batch_dst,
+                         1.0f / radius, (int)n_src, n_dst, counts, (int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr,
+                         (int32_t*)nullptr, *cap);
     if (skip_scan) return check_launch();
     if (hipcub::DeviceScan::InclusiveSum(ws + l.temp, temp_bytes, counts, ends, (int)n_dst, stream) != hipSuccess)
       return SE3_ERR_LAUNCH;
@@ -908,6 +1040,10 @@ static int ball_query_count_impl(const float* pts_src, const float* pts_dst, con
   hipLaunchKernelGGL(scan_candidates_kernel<0>, dim3((unsigned)((n_dst + 3) / 4)), dim3(256), 0, stream, pts_dst,
                      1.0f / radius, spts, ranges, n_dst, counts, (int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr,
                      (int32_t*)nullptr, order);
+  if (cap)
+    hipLaunchKernelGGL((scan_candidates_kernel<4, true>), dim3((unsigned)((n_dst + 3) / 4)), dim3(256), 0, stream, pts_dst,
+                       1.0f / radius, spts, ranges, n_dst, counts, (int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr,
+                       (int32_t*)nullptr, order, *cap);
   temp_bytes = l.temp_bytes;
   if (hipcub::DeviceScan::InclusiveSum(ws + l.temp, temp_bytes, counts, ends, (int)n_dst, stream) != hipSuccess)
     return SE3_ERR_LAUNCH;
@@ -926,7 +1062,7 @@ extern "C" int se3_ball_query_count(const float* pts_src, const float* pts_dst, 
 static int ball_query_store_impl(const float* pts_dst, const int32_t* batch_dst, float radius, int64_t n_src,
                                  int64_t n_dst, const void* workspace, size_t workspace_bytes, int32_t* ends,
                                  int32_t* neighbors, int limit, int mode, int32_t* sources, int32_t* info, bool ordered,
-                                 void* stream, const void* grid = nullptr) {
+                                 void* stream, const void* grid = nullptr, const CapArgs* cap = nullptr) {
   const BqLayout l = bq_layout(n_src, n_dst);
   if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
   const char* ws = (const char*)workspace;
@@ -940,13 +1076,24 @@ static int ball_query_store_impl(const float* pts_dst, const int32_t* batch_dst,
 #define SE3_SCAN_ALL(M)                                                                                                 \
   hipLaunchKernelGGL(scan_all_kernel<M>, wgrid, block, 0, st, (const float*)nullptr, (const int32_t*)nullptr, recs, pts_dst, \
                      batch_dst, 1.0f / radius, (int)n_src, n_dst, counts, ends, neighbors, limit, sources, info)
-    if (mode == 1) SE3_SCAN_ALL(1);
+    if (cap) {  // (the capped call is a bounded one: modes 2 and 3)
+      if (mode == 2)
+        hipLaunchKernelGGL((scan_all_kernel<2, true>), wgrid, block, 0, st, (const float*)nullptr, (const int32_t*)nullptr, recs,
+                           pts_dst, batch_dst, 1.0f / radius, (int)n_src, n_dst, counts, ends, neighbors, limit, sources, info, *cap);
+      else
+        hipLaunchKernelGGL((scan_all_kernel<3, true>), wgrid, block, 0, st, (const float*)nullptr, (const int32_t*)nullptr, recs,
+                           pts_dst, batch_dst, 1.0f / radius, (int)n_src, n_dst, counts, ends, neighbors, limit, sources, info, *cap);
+    } else if (mode == 1) SE3_SCAN_ALL(1);
     else if (mode == 2) SE3_SCAN_ALL(2);
     else SE3_SCAN_ALL(3);
 #undef SE3_SCAN_ALL
     return check_launch();
   }
-  if (mode == 1)
+  if (cap)
+    hipLaunchKernelGGL((scan_candidates_kernel<2, true>), wgrid, block, 0, st, pts_dst, 1.0f / radius,
+                       (const float4*)(gws + l.spts), (const int2*)(ws + l.ranges), n_dst, (int32_t*)nullptr, ends, neighbors,
+                       limit, sources, info, ordered ? (const int32_t*)(gws + l.sids) : (const int32_t*)nullptr, *cap);
+  else if (mode == 1)
     hipLaunchKernelGGL(scan_candidates_kernel<1>, wgrid, block, 0, st, pts_dst, 1.0f / radius, (const float4*)(gws + l.spts),
                        (const int2*)(ws + l.ranges), n_dst, (int32_t*)nullptr, ends, neighbors, limit, sources, info,
                        ordered ? (const int32_t*)(gws + l.sids) : (const int32_t*)nullptr);
@@ -971,7 +1118,9 @@ static int ball_query_bounded_impl(const float* pts_src, const float* pts_dst, c
                                    const int32_t* batch_dst, const float* aabb_min, const int32_t* num_cells,
                                    float radius, int64_t n_src, int64_t n_dst, int32_t n_batches, void* workspace,
                                    size_t workspace_bytes, int64_t capacity, int32_t* neighbors, int32_t* sources,
-                                   int32_t* ends, int32_t* info, void* stream, void* grid, bool grid_valid) {
+                                   int32_t* ends, int32_t* info, void* stream, void* grid, bool grid_valid,
+                                   const CapArgs* threshold = nullptr, const CapArgs* cap = nullptr) {
+  // threshold: run the capped query's threshold pass (degrees, and with a cap the thresholds); cap: store under them
   if (capacity < 0 || capacity >= (1ll << 31) || !info) return SE3_ERR_INVALID_ARGUMENT;
   if (n_dst == 0) return se3::launch_fill_words(info, 0u, 2, (hipStream_t)stream);
   if (capacity > 0 && !neighbors) return SE3_ERR_INVALID_ARGUMENT;
@@ -983,12 +1132,13 @@ static int ball_query_bounded_impl(const float* pts_src, const float* pts_dst, c
   // (count + prefix + store as one launch with a decoupled look-back was measured in round 4: slower, removed --
   // profiles/r04_ball_query_onepass_ab.txt)
   if (int rc = ball_query_count_impl(pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst,
-                                     workspace, workspace_bytes, ends, inline_prefix, key_bits, stream, grid, grid_valid))
+                                     workspace, workspace_bytes, ends, inline_prefix, key_bits, stream, grid, grid_valid,
+                                     threshold))
     return rc;
   // one store launch also clamps the offsets to the buffer and records total + overflow flag
   return ball_query_store_impl(pts_dst, batch_dst, radius, n_src, n_dst, workspace, workspace_bytes, ends, neighbors,
                                (int)capacity, inline_prefix ? 3 : 2, sources, info,
-                               pts_src == pts_dst && n_src == n_dst && batch_src == batch_dst, stream, grid);
+                               pts_src == pts_dst && n_src == n_dst && batch_src == batch_dst, stream, grid, cap);
 }
 
 extern "C" int se3_ball_query_bounded(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
@@ -1012,6 +1162,32 @@ extern "C" int se3_ball_query_bounded_shared(const float* pts_src, const float* 
   return ball_query_bounded_impl(pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, n_batches,
                                  workspace, workspace_bytes, capacity, neighbors, sources, ends, info, stream, grid,
                                  grid_valid != 0);
+}
+
+// ---- capped query (include/se3conv_capped.h) ----------------------------------------------------------------------------
+// the workspace of the bounded query, then one 64-bit threshold per sample
+static size_t capped_tau_offset(int64_t n_src, int64_t n_dst) { return align_up(bq_layout(n_src, n_dst).total, 256); }
+
+extern "C" size_t se3_ball_query_capped_workspace_bytes(int64_t n_src, int64_t n_dst) {
+  return capped_tau_offset(n_src, n_dst) + (size_t)(n_dst > 0 ? n_dst : 1) * 8;
+}
+
+extern "C" int se3_ball_query_capped(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
+                                     const int32_t* batch_dst, const float* aabb_min, const int32_t* num_cells, float radius,
+                                     int64_t n_src, int64_t n_dst, int32_t n_batches, void* grid, size_t grid_bytes,
+                                     int32_t grid_valid, void* workspace, size_t workspace_bytes, int64_t capacity,
+                                     int32_t* neighbors, int32_t* sources, int32_t* ends, int32_t* info, void* stream,
+                                     int32_t max_neighbors, uint32_t seed, const uint32_t* seed_device, int32_t* degrees) {
+  if (n_src < 0 || n_dst < 0) return SE3_ERR_INVALID_ARGUMENT;
+  if (max_neighbors > kCapMax) return SE3_ERR_UNSUPPORTED;
+  if (grid && grid_bytes < bq_layout(n_src, 0).ranges) return SE3_ERR_WORKSPACE;
+  if (workspace && workspace_bytes < se3_ball_query_capped_workspace_bytes(n_src, n_dst)) return SE3_ERR_WORKSPACE;
+  const bool capped = max_neighbors > 0;
+  CapArgs cap{capped ? max_neighbors : 0x7fffffff, seed, seed_device,
+              workspace ? (uint64_t*)((char*)workspace + capped_tau_offset(n_src, n_dst)) : nullptr, degrees};
+  return ball_query_bounded_impl(pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, n_batches,
+                                 workspace, workspace_bytes, capacity, neighbors, sources, ends, info, stream, grid,
+                                 grid && grid_valid != 0, capped || degrees ? &cap : nullptr, capped ? &cap : nullptr);
 }
 
 // ---- source-major copy of an edge list (se3_csr_transpose*) -----------------------------------------------------------

@@ -352,17 +352,110 @@ def ball_query_bounded(pts_src, pts_dst, batch_src, batch_dst, radius: float, ca
     return (neighbors, ends, info, sources) if want_sources else (neighbors, ends, info)
 
 
+MAX_CAPPED_NEIGHBORS = 64  # se3_ball_query_capped keeps one key per lane of a wavefront (include/se3conv_capped.h)
+
+
+def draw_seed() -> int:
+    """A 32-bit seed from torch's default CPU generator (reproducible under ``torch.manual_seed``; no device work)."""
+    return int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
+
+
+def ball_query_capped(pts_src, pts_dst, batch_src, batch_dst, radius: float, max_neighbors: int, seed: int,
+                      capacity: Optional[int] = None, n_batches: Optional[int] = None, want_degrees: bool = False,
+                      neighbors_out: Optional[torch.Tensor] = None, src_box=None, grids: Optional[SourceGrids] = None,
+                      seed_tensor: Optional[torch.Tensor] = None):
+    """Radius neighbours with at most ``max_neighbors`` sources per sample (``se3_ball_query_capped``): a sample with more
+    hits keeps the ``max_neighbors`` of them with the smallest keys ``hash(seed, sample, source)`` -- a uniform subset that
+    depends on the seed, the sample and its hit SET only, in the order the uncapped query lists them (the contract is in
+    include/se3conv_capped.h).  ``max_neighbors <= 0``: no limit.
+
+    ``capacity=None``: builds into ``n_dst * max_neighbors`` rows (which cannot overflow), reads the edge count back once
+    and returns ``(neighbors [E,2] int32, ends [M] int32)`` -- the one synchronisation ``ball_query`` has.  With a
+    ``capacity`` there is none (capturable when ``n_batches`` is given) and the result is ``(neighbors [capacity,2], ends,
+    info [2] on the device)`` as from ``ball_query_bounded``.  ``want_degrees``: one more result, the uncapped degree of
+    every sample ``[M] int32``.  ``seed_tensor``: a 1-element int32 device tensor whose bits are added to ``seed`` on the
+    device -- a replayed graph draws fresh subsets when it is updated.  ``neighbors_out`` / ``src_box`` / ``grids``: as for
+    ``ball_query_bounded``."""
+    lib = _lib.load()
+    m = int(max_neighbors)
+    if m > MAX_CAPPED_NEIGHBORS:
+        raise NotImplementedError(f"ball_query_capped: max_neighbors = {m}; the HIP kernel keeps at most "
+                                  f"{MAX_CAPPED_NEIGHBORS} neighbours per sample (one per lane of a wavefront)")
+    src_own, batch_own = pts_src, batch_src
+    pts_src = _as(pts_src, torch.float32)
+    pts_dst = _as(pts_dst, torch.float32)
+    if pts_src.dim() != 2 or pts_src.shape[1] != 3 or pts_dst.dim() != 2 or pts_dst.shape[1] != 3:
+        raise ValueError("ball_query: only [N,3] point sets are supported")
+    if not (radius > 0) or (capacity is not None and capacity < 0):
+        raise ValueError("ball_query_capped: radius must be positive and capacity non-negative")
+    dev = pts_src.device
+    n_src, n_dst = pts_src.shape[0], pts_dst.shape[0]
+    f32, i32 = torch.float32, torch.int32
+    exact = capacity is None
+    if exact and m <= 0:  # no cap and no buffer to size from it: the two-phase query
+        nb, ends = ball_query(pts_src, pts_dst, batch_src, batch_dst, radius, n_batches, src_box)
+        return (nb, ends, torch.diff(ends, prepend=ends.new_zeros(1))) if want_degrees else (nb, ends)
+    rows = n_dst * m if exact else int(capacity)
+    bs, bd = _as(batch_src, i32), _as(batch_dst, i32)
+    if neighbors_out is not None:
+        if exact or neighbors_out.shape != (rows, 2) or neighbors_out.dtype != i32 or not neighbors_out.is_contiguous():
+            raise ValueError("neighbors_out must be a contiguous int32 [capacity, 2] tensor (and needs a capacity)")
+        neighbors = neighbors_out
+    else:
+        neighbors = _empty((rows, 2), dtype=i32, device=dev)
+    ends = _empty(n_dst, dtype=i32, device=dev)
+    degrees = _empty(n_dst, dtype=i32, device=dev) if want_degrees else None
+    if seed_tensor is not None and (seed_tensor.numel() != 1 or seed_tensor.dtype != i32):
+        raise ValueError("seed_tensor must be a 1-element int32 tensor")
+    if n_dst == 0:
+        info = torch.zeros(2, dtype=i32, device=dev)
+    else:
+        info = _empty(2, dtype=i32, device=dev)  # both words are written by the store pass
+        needs_grid = bool(_ball_query_sizes(n_src, n_dst)[0])
+        grid_bytes = _ball_query_sizes(n_src, n_dst)[2]
+        ws = _workspace(lib.se3_ball_query_capped_workspace_bytes(n_src, n_dst), dev)
+        grid, valid, key = None, False, None
+        if grids is not None and needs_grid and src_box is not None and SHARED_GRIDS and not torch.cuda.is_current_stream_capturing():
+            # the source cloud's grid for this radius, shared with the uncapped queries (see ball_query_bounded)
+            key = SourceGrids.key(src_own, batch_own, n_batches)
+            grid, valid = grids.slot(key, radius, grid_bytes, dev)
+            params = grids.params.get(float(radius)) if valid else None
+            if params is None:
+                valid, params = False, _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box)
+            mn, nc = params
+        else:
+            mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if needs_grid else (None, None)
+        _lib.check(lib.se3_ball_query_capped(
+            _ptr(pts_src, f32, "pts_src"), _ptr(pts_dst, f32, "pts_dst", dev), _ptr(bs, i32, "batch_src", dev),
+            _ptr(bd, i32, "batch_dst", dev), _ptr(mn, f32, "aabb_min"), _ptr(nc, i32, "num_cells"), float(radius), n_src,
+            n_dst, int(n_batches or 0), C.c_void_p(grid.data_ptr() if grid is not None else 0),
+            grid.numel() if grid is not None else 0, int(valid), C.c_void_p(ws.data_ptr()), ws.numel(), rows,
+            _ptr(neighbors, i32, "neighbors"), C.c_void_p(0), _ptr(ends, i32, "ends"), _ptr(info, i32, "info"), _stream(dev),
+            m, int(seed) & 0xFFFFFFFF, _ptr(seed_tensor, i32, "seed_tensor", dev), _ptr(degrees, i32, "degrees")),
+            "se3_ball_query_capped")
+        if grid is not None and not valid:
+            grids.commit(key, radius, grid, params)
+    if exact:
+        res = (neighbors[:int(info[0].item())], ends)
+    else:
+        res = (neighbors, ends, info)
+    return res + (degrees,) if want_degrees else res
+
+
 class BallQuery(torch.autograd.Function):
     """Drop-in for ``point_cloud_lib.custom_ops.BallQuery`` (BallQuery.py:11-53).  Like the
     reference it returns ``neighbors`` as int64 (ball_query.cu:99-101 promotes through ``cat``)
-    and ``start_ids`` (inclusive ends) as int32; ``max_neighbors`` must be 0."""
+    and ``start_ids`` (inclusive ends) as int32.  ``max_neighbors > 0`` keeps a seeded uniform subset of that size per
+    sample (``ball_query_capped``; the seed comes from torch's default CPU generator), zero or less means no limit."""
 
     @staticmethod
     def forward(ctx, p_pt_src, p_pt_sample, p_batch_id_src, p_batch_id_sample, radius, max_neighbors, n_batches=None):
         """``n_batches`` (extension; the reference reads it back from the device, ball_query.cu:46): batch count
         when the caller knows it -- saves a host sync."""
-        if max_neighbors != 0:
-            raise NotImplementedError("max_neighbors > 0 (random sub-sampling) is not used by any model path")
+        if max_neighbors > 0:
+            nb, ends = ball_query_capped(p_pt_src, p_pt_sample, p_batch_id_src, p_batch_id_sample, radius, int(max_neighbors),
+                                         draw_seed(), n_batches=n_batches)
+            return nb.to(torch.int64), ends
         nb, ends = ball_query(p_pt_src, p_pt_sample, p_batch_id_src, p_batch_id_sample, radius, n_batches)
         return nb.to(torch.int64), ends
 

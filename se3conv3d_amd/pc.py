@@ -293,28 +293,49 @@ class BQNeighborhood(Neighborhood):
     ``p_capacity`` (extension): build into an edge buffer of that many rows without reading the edge count back to the
     host -- no synchronisation, capturable in a HIP graph.  ``neighbors_`` then has ``p_capacity`` rows of which the
     first ``num_edges()`` are edges (``start_ids_`` never points past them); ``overflowed()`` tells whether the buffer
-    was too small (the list is then truncated: rebuild with a larger one)."""
+    was too small (the list is then truncated: rebuild with a larger one).
 
-    def __init__(self, p_pc_src, p_samples, p_radius, p_max_neighbors=0, p_capacity=None):
+    ``p_max_neighbors > 0``: every sample keeps at most that many of its neighbours, a seeded uniform subset
+    (``ops.ball_query_capped``, at most ``ops.MAX_CAPPED_NEIGHBORS``; zero or less = no limit, as in the reference).
+    ``degrees_ [M]`` then holds the uncapped degrees and ``seed_`` the seed (``p_seed``, or one drawn from torch's default CPU
+    generator); ``p_seed_tensor`` is a 1-element int32 device tensor added to it on the device (a captured build draws fresh
+    subsets when it is updated).  A capped list is not symmetric, also for a cloud against itself, and a second query
+    with the roles swapped would draw another subset: ``symmetric_`` is False, ``source_major()`` is None, and backward
+    reads the library's transposition of this very list."""
+
+    def __init__(self, p_pc_src, p_samples, p_radius, p_max_neighbors=0, p_capacity=None, p_seed=None, p_seed_tensor=None):
         self.radius_ = p_radius
         self.max_neighbors_ = p_max_neighbors
         self.capacity_ = p_capacity
         self.edge_info_ = None
+        self.degrees_ = None
+        self.seed_ = None
+        self.seed_tensor_ = p_seed_tensor
+        if p_max_neighbors > 0:
+            self.seed_ = ops.draw_seed() if p_seed is None else int(p_seed)
         # a cloud against itself: (s, p) is an edge iff (p, s) is -- the operator's backward then needs no
         # source-major copy of the edge list (ops.ConvGeometry.transpose)
-        self.symmetric_ = p_pc_src is p_samples and p_max_neighbors == 0
+        self.symmetric_ = p_pc_src is p_samples and p_max_neighbors <= 0
         super().__init__(p_pc_src, p_samples)
 
     def __compute_neighborhood__(self):
-        if self.max_neighbors_ != 0:
-            raise NotImplementedError("max_neighbors > 0 (random sub-sampling) is not used by any model path")
         # same call as ops.BallQuery.apply (which stays for code that uses the op directly), without the autograd node --
         # the edge list carries no gradient.  The kernels read the int32 list (``neighbors_i32_``); the int64
         # ``neighbors_`` the reference exposes is materialised on first access only (33 MB at the headline shape).
         self.sources_i32_ = None
         # the source cloud's boxes: computed once per cloud (Pointcloud.aabb), not once per query
         src_box = self.pc_src_.aabb() if hasattr(self.pc_src_, "aabb") and ops.ball_query_needs_grid(self.pc_src_.pts_.shape[0]) else None
-        if self.capacity_ is not None:
+        if self.max_neighbors_ > 0:
+            res = ops.ball_query_capped(self.pc_src_.pts_, self.samples_.pts_, self.pc_src_.batch_ids_,
+                                        self.samples_.batch_ids_, self.radius_, int(self.max_neighbors_), self.seed_,
+                                        capacity=None if self.capacity_ is None else int(self.capacity_),
+                                        n_batches=self.pc_src_.num_batches(), want_degrees=True, src_box=src_box,
+                                        grids=ops.source_grids(self.pc_src_), seed_tensor=self.seed_tensor_)
+            nb, self.start_ids_ = res[:2]
+            if self.capacity_ is not None:
+                self.edge_info_ = res[2]
+            self.degrees_ = res[-1]
+        elif self.capacity_ is not None:
             res = ops.ball_query_bounded(self.pc_src_.pts_, self.samples_.pts_, self.pc_src_.batch_ids_,
                                          self.samples_.batch_ids_, self.radius_, int(self.capacity_),
                                          self.pc_src_.num_batches(), want_sources=self.symmetric_, src_box=src_box,
@@ -352,7 +373,7 @@ class BQNeighborhood(Neighborhood):
         capturable.  After an overflow the two lists are truncated differently (sample-major / source-major order), i.e.
         backward would differentiate another sub-graph than forward ran on: ``overflowed()`` must be checked and the step
         redone with a larger buffer -- as for any overflowed neighbourhood (include/se3conv.h, se3_csr_transpose_bounded)."""
-        if self.symmetric_ or self.max_neighbors_ != 0 or getattr(self, "neighbors_i32_", None) is None:
+        if self.symmetric_ or self.max_neighbors_ > 0 or getattr(self, "neighbors_i32_", None) is None:
             return None
         n_src, n_smp = self.pc_src_.pts_.shape[0], self.samples_.pts_.shape[0]
         rows = int(self.neighbors_i32_.shape[0])
@@ -520,7 +541,9 @@ class PointHierarchy(object):
 
     def create_neighborhood(self, p_pc_src_id, p_pc_dest_id, p_neigh_method, **kwargs):
         """Memoised per (source level, destination level, method + its parameter), pc/PointHierarchy.py:60-79 (the k-NN
-        keyword is spelled ``neihg_k`` there; ``neigh_k`` is accepted too)."""
+        keyword is spelled ``neihg_k`` there; ``neigh_k`` is accepted too).  ``bq_max_neighbors`` (> 0) and ``bq_seed`` cap a ball-query
+        neighbourhood (``BQNeighborhood``); they enter the key only then."""
+        cap = int(kwargs.get("bq_max_neighbors", 0) or 0) if p_neigh_method == "ball_query" else 0
         if p_neigh_method == "ball_query":
             param = kwargs["bq_radius"]
         elif p_neigh_method == "knn":
@@ -528,10 +551,12 @@ class PointHierarchy(object):
         else:
             raise ValueError(f"unknown neighbourhood method {p_neigh_method!r} (ball_query, knn)")
         key = f"{p_pc_src_id}_{p_pc_dest_id}_{p_neigh_method}{param}"
+        if cap > 0:  # (a capped neighbourhood is another list, and so is one drawn with another seed)
+            key += f"_max{cap}_seed{kwargs.get('bq_seed')}"
         if key not in self.neigh_cache_:
             src, dst = self.pcs_[p_pc_src_id], self.pcs_[p_pc_dest_id]
-            self.neigh_cache_[key] = BQNeighborhood(src, dst, param) if p_neigh_method == "ball_query" else \
-                KnnNeighborhood(src, dst, param)
+            self.neigh_cache_[key] = BQNeighborhood(src, dst, param, cap, p_seed=kwargs.get("bq_seed")) \
+                if p_neigh_method == "ball_query" else KnnNeighborhood(src, dst, param)
         return self.neigh_cache_[key]
 
     def clear_neigh_cache(self):

@@ -234,51 +234,135 @@ int shape_supported(const se3conv_shape* s) {
   return SE3_OK;
 }
 
-struct FwdLayout { size_t axes_ext, t, featpk, bt_hi, bt_lo, split, geom_in, geom_out, total; };
-FwdLayout fwd_layout(const se3conv_shape* s, int save_t) {
-  FwdLayout l{};
+// The two views of a call's graph for the edge kernels.  Without pointers they are the shape alone, which is all the
+// plans below ask the kernels' `*_applicable` / `*_rows` predicates about.
+EdgeGeom forward_geom(const se3conv_shape* s, const float* pts_in = nullptr, const float* pts_out = nullptr,
+                      const float* frames_in = nullptr, const float* frames_out = nullptr, const int32_t* neighbors = nullptr,
+                      const int32_t* ends = nullptr) {
+  EdgeGeom g{};
+  g.ctr_pts = pts_out, g.ctr_frames = frames_out, g.nb_pts = pts_in, g.nb_frames = frames_in;
+  g.nbr = neighbors, g.nbr_stride = 2, g.nbr_offset = 1, g.ends = ends;
+  g.n_ctr = s->n_out, g.f_ctr = s->f_out, g.f_nb = s->f_in, g.transposed = 0;
+  g.n_nb = s->n_in;
+  g.n_edges = s->n_edges;
+  return g;
+}
+// transposed graph: centre = input point, edges lead to output points (feature gradient)
+EdgeGeom transposed_geom(const se3conv_shape* s, const float* pts_in = nullptr, const float* pts_out = nullptr,
+                         const float* frames_in = nullptr, const float* frames_out = nullptr, const int32_t* t_samples = nullptr,
+                         const int32_t* t_ends = nullptr) {
+  EdgeGeom g{};
+  g.ctr_pts = pts_in, g.ctr_frames = frames_in, g.nb_pts = pts_out, g.nb_frames = frames_out;
+  g.nbr = t_samples, g.nbr_stride = 1, g.nbr_offset = 0, g.ends = t_ends;
+  g.n_ctr = s->n_in, g.f_ctr = s->f_in, g.f_nb = s->f_out, g.transposed = 1;
+  g.n_nb = s->n_out;
+  g.n_edges = s->n_edges;
+  return g;
+}
+
+// The geometry records of a call.  Where they live: the caller's buffers (se3conv_prepared) where it keeps them, the
+// workspace slots otherwise; a cloud against itself has one set of records for both sides.  The records this call has to
+// build become jobs of `pb`; the forward view `g` and, in backward, the transposed view `gt` get their pointers.
+void prepare_geometry(PrepBatch& pb, const se3conv_prepared* prep, const se3conv_shape* s, float* ws_in, float* ws_out,
+                      EdgeGeom* g, EdgeGeom* gt) {
+  const float *pts_in = g->nb_pts, *frames_in = g->nb_frames, *pts_out = g->ctr_pts, *frames_out = g->ctr_frames;
+  const bool same_cloud = pts_in == pts_out && frames_in == frames_out && s->n_in == s->n_out && s->f_in == s->f_out;
+  float *in = ws_in, *out = ws_out;
+  bool need_in = true, need_out = true;
+  if (prep && prep->geom_in) in = prep->geom_in, need_in = !prep->geom_in_valid;
+  if (same_cloud) out = in, need_out = false;
+  else if (prep && prep->geom_out) out = prep->geom_out, need_out = !prep->geom_out_valid;
+  if (need_in) pb.geometry(pts_in, frames_in, s->n_in, s->f_in, in);
+  if (need_out) pb.geometry(pts_out, frames_out, s->n_out, s->f_out, out);
+  g->ctr_geom = out, g->nb_geom = in;
+  if (gt) gt->ctr_geom = in, gt->nb_geom = out;
+}
+
+// Format of the row-sized intermediates (T, and U of the feature gradient): 0 packed hi|lo words (4 bytes per element), 1
+// the 3-byte rows of common.h when the edge kernel can produce them (edge_t_bf16_t24_rows) and the buffer-load GEMMs consume
+// them (SE3_NO_T24=1: packed words everywhere), 2 the 2.25-byte block format T16 -- only in SE3_PRECISION_BF16X3_T16, where
+// the wave-pair edge kernel produces it (rows of a multiple of 64 channels); other shapes of that mode fall back to 1 / 0.
+// tn_cols = the column count of the TN product that also reads the rows (0: none).  Any row count: the GEMMs that read the
+// rows walk them in blocks their 32-bit offsets reach (gemm_bf16.hip).
+int row_format(const se3conv_shape* s, const EdgeGeom& g, int channels, int tn_cols) {
+  static const bool on = getenv("SE3_NO_T24") == nullptr;
+  if (s->precision == SE3_PRECISION_BF16X3_T16 && kBasis == 32 && edge_t_bf16_t16_rows(g, channels) && tn_cols % 4 == 0)
+    return 2;
+  return on && kBasis == 32 && channels % 2 == 0 && edge_t_bf16_t24_rows(g, channels) && tn_cols % 4 == 0 ? 1 : 0;
+}
+// T: written by the forward pass, read by its GEMM and by the weight gradient's TN product (both plans)
+int t_row_format(const se3conv_shape* s) { return row_format(s, forward_geom(s), s->c_in, s->c_out); }
+
+// ---- the plans of a K = 32 call -------------------------------------------------------------------------------------
+// Everything that is decided about HOW a call runs, and where its tensors live in the workspace, is decided here, once,
+// from the shape and the request: the workspace queries, se3conv_bwd_needs_t, the traffic queries and the calls
+// themselves read the same struct.  (Other K: the wrappers plan their inner K = 32 calls, see slice_params_kernel.)
+
+struct FwdPlan {
+  int fmt_t;  // row format of T (row_format)
+  size_t axes_ext, t, featpk, bt_hi, bt_lo, split, geom_in, geom_out, total;
+};
+FwdPlan plan_fwd(const se3conv_shape* s, bool save_t) {
+  FwdPlan p{};
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
   const size_t kb = s->num_basis;
-  l.axes_ext = take(kDescExt * kBasis * 4);
-  l.t = save_t ? 0 : take((size_t)s->n_out * s->f_out * s->c_in * kb * 4);
-  if (s->precision != SE3_PRECISION_FP32) {
-    l.featpk = take((size_t)s->n_in * s->f_in * s->c_in * 4);
+  const bool fast = s->precision != SE3_PRECISION_FP32;
+  p.fmt_t = fast ? t_row_format(s) : 0;
+  p.axes_ext = take(kDescExt * kBasis * 4);
+  p.t = save_t ? 0 : take((size_t)s->n_out * s->f_out * s->c_in * kb * 4);
+  if (fast) {
+    p.featpk = take((size_t)s->n_in * s->f_in * s->c_in * 4);
     const size_t plane = (size_t)s->c_out * align_up((size_t)s->c_in * kb, 32) * 2;
-    l.bt_hi = take(plane);
-    l.bt_lo = take(plane);
-    l.split = take(gemm_nn_bf16_split_bytes((int64_t)s->n_out * s->f_out, s->c_out, s->c_in * (int)kb));
+    p.bt_hi = take(plane);
+    p.bt_lo = take(plane);
+    p.split = take(gemm_nn_bf16_split_bytes((int64_t)s->n_out * s->f_out, s->c_out, s->c_in * (int)kb));
   } else {
-    l.split = take(gemm_nn_split_bytes((int64_t)s->n_out * s->f_out, s->c_out, s->c_in * (int)kb));
+    p.split = take(gemm_nn_split_bytes((int64_t)s->n_out * s->f_out, s->c_out, s->c_in * (int)kb));
   }
-  l.geom_in = take((size_t)s->n_in * s->f_in * 64);
-  l.geom_out = take((size_t)s->n_out * s->f_out * 64);
-  l.total = off;
-  return l;
+  p.geom_in = take((size_t)s->n_in * s->f_in * 64);
+  p.geom_out = take((size_t)s->n_out * s->f_out * 64);
+  p.total = off;
+  return p;
 }
 
-struct BwdLayout {
-  size_t axes_ext, wt, w2, big, t, param_partials, tn_partials, featpk, gpk, bt_hi, bt_lo, split, geom_in, geom_out, total;
-  size_t dx_rows;  // edge-major feature gradient (use_edge_dx): D [edge rows * F_in, C_in] fp32
-  size_t big_u, bt2_hi, bt2_lo, split2;  // U and the grad_X partials when both branches run: grad_T takes `big` meanwhile
-  int n_param_partials, tn_splits;
+enum class FeatGrad { none, u, edge_major };               // the feature gradient: U rows + the grad_X GEMM, or edge_dx.hip
+enum class WeightGrad { none, t_saved, t_recomputed, u };  // the tensor the weight gradient's product reads
+
+// How a backward call runs.  Made from the shape and from WHAT is asked for -- a feature gradient, any parameter gradient,
+// with or without a saved T -- not from which of grad_axes / grad_biases / grad_weights the call passes: a NULL pointer
+// among them only skips the stage that would write it, it never selects another buffer or another form.
+struct BwdPlan {
+  bool fast;           // split-bf16 arithmetic (exact fp32 otherwise)
+  bool feat_branch;    // the feature gradient has rows to run on: want_feat && rows_in > 0.  (The form, and what is reserved
+                       // for it, follow the request alone: a U form on zero rows reserves its weight planes and launches nothing.)
+  FeatGrad feat;
+  WeightGrad dw;
+  bool grad_t;         // grad_T is computed: for the parameter gradients, and as the operand of the edge-major form ...
+  bool strip_t;        // ... by the row-strip GEMM (else the tiled one); the weights are prepared in its fragment layout
+  int fmt_t, fmt_u;    // row formats of T and of U (row_format)
+  struct { int64_t m; int ka, n, splits; } tn;  // the weight gradient's TN product: over the rows of U or over those of T
+  int n_param_partials;
+  // Workspace offsets.  `big`: grad_T, and U when grad_T is not there at the same time.  `u`, `split_x`: where U and the
+  // split-K partials of the grad_X GEMM go -- slots of their own when both branches run, `big` and `split` otherwise.
+  // `bx_*`: the weight planes of the grad_X GEMM.  `dx_rows`: D [edge rows * F_in, C_in] fp32 of the edge-major form.
+  size_t axes_ext, wt, w2, bt_hi, bt_lo, featpk, gpk, split, geom_in, geom_out, big, bx_hi, bx_lo, u, split_x, dx_rows, t,
+      param_partials, tn_partials, total;
 };
 // The feature gradient of a convolution with many more input rows than edges per row can carry (a down-convolution)
 // goes edge-major (edge_dx.hip): D = phi gT^T per frame-edge, summed per source row -- instead of a U row per source
-// row and its GEMM.  Decided from the shape alone (bwd_layout and se3conv_bwd must agree): implemented shapes only, split-
-// bf16 arithmetic, and the bytes the two forms move through memory -- U written and read (3-byte rows) against D written
+// row and its GEMM.  Decided from the shape alone, for plan_bwd when a feature gradient is wanted: implemented shapes only,
+// split-bf16 arithmetic, and the bytes the two forms move through memory -- U written and read (3-byte rows) against D written
 // and gathered, plus grad_T when the parameter gradients do not need it anyway -- with a factor of two in favour of the
 // default.  SE3_DX_PATH=0 never, =1 whenever implemented (tests force both on the same shapes).
-bool use_edge_dx(const se3conv_shape* s, bool want_feat, bool want_params) {
+bool plan_edge_major(const se3conv_shape* s, bool want_params) {
   static const int mode = [] {
     const char* e = getenv("SE3_DX_PATH");
     return e ? atoi(e) : -1;
   }();
-  if (!want_feat || mode == 0 || s->precision == SE3_PRECISION_FP32 || s->num_basis != kBasis) return false;
+  if (mode == 0 || s->precision == SE3_PRECISION_FP32) return false;
   if (s->n_in == 0 || s->n_out == 0) return false;
-  EdgeGeom g{};
-  g.f_ctr = s->f_out, g.f_nb = s->f_in;
-  if (!edge_dx_bf16_applicable(g, s->c_in)) return false;
+  if (!edge_dx_bf16_applicable(forward_geom(s), s->c_in)) return false;
   if (s->n_edges * s->f_in * (int64_t)s->c_in >= (1ll << 31)) return false;
   if (mode == 1) return true;
   const double rows_in = (double)s->n_in * s->f_in, rows_out = (double)s->n_out * s->f_out;
@@ -295,37 +379,45 @@ bool use_edge_dx(const se3conv_shape* s, bool want_feat, bool want_params) {
   return 15.0 + d_bytes / 2.2e6 < 45.0 + u_bytes / 6.0e6;
 }
 
-// The weight gradient from U instead of T (round 5): dW[i,k,o] = alpha sum_p f[p,i] U[p,o,k] -- U is the transposed pass's
-// tensor, which backward produces anyway for the feature gradient.  Available in the split-bf16 modes whenever the U form
-// of the feature gradient runs; then the forward pass need not keep T (0.8 GB per layer at the headline shape: the largest
-// saved activation by a factor of 24), and for an up-convolution the product walks the few rows of the coarse level
-// instead of the many of the fine one.  Used when T was not saved, or when U has fewer (row x channel) entries than T.
-// From the shape alone: se3conv_bwd_workspace_bytes, se3conv_bwd and se3conv_bwd_needs_t must agree.
-bool dw_from_u_available(const se3conv_shape* s, bool want_feat, bool want_params) {
-  if (!want_feat || !want_params || s->precision == SE3_PRECISION_FP32 || s->num_basis != kBasis) return false;
-  if (s->n_in == 0 || s->n_out == 0 || s->c_in % 4 != 0 || s->c_out % 2 != 0) return false;
-  return !use_edge_dx(s, true, true);
-}
-bool use_u_for_dw(const se3conv_shape* s, bool want_feat, bool want_params, bool have_t) {
-  if (!dw_from_u_available(s, want_feat, want_params)) return false;
-  return !have_t || (double)s->n_in * s->f_in * s->c_out < (double)s->n_out * s->f_out * s->c_in;
-}
-
-BwdLayout bwd_layout(const se3conv_shape* s, int want_feat, int want_params, int have_t) {
-  BwdLayout l{};
-  const bool dx = use_edge_dx(s, want_feat != 0, want_params != 0);
-  const bool dw_u = use_u_for_dw(s, want_feat != 0, want_params != 0, have_t != 0);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+BwdPlan plan_bwd(const se3conv_shape* s, bool want_feat, bool want_params, bool have_t) {
+  BwdPlan p{};
   const size_t kb = s->num_basis;
   const size_t rows_out = (size_t)s->n_out * s->f_out, rows_in = (size_t)s->n_in * s->f_in;
+  const int ck = s->c_in * (int)kb, cok = s->c_out * (int)kb;
+  p.fast = s->precision != SE3_PRECISION_FP32;
+  p.feat_branch = want_feat && rows_in > 0;
+  p.feat = !want_feat ? FeatGrad::none : plan_edge_major(s, want_params) ? FeatGrad::edge_major : FeatGrad::u;
+  const bool u_form = p.feat == FeatGrad::u, edge_major = p.feat == FeatGrad::edge_major;
+  p.grad_t = want_params || edge_major;
+  if (p.fast) {
+    p.strip_t = gemm_strip_bf16_applicable((int64_t)rows_out, ck, s->c_out);  // grad_T = g W^T
+    p.fmt_t = t_row_format(s);
+    p.fmt_u = row_format(s, transposed_geom(s), s->c_out, 0);
+  }
+  // The weight gradient from U instead of T (round 5): dW[i,k,o] = alpha sum_p f[p,i] U[p,o,k] -- U is the transposed pass's
+  // tensor, which backward produces anyway for the feature gradient.  Available in the split-bf16 modes whenever the U form
+  // of the feature gradient runs; then the forward pass need not keep T (0.8 GB per layer at the headline shape: the largest
+  // saved activation by a factor of 24), and for an up-convolution the product walks the few rows of the coarse level
+  // instead of the many of the fine one.  Used when T was not saved, or when U has fewer (row x channel) entries than T.
+  const bool dw_u = p.fast && u_form && p.feat_branch && want_params && rows_out > 0 && s->c_in % 4 == 0 && s->c_out % 2 == 0 &&
+                    (!have_t || (double)rows_in * s->c_out < (double)rows_out * s->c_in);
+  p.dw = !want_params ? WeightGrad::none : dw_u ? WeightGrad::u : have_t ? WeightGrad::t_saved : WeightGrad::t_recomputed;
+  if (dw_u) p.tn = {(int64_t)rows_in, cok, s->c_in, 0};
+  else p.tn = {(int64_t)rows_out, ck, s->c_out, 0};
+  p.tn.splits = gemm_tn_splits(p.tn.m, p.tn.ka, p.tn.n);
+  p.n_param_partials = edge_param_grad_blocks((int64_t)rows_out);
+
+  // The workspace.  Callers cache these sizes: a reservation that is wider than its use (the packed feature words although
+  // the caller may bring them, se3conv_prepared; the grad_X planes of a U form on zero rows) stays as wide.
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
   const size_t wsz = (size_t)s->c_in * kb * s->c_out * 4;
-  const bool fast = s->precision != SE3_PRECISION_FP32;
-  l.axes_ext = take(kDescExt * kBasis * 4);
-  if (!fast) {
-    l.wt = want_params ? take(wsz) : 0;
-    l.w2 = want_feat ? take(wsz) : 0;
-    l.split = want_feat ? take(gemm_nn_split_bytes((int64_t)rows_in, s->c_in, s->c_out * (int)kb)) : 0;
+  const size_t t_bytes = rows_out * s->c_in * kb * 4, u_bytes = rows_in * s->c_out * kb * 4;  // grad_T and a recomputed T; U
+  p.axes_ext = take(kDescExt * kBasis * 4);
+  if (!p.fast) {
+    p.wt = want_params ? take(wsz) : 0;
+    p.w2 = u_form ? take(wsz) : 0;
+    p.split = u_form ? take(gemm_nn_split_bytes((int64_t)rows_in, s->c_in, cok)) : 0;
   } else {
     // the largest of the three pre-split weight layouts (see prep_weights_kernel)
     size_t plane = (size_t)s->c_in * kb * align_up((size_t)s->c_out, 32) * 2;
@@ -333,44 +425,39 @@ BwdLayout bwd_layout(const se3conv_shape* s, int want_feat, int want_params, int
     if (p2 > plane) plane = p2;
     const size_t p3 = (size_t)s->c_out * kb * align_up((size_t)s->c_in, 32) * 2;
     if (p3 > plane) plane = p3;
-    l.bt_hi = take(plane);
-    l.bt_lo = take(plane);
-    l.featpk = want_params ? take(rows_in * s->c_in * 4) : 0;
-    l.gpk = take(rows_out * s->c_out * 4);
-    size_t sp = (want_params || dx) ? gemm_nn_bf16_split_bytes((int64_t)rows_out, s->c_in * (int)kb, s->c_out) : 0;
-    const size_t sp3 = want_params ? gemm_nn_bf16_split_bytes((int64_t)rows_in, s->c_out * (int)kb, s->c_in) : 0;
+    p.bt_hi = take(plane);
+    p.bt_lo = take(plane);
+    p.featpk = want_params ? take(rows_in * s->c_in * 4) : 0;
+    p.gpk = take(rows_out * s->c_out * 4);
+    size_t sp = p.grad_t ? gemm_nn_bf16_split_bytes((int64_t)rows_out, ck, s->c_out) : 0;
+    const size_t sp3 = want_params ? gemm_nn_bf16_split_bytes((int64_t)rows_in, cok, s->c_in) : 0;
     if (sp3 > sp) sp = sp3;
-    const size_t sp2 = (want_feat && !dx) ? gemm_nn_bf16_split_bytes((int64_t)rows_in, s->c_in, s->c_out * (int)kb) : 0;
+    const size_t sp2 = u_form ? gemm_nn_bf16_split_bytes((int64_t)rows_in, s->c_in, cok) : 0;
     if (sp2 > sp) sp = sp2;
-    l.split = take(sp);
+    p.split = take(sp);
   }
-  l.geom_in = take(rows_in * 64);
-  l.geom_out = take(rows_out * 64);
+  p.geom_in = take(rows_in * 64);
+  p.geom_out = take(rows_out * 64);
   // (the edge-major feature gradient has no U: none of the U-sized terms is reserved on that path -- at a down-convolution
   // of the headline hierarchy they were 2 GB of workspace nobody touched)
-  size_t big = 0;
-  if (want_params || dx) big = rows_out * s->c_in * kb * 4;
-  if (want_feat && !dx && rows_in * s->c_out * kb * 4 > big) big = rows_in * s->c_out * kb * 4;
-  l.big = take(big);
-  if (fast && want_feat && !dx) {
+  size_t big = p.grad_t ? t_bytes : 0;
+  if (u_form && u_bytes > big) big = u_bytes;
+  p.big = take(big);
+  if (p.fast && u_form) {
     const size_t p2 = (size_t)s->c_in * align_up((size_t)s->c_out * kb, 32) * 2;
-    l.bt2_hi = take(p2);
-    l.bt2_lo = take(p2);
+    p.bx_hi = take(p2);
+    p.bx_lo = take(p2);
   }
-  if (fast && want_feat && want_params && !dx) {
-    l.big_u = take(rows_in * s->c_out * kb * 4);
-    l.split2 = take(gemm_nn_bf16_split_bytes((int64_t)rows_in, s->c_in, s->c_out * (int)kb));
-  }
-  l.dx_rows = dx ? take((size_t)s->n_edges * s->f_in * s->c_in * 4) : 0;
-  l.t = (want_params && !have_t && !dw_u) ? take(rows_out * s->c_in * kb * 4) : 0;
-  l.n_param_partials = edge_param_grad_blocks((int64_t)rows_out);
-  l.param_partials = want_params ? take((size_t)l.n_param_partials * edge_param_grad_bf16_channel_blocks(s->c_in) *
+  const bool both = p.fast && u_form && want_params;  // both branches run: grad_T takes `big` while U is alive
+  p.u = both ? take(u_bytes) : p.big;
+  p.split_x = both ? take(gemm_nn_bf16_split_bytes((int64_t)rows_in, s->c_in, cok)) : p.split;
+  p.dx_rows = edge_major ? take((size_t)s->n_edges * s->f_in * s->c_in * 4) : 0;
+  p.t = p.dw == WeightGrad::t_recomputed ? take(t_bytes) : 0;
+  p.param_partials = want_params ? take((size_t)p.n_param_partials * edge_param_grad_bf16_channel_blocks(s->c_in) *
                                          kDescExt * kBasis * 4) : 0;
-  l.tn_splits = dw_u ? gemm_tn_splits((int64_t)rows_in, s->c_out * (int)kb, s->c_in)
-                     : gemm_tn_splits((int64_t)rows_out, s->c_in * (int)kb, s->c_out);
-  l.tn_partials = want_params ? take((size_t)l.tn_splits * wsz) : 0;
-  l.total = off;
-  return l;
+  p.tn_partials = want_params ? take((size_t)p.tn.splits * wsz) : 0;
+  p.total = off;
+  return p;
 }
 
 // ---- any number of basis functions on the K = 32 kernels (se3conv_fwd / se3conv_bwd with num_basis != 32) ---------------
@@ -449,34 +536,6 @@ se3conv_shape with_32_basis(const se3conv_shape* s) {
   se3conv_shape t = *s;
   t.num_basis = kBasis;
   return t;
-}
-
-// Where a call's geometry records live and which of them it has to build: the caller's buffers (se3conv_prepared) where it
-// keeps them, the workspace otherwise; a cloud against itself has one set of records for both sides.
-struct PreparedGeometry {
-  float *in, *out;
-  bool need_in, need_out;
-};
-PreparedGeometry prepared_geometry(const se3conv_prepared* prep, bool same_cloud, float* ws_in, float* ws_out) {
-  PreparedGeometry g{ws_in, ws_out, true, true};
-  if (prep && prep->geom_in) g.in = prep->geom_in, g.need_in = !prep->geom_in_valid;
-  if (same_cloud) {
-    g.out = g.in, g.need_out = false;
-    return g;
-  }
-  if (prep && prep->geom_out) g.out = prep->geom_out, g.need_out = !prep->geom_out_valid;
-  return g;
-}
-
-EdgeGeom forward_geom(const float* pts_in, const float* pts_out, const float* frames_in, const float* frames_out,
-                      const int32_t* neighbors, const int32_t* ends, const se3conv_shape* s) {
-  EdgeGeom g{};
-  g.ctr_pts = pts_out, g.ctr_frames = frames_out, g.nb_pts = pts_in, g.nb_frames = frames_in;
-  g.nbr = neighbors, g.nbr_stride = 2, g.nbr_offset = 1, g.ends = ends;
-  g.n_ctr = s->n_out, g.f_ctr = s->f_out, g.f_nb = s->f_in, g.transposed = 0;
-  g.n_nb = s->n_in;
-  g.n_edges = s->n_edges;
-  return g;
 }
 
 }  // namespace
@@ -567,30 +626,14 @@ extern "C" int se3_feat_basis_proj_grad(const float* basis, const float* feat, c
   return check_launch();
 }
 
-// Format of the row-sized intermediates (T, and U of the feature gradient): 0 packed hi|lo words (4 bytes per element), 1
-// the 3-byte rows of common.h when the edge kernel can produce them (edge_t_bf16_t24_rows) and the buffer-load GEMMs consume
-// them (SE3_NO_T24=1: packed words everywhere), 2 the 2.25-byte block format T16 -- only in SE3_PRECISION_BF16X3_T16, where
-// the wave-pair edge kernel produces it (rows of a multiple of 64 channels); other shapes of that mode fall back to 1 / 0.
-// tn_cols = the column count of the TN product that also reads the rows (0: none).
-static int row_format(const se3conv_shape* s, const EdgeGeom& g, int channels, int64_t rows, int tn_cols) {
-  static const bool on = getenv("SE3_NO_T24") == nullptr;
-  (void)rows;  // any row count: the GEMMs that read the rows walk them in blocks their 32-bit offsets reach (gemm_bf16.hip)
-  if (s->precision == SE3_PRECISION_BF16X3_T16 && kBasis == 32 && edge_t_bf16_t16_rows(g, channels) && tn_cols % 4 == 0)
-    return 2;
-  return on && kBasis == 32 && channels % 2 == 0 && edge_t_bf16_t24_rows(g, channels) && tn_cols % 4 == 0 ? 1 : 0;
-}
-
 // Bytes per element of the row-sized intermediates this shape would move (what a traffic model has to assume):
 // which = 0: T (forward, read again by the weight gradient), 1: U (feature gradient), 2: grad_T.  < 0: bad shape.
 // The T16 format's 2.25 bytes are reported as 2 here (an integer interface); se3conv_intermediate_row_bytes is exact.
 static int64_t intermediate_row_bytes(const se3conv_shape* s, int which) {
   const int64_t ck = (int64_t)(which == 1 ? s->c_out : s->c_in) * s->num_basis;
   if (s->precision == SE3_PRECISION_FP32 || s->num_basis != kBasis || which == 2) return ck * 4;  // (grad_T: packed words)
-  EdgeGeom g = forward_geom(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);
-  EdgeGeom gt{};
-  gt.n_ctr = s->n_in, gt.f_ctr = s->f_in, gt.f_nb = s->f_out, gt.n_nb = s->n_out, gt.transposed = 1;
-  const int fmt = which == 0 ? row_format(s, g, s->c_in, s->n_out * s->f_out, s->c_out)
-                             : row_format(s, gt, s->c_out, s->n_in * s->f_in, 0);
+  const BwdPlan p = plan_bwd(s, true, true, false);
+  const int fmt = which == 0 ? p.fmt_t : p.fmt_u;
   return fmt == 2 ? t16_row_bytes(which == 0 ? s->c_in : s->c_out) : ck * (fmt == 1 ? 3 : 4);
 }
 extern "C" int64_t se3conv_intermediate_row_bytes(const se3conv_shape* s, int which) {
@@ -607,9 +650,9 @@ extern "C" size_t se3conv_fwd_workspace_bytes(const se3conv_shape* s, int save_t
   if (!shape_ok(s)) return 0;
   if (s->num_basis != kBasis) {
     const se3conv_shape s32 = with_32_basis(s);
-    return any_basis_layout(s, (size_t)s->n_out * s->f_out * s->c_out * 4, false, fwd_layout(&s32, 0).total).total;
+    return any_basis_layout(s, (size_t)s->n_out * s->f_out * s->c_out * 4, false, plan_fwd(&s32, false).total).total;
   }
-  return fwd_layout(s, save_t).total;
+  return plan_fwd(s, save_t != 0).total;
 }
 
 extern "C" int se3conv_fwd(const float* pts_in, const float* pts_out, const float* frames_in, const float* frames_out,
@@ -633,7 +676,7 @@ extern "C" int se3conv_fwd_prepared(const float* pts_in, const float* pts_out, c
     if (!proj_axes || !proj_biases || !conv_weights || !out || !workspace) return SE3_ERR_INVALID_ARGUMENT;
     const se3conv_shape s32 = with_32_basis(s);
     const int64_t n_out_el = s->n_out * s->f_out * s->c_out;
-    const AnyBasisLayout l = any_basis_layout(s, (size_t)n_out_el * 4, false, fwd_layout(&s32, 0).total);
+    const AnyBasisLayout l = any_basis_layout(s, (size_t)n_out_el * 4, false, plan_fwd(&s32, false).total);
     if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
     char* ws = (char*)workspace;
@@ -656,60 +699,45 @@ extern "C" int se3conv_fwd_prepared(const float* pts_in, const float* pts_out, c
   if (!pts_out || !frames_out || !ends || !proj_axes || !proj_biases || !conv_weights || !rho || !nu || !out ||
       !workspace || (s->n_edges > 0 && (!pts_in || !frames_in || !neighbors || !feat)))
     return SE3_ERR_INVALID_ARGUMENT;
-  const FwdLayout l = fwd_layout(s, t_save != nullptr);
-  if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
+  const FwdPlan p = plan_fwd(s, t_save != nullptr);
+  if (workspace_bytes < p.total) return SE3_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)workspace;
-  float* axes_ext = (float*)(ws + l.axes_ext);
-  float* t = t_save ? t_save : (float*)(ws + l.t);
+  float* axes_ext = (float*)(ws + p.axes_ext);
+  float* t = t_save ? t_save : (float*)(ws + p.t);
 
-  EdgeGeom g = forward_geom(pts_in, pts_out, frames_in, frames_out, neighbors, ends, s);
+  EdgeGeom g = forward_geom(s, pts_in, pts_out, frames_in, frames_out, neighbors, ends);
   const int64_t rows_out = s->n_out * s->f_out;
   const int ck = s->c_in * s->num_basis;
   const float inv_fin = 1.0f / (float)s->f_in;
   // einsum('nik,iko->no') :210, /F_in :213, *norm_num_neighs_ :216 are the GEMM + its alpha
-  const bool same_cloud = pts_in == pts_out && frames_in == frames_out && s->n_in == s->n_out && s->f_in == s->f_out;
-  // the caller's records where it keeps them (se3conv_prepared), the workspace otherwise; `need_*`: built by this call
-  const PreparedGeometry pg = prepared_geometry(prep, same_cloud, (float*)(ws + l.geom_in), (float*)(ws + l.geom_out));
-  float* geom_in = pg.in;
-  float* geom_out = pg.out;
+  PrepBatch pb;  // one launch: [A; beta] table, packed geometry records; split-bf16: packed feature words, weight planes
+  pb.axes(proj_axes, proj_biases, axes_ext);
+  prepare_geometry(pb, prep, s, (float*)(ws + p.geom_in), (float*)(ws + p.geom_out), &g, nullptr);
   if (s->precision == SE3_PRECISION_FP32) {
-    PrepBatch pb;  // one launch: [A; beta] table and the packed geometry records
-    pb.axes(proj_axes, proj_biases, axes_ext);
-    if (pg.need_in) pb.geometry(pts_in, frames_in, s->n_in, s->f_in, geom_in);
-    if (pg.need_out) pb.geometry(pts_out, frames_out, s->n_out, s->f_out, geom_out);
     if (int rc = pb.launch(stream)) return rc;
-    g.ctr_geom = geom_out, g.nb_geom = geom_in;
     if (int rc = launch_edge_t("edge_t_fwd", g, feat, s->c_in, s->n_in * s->f_in, axes_ext, rho, t, stream)) return rc;
-    return launch_gemm_nn("gemm_out", t, conv_weights, out, rows_out, s->c_out, ck, nu, inv_fin, stream, (float*)(ws + l.split));
+    return launch_gemm_nn("gemm_out", t, conv_weights, out, rows_out, s->c_out, ck, nu, inv_fin, stream, (float*)(ws + p.split));
   }
   // (packed feature words: into the caller's buffer where backward will want them again)
-  uint32_t* featpk = prep && prep->feat_words ? prep->feat_words : (uint32_t*)(ws + l.featpk);
+  uint32_t* featpk = prep && prep->feat_words ? prep->feat_words : (uint32_t*)(ws + p.featpk);
   const bool need_featpk = !(prep && prep->feat_words && prep->feat_words_valid);
-  uint16_t* bt_hi = (uint16_t*)(ws + l.bt_hi);
-  uint16_t* bt_lo = (uint16_t*)(ws + l.bt_lo);
+  uint16_t* bt_hi = (uint16_t*)(ws + p.bt_hi);
+  uint16_t* bt_lo = (uint16_t*)(ws + p.bt_lo);
   const float inv_phi = inv_fin / kGeluOut;  // the bf16 edge kernels produce kGeluOut * phi (gelu_scaled)
-  const int t24 = row_format(s, g, s->c_in, rows_out, s->c_out);  // 0 / 1 / 2 (row_format); se3conv_bwd decides the same way
-  {  // one launch: [A; beta] table, packed geometry records, packed feature words, weight planes
-    PrepBatch pb;
-    pb.axes(proj_axes, proj_biases, axes_ext);
-    if (pg.need_in) pb.geometry(pts_in, frames_in, s->n_in, s->f_in, geom_in);
-    if (pg.need_out) pb.geometry(pts_out, frames_out, s->n_out, s->f_out, geom_out);
-    if (need_featpk) pb.split(feat, featpk, s->n_in * s->f_in * s->c_in);
-    pb.weights(conv_weights, s->c_in, s->num_basis, s->c_out, 0, bt_hi, bt_lo, nullptr, 1.0f, false, t24);
-    if (int rc = pb.launch(stream)) return rc;
-    g.ctr_geom = geom_out, g.nb_geom = geom_in;
-  }
-  if (int rc = launch_edge_t_bf16("edge_t_fwd", g, featpk, s->c_in, s->n_in * s->f_in, axes_ext, rho, (uint32_t*)t, stream, t24))
+  if (need_featpk) pb.split(feat, featpk, s->n_in * s->f_in * s->c_in);
+  pb.weights(conv_weights, s->c_in, s->num_basis, s->c_out, 0, bt_hi, bt_lo, nullptr, 1.0f, false, p.fmt_t);
+  if (int rc = pb.launch(stream)) return rc;
+  if (int rc = launch_edge_t_bf16("edge_t_fwd", g, featpk, s->c_in, s->n_in * s->f_in, axes_ext, rho, (uint32_t*)t, stream, p.fmt_t))
     return rc;
   return launch_gemm_nn_bf16("gemm_out", (const uint32_t*)t, bt_hi, bt_lo, out, false, rows_out, s->c_out, ck,
-                             (float*)(ws + l.split), nu, inv_phi, stream, t24);
+                             (float*)(ws + p.split), nu, inv_phi, stream, p.fmt_t);
 }
 
 extern "C" int se3conv_bwd_needs_t(const se3conv_shape* s, int want_feat) {
   if (!shape_ok(s)) return SE3_ERR_INVALID_ARGUMENT;
   if (s->num_basis != kBasis) return 0;  // other K: T is recomputed per slice of 32 basis functions, `t_save` is never read
-  return dw_from_u_available(s, want_feat != 0, true) ? 0 : 1;
+  return plan_bwd(s, want_feat != 0, true, false).dw == WeightGrad::u ? 0 : 1;
 }
 
 extern "C" size_t se3conv_bwd_workspace_bytes(const se3conv_shape* s, int want_feat, int want_params, int have_t) {
@@ -717,9 +745,9 @@ extern "C" size_t se3conv_bwd_workspace_bytes(const se3conv_shape* s, int want_f
   if (s->num_basis != kBasis) {
     const se3conv_shape s32 = with_32_basis(s);
     return any_basis_layout(s, want_feat ? (size_t)s->n_in * s->f_in * s->c_in * 4 : 0, want_params != 0,
-                            bwd_layout(&s32, want_feat, want_params, 0).total).total;
+                            plan_bwd(&s32, want_feat != 0, want_params != 0, false).total).total;
   }
-  return bwd_layout(s, want_feat, want_params, have_t).total;
+  return plan_bwd(s, want_feat != 0, want_params != 0, have_t != 0).total;
 }
 
 extern "C" int se3conv_bwd(const float* pts_in, const float* pts_out, const float* frames_in, const float* frames_out,
@@ -751,7 +779,7 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
     if (!proj_axes || !proj_biases || !conv_weights || !workspace) return SE3_ERR_INVALID_ARGUMENT;
     const se3conv_shape s32 = with_32_basis(s);
     const int64_t n_in_el = s->n_in * s->f_in * s->c_in;
-    const AnyBasisLayout l = any_basis_layout(s, wf ? (size_t)n_in_el * 4 : 0, wp, bwd_layout(&s32, wf, wp, 0).total);
+    const AnyBasisLayout l = any_basis_layout(s, wf ? (size_t)n_in_el * 4 : 0, wp, plan_bwd(&s32, wf, wp, false).total);
     if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
     char* ws = (char*)workspace;
@@ -784,192 +812,147 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
   if (s->n_in > 0 && (!pts_in || !frames_in || !feat)) return SE3_ERR_INVALID_ARGUMENT;
   if (s->n_edges > 0 && !neighbors) return SE3_ERR_INVALID_ARGUMENT;
   if (want_feat && s->n_in > 0 && (!t_ends || (s->n_edges > 0 && !t_samples))) return SE3_ERR_INVALID_ARGUMENT;
-  const BwdLayout l = bwd_layout(s, want_feat, want_params, t_save != nullptr);
-  if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
+  const BwdPlan p = plan_bwd(s, want_feat, want_params, t_save != nullptr);
+  if (workspace_bytes < p.total) return SE3_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)workspace;
-  float* axes_ext = (float*)(ws + l.axes_ext);
-  float* big = (float*)(ws + l.big);
+  float* axes_ext = (float*)(ws + p.axes_ext);
+  float* big = (float*)(ws + p.big);
   const int kb = s->num_basis;
   const int ck = s->c_in * kb;
   const int64_t rows_out = s->n_out * s->f_out, rows_in = s->n_in * s->f_in;
   const float inv_fin = 1.0f / (float)s->f_in;
+  float* partials = (float*)(ws + p.param_partials);
+  float* tn_partials = (float*)(ws + p.tn_partials);
 
-  EdgeGeom g = forward_geom(pts_in, pts_out, frames_in, frames_out, neighbors, ends, s);
-  // transposed graph: centre = input point, edges lead to output points (feature gradient)
-  EdgeGeom gt{};
-  gt.ctr_pts = pts_in, gt.ctr_frames = frames_in, gt.nb_pts = pts_out, gt.nb_frames = frames_out;
-  gt.nbr = t_samples, gt.nbr_stride = 1, gt.nbr_offset = 0, gt.ends = t_ends;
-  gt.n_ctr = s->n_in, gt.f_ctr = s->f_in, gt.f_nb = s->f_out, gt.transposed = 1;
-  gt.n_nb = s->n_out;
-  gt.n_edges = s->n_edges;
-  float* partials = (float*)(ws + l.param_partials);
-  float* tn_partials = (float*)(ws + l.tn_partials);
+  EdgeGeom g = forward_geom(s, pts_in, pts_out, frames_in, frames_out, neighbors, ends);
+  EdgeGeom gt = transposed_geom(s, pts_in, pts_out, frames_in, frames_out, t_samples, t_ends);
+  // one launch: [A; beta] table and the packed geometry records of both sides; split-bf16: the packed words of g and f and
+  // the weight planes too
+  PrepBatch pb;
+  pb.axes(proj_axes, proj_biases, axes_ext);
+  prepare_geometry(pb, prep, s, (float*)(ws + p.geom_in), (float*)(ws + p.geom_out), &g, &gt);
 
-  if (s->precision == SE3_PRECISION_FP32) {
-    {  // one launch: [A; beta] table and the packed geometry records of both sides
-      const bool same_cloud = pts_in == pts_out && frames_in == frames_out && s->n_in == s->n_out && s->f_in == s->f_out;
-      const PreparedGeometry pg = prepared_geometry(prep, same_cloud, (float*)(ws + l.geom_in), (float*)(ws + l.geom_out));
-      float* geom_in = pg.in;
-      float* geom_out = pg.out;
-      PrepBatch pb;
-      pb.axes(proj_axes, proj_biases, axes_ext);
-      if (pg.need_in) pb.geometry(pts_in, frames_in, s->n_in, s->f_in, geom_in);
-      if (pg.need_out) pb.geometry(pts_out, frames_out, s->n_out, s->f_out, geom_out);
-      if (int rc = pb.launch(stream)) return rc;
-      g.ctr_geom = geom_out, g.nb_geom = geom_in;
-      gt.ctr_geom = geom_in, gt.nb_geom = geom_out;
-    }
+  if (!p.fast) {
+    if (int rc = pb.launch(stream)) return rc;
     if (want_params) {
       // gT[m,(i,k)] = alpha * sum_o g[m,o] W[i,k,o]
-      float* wt = (float*)(ws + l.wt);
+      float* wt = (float*)(ws + p.wt);
       hipLaunchKernelGGL(transpose_kernel, dim3(grid_for((int64_t)ck * s->c_out)), dim3(256), 0, stream, conv_weights,
                          wt, ck, s->c_out);
       if (int rc = launch_gemm_nn("gemm_gradT", grad_out, wt, big, rows_out, ck, s->c_out, nu, inv_fin, stream)) return rc;
       if (grad_axes || grad_biases) {
         int n_part = 0;
         if (int rc = launch_edge_param_grad("edge_param_grad", g, feat, s->c_in, rows_in, axes_ext, rho, big, partials,
-                                            l.n_param_partials, &n_part, stream))
+                                            p.n_param_partials, &n_part, stream))
           return rc;
         hipLaunchKernelGGL(reduce_param_partials_kernel, dim3(kDescExt * kBasis), dim3(256), 0, stream, partials,
                            n_part, grad_axes, grad_biases, 1.0f);
       }
       if (grad_weights) {
         const float* t = t_save;
-        if (!t) {
-          float* tt = (float*)(ws + l.t);
+        if (p.dw == WeightGrad::t_recomputed) {
+          float* tt = (float*)(ws + p.t);
           if (int rc = launch_edge_t("edge_t_recompute", g, feat, s->c_in, rows_in, axes_ext, rho, tt, stream)) return rc;
           t = tt;
         }
         // dW[(i,k),o] = alpha * sum_m T[m,(i,k)] g[m,o]
-        if (int rc = launch_gemm_tn("gemm_gradW", t, grad_out, grad_weights, tn_partials, l.tn_splits, rows_out, ck,
-                                    s->c_out, nu, inv_fin, stream))
+        if (int rc = launch_gemm_tn("gemm_gradW", t, grad_out, grad_weights, tn_partials, p.tn.splits, p.tn.m, p.tn.ka,
+                                    p.tn.n, nu, inv_fin, stream))
           return rc;
       }
     }
-    if (want_feat && rows_in > 0) {
+    if (p.feat_branch) {
       // Transposed convolution instead of scatter atomics:
       //   U[(p,b),o,k] = sum_{edges into p} sum_a phi(s,a,p,b)[k] g[(s,a),o];  dX[(p,b),i] = alpha * sum_{o,k} U W[i,k,o]
-      if (int rc = launch_edge_t("edge_t_transposed", gt, grad_out, s->c_out, rows_out, axes_ext, rho, big, stream)) return rc;
-      float* w2 = (float*)(ws + l.w2);
+      float* u = (float*)(ws + p.u);
+      if (int rc = launch_edge_t("edge_t_transposed", gt, grad_out, s->c_out, rows_out, axes_ext, rho, u, stream)) return rc;
+      float* w2 = (float*)(ws + p.w2);
       hipLaunchKernelGGL(permute_weights_oki_kernel, dim3(grid_for((int64_t)ck * s->c_out)), dim3(256), 0, stream,
                          conv_weights, w2, s->c_in, kb, s->c_out);
-      if (int rc = launch_gemm_nn("gemm_gradX", big, w2, grad_feat, rows_in, s->c_in, s->c_out * kb, nu, inv_fin, stream,
-                                  (float*)(ws + l.split)))
+      if (int rc = launch_gemm_nn("gemm_gradX", u, w2, grad_feat, rows_in, s->c_in, s->c_out * kb, nu, inv_fin, stream,
+                                  (float*)(ws + p.split_x)))
         return rc;
     }
     return check_launch();
   }
 
   // ---- split-bf16 path: same stages, operands as packed words -----------------------------------------
-  uint16_t* bt_hi = (uint16_t*)(ws + l.bt_hi);    // parameter branch: grad_T weights
-  uint16_t* bt_lo = (uint16_t*)(ws + l.bt_lo);
-  uint16_t* bx_hi = (uint16_t*)(ws + l.bt2_hi);   // feature branch: grad_X weights
-  uint16_t* bx_lo = (uint16_t*)(ws + l.bt2_lo);
-  uint32_t* gpk = (uint32_t*)(ws + l.gpk);
+  const bool u_form = p.feat_branch && p.feat == FeatGrad::u, edge_major = p.feat == FeatGrad::edge_major;
+  uint16_t* bt_hi = (uint16_t*)(ws + p.bt_hi);    // parameter branch: grad_T weights
+  uint16_t* bt_lo = (uint16_t*)(ws + p.bt_lo);
+  uint16_t* bx_hi = (uint16_t*)(ws + p.bx_hi);    // feature branch: grad_X weights
+  uint16_t* bx_lo = (uint16_t*)(ws + p.bx_lo);
+  uint32_t* gpk = (uint32_t*)(ws + p.gpk);
   // (the packed feature words the forward call left with the caller, se3conv_prepared, or this call's own)
   const bool have_featpk = prep && prep->feat_words && prep->feat_words_valid;
-  uint32_t* featpk = prep && prep->feat_words ? prep->feat_words : (uint32_t*)(ws + l.featpk);
+  uint32_t* featpk = prep && prep->feat_words ? prep->feat_words : (uint32_t*)(ws + p.featpk);
   uint32_t* bigw = (uint32_t*)big;
-  uint32_t* big_u = (uint32_t*)(ws + l.big_u);  // U when both branches run (grad_T takes `big`)
+  uint32_t* u = (uint32_t*)(ws + p.u);
   const float inv_phi = inv_fin / kGeluOut;  // T and U hold kGeluOut * (the reference's values), see gelu_scaled
-  const bool feat_branch = want_feat && rows_in > 0;
-  const int t24_t = row_format(s, g, s->c_in, rows_out, s->c_out);  // as se3conv_fwd
-  const int t24_u = feat_branch ? row_format(s, gt, s->c_out, rows_in, 0) : 0;
-  const bool strip_t = gemm_strip_bf16_applicable(rows_out, ck, s->c_out);            // grad_T = g W^T
-  const bool edge_dx = use_edge_dx(s, want_feat, want_params) && feat_branch;         // feature gradient edge-major (edge_dx.hip)
-  {  // one launch: [A; beta] table, packed geometry records, packed words of g and f, weight planes
-    const bool same_cloud = pts_in == pts_out && frames_in == frames_out && s->n_in == s->n_out && s->f_in == s->f_out;
-    const PreparedGeometry pg = prepared_geometry(prep, same_cloud, (float*)(ws + l.geom_in), (float*)(ws + l.geom_out));
-    float* geom_in = pg.in;
-    float* geom_out = pg.out;
-    PrepBatch pb;
-    pb.axes(proj_axes, proj_biases, axes_ext);
-    if (pg.need_in) pb.geometry(pts_in, frames_in, s->n_in, s->f_in, geom_in);
-    if (pg.need_out) pb.geometry(pts_out, frames_out, s->n_out, s->f_out, geom_out);
-    pb.split(grad_out, gpk, rows_out * s->c_out);
-    if (feat_branch && !edge_dx) pb.weights(conv_weights, s->c_in, kb, s->c_out, 2, bx_hi, bx_lo, nullptr, 1.0f, false, t24_u);
-    if (want_params && !have_featpk) pb.split(feat, featpk, rows_in * s->c_in);
-    if (want_params || edge_dx)
-      // alpha = nu/F_in is folded into these weights (one multiply per weight instead of one per grad_T element)
-      pb.weights(conv_weights, s->c_in, kb, s->c_out, 1, bt_hi, bt_lo, nu, inv_fin, strip_t);
-    if (int rc = pb.launch(stream)) return rc;
-    g.ctr_geom = geom_out, g.nb_geom = geom_in;
-    gt.ctr_geom = geom_in, gt.nb_geom = geom_out;
-  }
+  pb.split(grad_out, gpk, rows_out * s->c_out);
+  if (u_form) pb.weights(conv_weights, s->c_in, kb, s->c_out, 2, bx_hi, bx_lo, nullptr, 1.0f, false, p.fmt_u);
+  if (want_params && !have_featpk) pb.split(feat, featpk, rows_in * s->c_in);
+  if (p.grad_t)
+    // alpha = nu/F_in is folded into these weights (one multiply per weight instead of one per grad_T element)
+    pb.weights(conv_weights, s->c_in, kb, s->c_out, 1, bt_hi, bt_lo, nu, inv_fin, p.strip_t);
+  if (int rc = pb.launch(stream)) return rc;
   // The sums that end the pass -- split-K partials of the grad_X GEMM, row-range partials of the weight-gradient GEMM,
   // per-workgroup partials of d[A; beta] -- write final outputs nobody in this call reads: one launch folds them all
   ReduceBatch final_sums;
-  const bool dw_u = grad_weights != nullptr && feat_branch && !edge_dx && use_u_for_dw(s, want_feat, want_params, t_save != nullptr);
-  // grad_T[m,(i,k)] = sum_o g[m,o] W'[i,k,o] into `big`
-  auto grad_t = [&]() -> int {
-    if (strip_t) return launch_gemm_strip_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, rows_out, ck, s->c_out, stream);
-    return launch_gemm_nn_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, true, rows_out, ck, s->c_out, (float*)(ws + l.split),
-                               nullptr, 1.0f, stream);
-  };
-  auto weight_gradient = [&]() -> int {
-    if (!grad_weights) return SE3_OK;
-    if (dw_u)  // C'[(o,k), i] = sum_p U[p,(o,k)] f[p,i]; the batched reduction stores it as dW[i,k,o]
-      return launch_gemm_tn_bf16("gemm_gradW", big_u, featpk, grad_weights, tn_partials, l.tn_splits, rows_in, s->c_out * kb,
-                                 s->c_in, nu, inv_phi, stream, t24_u, &final_sums, true);
-    const uint32_t* t = (const uint32_t*)t_save;
-    if (!t) {
-      uint32_t* tt = (uint32_t*)(ws + l.t);
-      if (int rc = launch_edge_t_bf16("edge_t_recompute", g, featpk, s->c_in, rows_in, axes_ext, rho, tt, stream, t24_t)) return rc;
-      t = tt;
-    }
-    return launch_gemm_tn_bf16("gemm_gradW", t, gpk, grad_weights, tn_partials, l.tn_splits, rows_out, ck, s->c_out, nu,
-                               inv_phi, stream, t24_t, &final_sums);
-  };
-  // d[A; beta]: per-workgroup partial sums; their fixed-order reduction joins the batch (the bf16 kernels accumulate with
-  // 2 GELU', gelu_scaled_grad: the 0.5 is applied there)
-  auto param_gradients = [&]() -> int {
-    if (!grad_axes && !grad_biases) return SE3_OK;
-    int n_part = 0;
-    if (int rc = launch_edge_param_grad_bf16("edge_param_grad", g, featpk, s->c_in, rows_in, axes_ext, rho, bigw, partials,
-                                             l.n_param_partials, &n_part, stream))
-      return rc;
-    final_sums.params(partials, n_part, grad_axes, grad_biases, 0.5f);
-    return SE3_OK;
-  };
 
-  if (edge_dx) {
-    // grad_T first (both branches read it), then the edge-major feature gradient and its per-source sums, then the
-    // parameter branch
-    if (int rc = grad_t()) return rc;
-    float* d_rows = (float*)(ws + l.dx_rows);
+  // One sequence of stages for every request, each behind its flag of the plan.  Writers first: the two kernels that write
+  // a row-sized tensor (U, grad_T) go first, their readers after them.  Whatever runs right behind a ~1 GB writer is slowed
+  // while the caches drain (a memory-bound reader by 15-30 %, whichever tensor it reads): in the order  U-writer, grad_X
+  // GEMM, grad_T writer, parameter gradients  two readers sit in that position, here only one does (gemm_gradX 0.221 ->
+  // 0.187 ms at the headline shape).
+  if (u_form) {
+    if (int rc = launch_edge_t_bf16("edge_t_transposed", gt, gpk, s->c_out, rows_out, axes_ext, rho, u, stream, p.fmt_u))
+      return rc;
+  }
+  if (p.grad_t) {  // grad_T[m,(i,k)] = sum_o g[m,o] W'[i,k,o] into `big`
+    if (int rc = p.strip_t ? launch_gemm_strip_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, rows_out, ck, s->c_out, stream)
+                           : launch_gemm_nn_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, true, rows_out, ck, s->c_out,
+                                                 (float*)(ws + p.split), nullptr, 1.0f, stream))
+      return rc;
+  }
+  if (edge_major) {  // the feature gradient per frame-edge from grad_T, then its per-source sums
+    float* d_rows = (float*)(ws + p.dx_rows);
     if (int rc = launch_edge_dx_bf16("edge_dx", g, axes_ext, rho, bigw, s->c_in, d_rows, stream)) return rc;
     if (int rc = launch_dx_gather_sum("dx_gather", d_rows, neighbors, ends, t_samples, t_ends, t_edge_ids, s->n_in, s->f_in * s->c_in,
                                       1.0f / kGeluOut, grad_feat, stream))
       return rc;
-    if (want_params) {
-      if (int rc = param_gradients()) return rc;
-      if (int rc = weight_gradient()) return rc;
+  }
+  if (grad_axes || grad_biases) {
+    // d[A; beta]: per-workgroup partial sums; their fixed-order reduction joins the batch (the bf16 kernels accumulate with
+    // 2 GELU', gelu_scaled_grad: the 0.5 is applied there)
+    int n_part = 0;
+    if (int rc = launch_edge_param_grad_bf16("edge_param_grad", g, featpk, s->c_in, rows_in, axes_ext, rho, bigw, partials,
+                                             p.n_param_partials, &n_part, stream))
+      return rc;
+    final_sums.params(partials, n_part, grad_axes, grad_biases, 0.5f);
+  }
+  if (u_form) {
+    if (int rc = launch_gemm_nn_bf16("gemm_gradX", u, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
+                                     (float*)(ws + p.split_x), nu, inv_phi, stream, p.fmt_u, &final_sums))
+      return rc;
+  }
+  if (grad_weights) {
+    if (p.dw == WeightGrad::u) {  // C'[(o,k), i] = sum_p U[p,(o,k)] f[p,i]; the batched reduction stores it as dW[i,k,o]
+      if (int rc = launch_gemm_tn_bf16("gemm_gradW", u, featpk, grad_weights, tn_partials, p.tn.splits, p.tn.m, p.tn.ka, p.tn.n,
+                                       nu, inv_phi, stream, p.fmt_u, &final_sums, true))
+        return rc;
+    } else {  // dW[(i,k),o] = sum_m T[m,(i,k)] g[m,o]
+      const uint32_t* t = (const uint32_t*)t_save;
+      if (p.dw == WeightGrad::t_recomputed) {
+        uint32_t* tt = (uint32_t*)(ws + p.t);
+        if (int rc = launch_edge_t_bf16("edge_t_recompute", g, featpk, s->c_in, rows_in, axes_ext, rho, tt, stream, p.fmt_t)) return rc;
+        t = tt;
+      }
+      if (int rc = launch_gemm_tn_bf16("gemm_gradW", t, gpk, grad_weights, tn_partials, p.tn.splits, p.tn.m, p.tn.ka, p.tn.n, nu,
+                                       inv_phi, stream, p.fmt_t, &final_sums))
+        return rc;
     }
-  } else if (feat_branch && want_params) {
-    // Both branches, writers first: the two kernels that write a row-sized tensor (U, grad_T) go first, their readers
-    // after them.  Whatever runs right behind a ~1 GB writer is slowed while the caches drain (a memory-bound reader by
-    // 15-30 %, whichever tensor it reads): in the order  U-writer, grad_X GEMM, grad_T writer, parameter gradients  two
-    // readers sit in that position, here only one does (gemm_gradX 0.221 -> 0.187 ms at the headline shape).
-    if (int rc = launch_edge_t_bf16("edge_t_transposed", gt, gpk, s->c_out, rows_out, axes_ext, rho, big_u, stream, t24_u))
-      return rc;
-    if (int rc = grad_t()) return rc;
-    if (int rc = param_gradients()) return rc;
-    if (int rc = launch_gemm_nn_bf16("gemm_gradX", big_u, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
-                                     (float*)(ws + l.split2), nu, inv_phi, stream, t24_u, &final_sums))
-      return rc;
-    if (int rc = weight_gradient()) return rc;
-  } else if (feat_branch) {
-    // feature gradient only: U into `big`, then the grad_X GEMM
-    if (int rc = launch_edge_t_bf16("edge_t_transposed", gt, gpk, s->c_out, rows_out, axes_ext, rho, bigw, stream, t24_u))
-      return rc;
-    if (int rc = launch_gemm_nn_bf16("gemm_gradX", bigw, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
-                                     (float*)(ws + l.split), nu, inv_phi, stream, t24_u, &final_sums))
-      return rc;
-  } else if (want_params) {
-    if (int rc = grad_t()) return rc;
-    if (int rc = param_gradients()) return rc;
-    if (int rc = weight_gradient()) return rc;
   }
   return final_sums.launch(stream);
 }

@@ -78,7 +78,8 @@ COVERED = {
     "se3conv_fwd": ["test_fused_random_shapes_other_basis_counts_at_the_c_abi"],
     "se3conv_bwd": ["test_fused_random_shapes_other_basis_counts_at_the_c_abi"],
     "se3conv_fwd_prepared": [FUSED_TEST, "test_fused_through_autograd_against_oracle", "test_down_and_up_layers_through_the_module"],
-    "se3conv_bwd_prepared": [FUSED_TEST, "test_fused_through_autograd_against_oracle", "test_down_and_up_layers_through_the_module"],
+    "se3conv_bwd_prepared": [FUSED_TEST, "test_fused_through_autograd_against_oracle", "test_down_and_up_layers_through_the_module",
+                             "test_fused_partial_parameter_requests_at_the_c_abi"],
     "se3_bn_fwd": ["test_batch_norm_forward_and_backward"],
     "se3_bn_bwd": ["test_batch_norm_forward_and_backward"],
     "se3_affine_act": ["test_bias_gelu_forward_and_backward"],
@@ -423,6 +424,80 @@ def test_fused_random_shapes_other_basis_counts_at_the_c_abi(amd, case, precisio
     """K = 8, 40, 70 through se3conv_fwd / se3conv_bwd: the padded [A; beta; W] slice of the K != 32 path lives in the
     workspace, next to the inner call's share."""
     check_fused(amd, case, precision, [(req, (False, False, False)) for req in REQUESTS])
+
+
+PARTIAL_CASES = [c for c in FUSED if c.name in ("c64_64_dense", "down", "c3_13_f1_f3")]  # dW from U / edge-major / dW from a recomputed T
+PARTIAL_REQUESTS = [("dW",), ("dA", "dbeta")]
+
+
+@pytest.mark.parametrize("precision", ["bf16x3", "fp32"])
+@pytest.mark.parametrize("case", PARTIAL_CASES, ids=[c.name for c in PARTIAL_CASES])
+def test_fused_partial_parameter_requests_at_the_c_abi(amd, request, case, precision):
+    """se3conv_bwd_prepared with only `grad_weights`, and with only `grad_axes` + `grad_biases` (ops.se3conv_backward always
+    passes all three), `t_save` = NULL, with and without `grad_feat`.  The call is planned from "any parameter gradient"
+    (api.hip, BwdPlan): a NULL pointer only skips a stage, it never selects another buffer or another form.  So every
+    requested output passes parity AND is bit for bit what the call with all outputs gives, the workspace of the all-
+    parameters query suffices, and the launch counts drop exactly the skipped stages: gemm_gradW (and the recomputation of
+    T that feeds it) runs only with grad_weights, edge_param_grad only with an axes or bias gradient, gemm_gradT whenever
+    any parameter gradient or the edge-major form is asked for."""
+    from se3conv3d_amd import _lib
+    ops, ptr = amd.ops, amd.ops._ptr
+    assert len(PARTIAL_CASES) == 3
+    c, nb, ends_ref, rho, nu, ref = fused_data(case)
+    ref = dict(zip(("out", "dx", "dA", "dbeta", "dW"), ref))
+    i32, f32 = torch.int32, torch.float32
+    with guarded(request) as arena:
+        lib = _lib.load()
+        put = arena.place
+        pts_in = put(c["pts_in"])
+        pts_out = pts_in if c["pts_out"] is c["pts_in"] else put(c["pts_out"])
+        fi = put(c["fi"])
+        fo = fi if c["fo"] is c["fi"] else put(c["fo"])
+        geom = ops.ConvGeometry.build(pts_in, pts_out, fi, fo, put(nb), put(ends_ref))
+        x, a, b, w, go = (put(c[k]) for k in ("x", "a", "b", "w", "go"))
+        rho_t, nu_t = put(rho.to(f32)), put(nu.to(f32))
+        c_in, kb, c_out = w.shape
+        shp = geom.shape(c_in, c_out, kb, precision)
+        ts, te = geom.transpose()
+
+        def call(want_feat, keys):
+            outs = {"dx": ops._empty_like(x) if want_feat else None}
+            outs.update({k: ops._empty_like(t) if k in keys else None for k, t in (("dA", a), ("dbeta", b), ("dW", w))})
+            ws = ops._workspace(lib.se3conv_bwd_workspace_bytes(C.byref(shp), int(want_feat), 1, 0), DEV)
+            lib.se3_profile_reset(), lib.se3_profile_enable(1)
+            _lib.check(lib.se3conv_bwd_prepared(
+                *ops._geom_ptrs(geom), ptr(ts if want_feat else None, i32, "ts"), ptr(te if want_feat else None, i32, "te"),
+                ptr(geom._edge_ids if want_feat else None, i32, "ids"), ptr(x, f32, "x"), ptr(a, f32, "a"), ptr(b, f32, "b"),
+                ptr(w, f32, "w"), ptr(rho_t, f32, "rho"), ptr(nu_t, f32, "nu"), None, ptr(go, f32, "go"), C.byref(shp),
+                ptr(outs["dx"], f32, "dx"), ptr(outs["dA"], f32, "da"), ptr(outs["dbeta"], f32, "db"), ptr(outs["dW"], f32, "dw"),
+                C.c_void_p(ws.data_ptr()), ws.numel(), ops._stream(x.device), None), "se3conv_bwd_prepared")
+            torch.cuda.synchronize()
+            lib.se3_profile_enable(0)
+            stages = profile_counts(lib, STAGES)
+            lib.se3_profile_reset()
+            return {k: v.cpu().clone() for k, v in outs.items() if v is not None}, stages
+
+        for want_feat in (True, False):
+            full, _ = call(want_feat, ("dA", "dbeta", "dW"))
+            for keys in PARTIAL_REQUESTS:
+                what = (case.name, precision, f"want_feat={want_feat}", keys)
+                res, stages = call(want_feat, keys)
+                assert set(res) == set(keys) | ({"dx"} if want_feat else set()), what
+                for key in res:
+                    err = rel_err(res[key], ref[key])
+                    print(f"partial {what} {key}: rel err {err:.3e}, bitwise equal to the full call: {torch.equal(res[key], full[key])}")
+                    assert err < TOLS[precision], (what, key, err)
+                    assert torch.equal(res[key], full[key]), (what, key, "differs from the call with all outputs")
+                on = expected_stages(case, precision, want_feat, True, False, lib, shp)
+                assert "gemm_gradT" in on
+                if "dW" not in keys:
+                    on -= {"gemm_gradW", "edge_t_recompute"}
+                if not {"dA", "dbeta"} & set(keys):
+                    on -= {"edge_param_grad"}
+                print(f"stages {what}: {stages}")
+                for tag in STAGES:
+                    assert (stages[tag] > 0) == (tag in on), (what, tag, stages, sorted(on))
+            arena.check()
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3", "bf16x3_t16"])

@@ -16,6 +16,9 @@ What is NOT the reference: three native modules are not installed here and canno
 stand-ins below are deliberately naive loop/index_add implementations of their documented
 semantics, written independently of ``oracle/se3conv_oracle.py`` so the fixtures cross-check
 the oracle instead of echoing it.  Everything stored is data (inputs + outputs), no source.
+
+One fixture does not come from the reference: ``python tools/gen_golden.py workspace_plan`` records the answers of this
+library's own host-only queries (see ``workspace_plan_case``); only on request, never as part of a plain run.
 """
 import os
 import sys
@@ -676,10 +679,25 @@ CASES = [
 ]
 
 
+def workspace_plan_case():
+    """The library's own host-only queries (tests/workspace_plan_table.py), one table per environment: recorded from the
+    commit BEFORE a change that must leave every workspace size and every decision of a fused call as it is -- not part of a
+    plain run, which would overwrite the record with the current library's answers."""
+    from workspace_plan_table import ENVIRONMENTS, table_in_child
+    return {name: table_in_child(switches) for name, switches in ENVIRONMENTS.items()}
+
+
 def main():
+    only = sys.argv[1] if len(sys.argv) > 1 else ""
+    if only == "workspace_plan":
+        path = os.path.join(OUT, "workspace_plan.npz")
+        data = workspace_plan_case()
+        np.savez_compressed(path, **data)
+        print({k: int((v != data["default"]).any(axis=1).sum()) for k, v in data.items()}, "rows differ from the default")
+        print(f"{path}: shapes={len(data['default'])} size={os.path.getsize(path) / 1e6:.2f} MB")
+        return
     pclib = _import_reference()
     os.makedirs(OUT, exist_ok=True)
-    only = sys.argv[1] if len(sys.argv) > 1 else ""
     if only in ("", "hierarchy"):
         path = os.path.join(OUT, "hierarchy.npz")
         np.savez_compressed(path, **hierarchy_case(pclib, 11))

@@ -32,23 +32,44 @@ __device__ __forceinline__ void cell_of(const float* __restrict__ pts, const int
   }
 }
 
-__device__ __forceinline__ int64_t key_of(const int cell[3], const int nc[3], int b) {
-  // grid_utils.cuh:79-93
-  return (((int64_t)b * nc[0] + cell[0]) * nc[1] + cell[1]) * nc[2] + cell[2];
-}
+// Key policies of the grid kernels: the key type, the cell counts the keys are built with, the key of a cell.
+// Key64 is the reference's key (grid_utils.cuh:79-93): the true cell counts multiplied out.
+struct Key64 {
+  using type = int64_t;
+  __device__ static __forceinline__ int cells(int n) { return n; }
+  __device__ static __forceinline__ type key(const int cell[3], const int nc[3], int b) {
+    return (((int64_t)b * nc[0] + cell[0]) * nc[1] + cell[1]) * nc[2] + cell[2];
+  }
+};
+// ---- 32-bit keys for the ball query (one or two batch elements) ---------------------------------------------------
+// The reference's key (grid_utils.cuh:79-93) multiplies the true cell counts; how many bits it needs is only known on
+// the device, so the radix sort has to walk all 64 (8 passes over 8-byte keys; at 9 k points those passes are latency:
+// ~10 us each).  The ball query's own keys need not be the reference's -- only the edge SET is defined -- so for
+// n_batches <= 2 they are built with a fixed stride of 1024 cells per dimension: 30 + 1 bits, 4 passes over 4-byte
+// keys.  Cell indices beyond 1023 are clamped to 1023 (points of the far cells share one cell: candidates are a
+// superset there, the distance test decides), so any extent / radius ratio stays exact.
+constexpr int kBq32Cells = 1024;
+struct Key32 {
+  using type = uint32_t;
+  __device__ static __forceinline__ int cells(int n) { return min(n, kBq32Cells); }
+  __device__ static __forceinline__ type key(const int cell[3], const int[3], int b) {
+    return ((((uint32_t)b * kBq32Cells + (uint32_t)cell[0]) * kBq32Cells) + (uint32_t)cell[1]) * kBq32Cells + (uint32_t)cell[2];
+  }
+};
 
+template <class KEY>
 __global__ void compute_keys_kernel(const float* __restrict__ pts, const int32_t* __restrict__ batch_ids,
                                     const float* __restrict__ aabb_min, const int32_t* __restrict__ num_cells,
                                     const float* __restrict__ cell_size, float cell_scalar, int64_t n,
-                                    int64_t* __restrict__ keys, int32_t* __restrict__ iota) {
+                                    typename KEY::type* __restrict__ keys, int32_t* __restrict__ iota) {
   // cell_size == nullptr: the same cell size `cell_scalar` in every dimension (ball query: cell = radius)
-  const int nc[3] = {num_cells[0], num_cells[1], num_cells[2]};
+  const int nc[3] = {KEY::cells(num_cells[0]), KEY::cells(num_cells[1]), KEY::cells(num_cells[2])};
   const float inv[3] = {1.0f / (cell_size ? cell_size[0] : cell_scalar), 1.0f / (cell_size ? cell_size[1] : cell_scalar),
                         1.0f / (cell_size ? cell_size[2] : cell_scalar)};
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     int cell[3], b;
     cell_of(pts, batch_ids, aabb_min, nc, inv, i, cell, b);
-    keys[i] = key_of(cell, nc, b);
+    keys[i] = KEY::key(cell, nc, b);
     if (iota) iota[i] = (int32_t)i;
   }
 }
@@ -61,7 +82,8 @@ __global__ void gather_sorted_points_kernel(const float* __restrict__ pts, const
   }
 }
 
-__device__ __forceinline__ int lower_bound_key(const int64_t* __restrict__ keys, int n, int64_t v) {
+template <class K>
+__device__ __forceinline__ int lower_bound_key(const K* __restrict__ keys, int n, K v) {
   int lo = 0, hi = n;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -70,75 +92,20 @@ __device__ __forceinline__ int lower_bound_key(const int64_t* __restrict__ keys,
   return lo;
 }
 
-// ranges[s][o] = [lo, hi) positions in the sorted source order of pencil window o = (dx+1)*3 + (dy+1)
+// ranges[s][o] = [lo, hi) positions in the sorted source order of pencil window o = (dx+1)*3 + (dy+1): the keys
+// [key(x, y, z0), key(x, y, z0) + (z1 - z0) + 1), which are consecutive under either policy
+template <class KEY>
 __global__ void find_ranges_kernel(const float* __restrict__ pts_dst, const int32_t* __restrict__ batch_dst,
                                    const float* __restrict__ aabb_min, const int32_t* __restrict__ num_cells,
-                                   float radius, const int64_t* __restrict__ skeys, int n_src, int64_t n_dst,
+                                   float radius, const typename KEY::type* __restrict__ skeys, int n_src, int64_t n_dst,
                                    int2* __restrict__ ranges, const int32_t* __restrict__ order) {
-  const int nc[3] = {num_cells[0], num_cells[1], num_cells[2]};
+  const int nc[3] = {KEY::cells(num_cells[0]), KEY::cells(num_cells[1]), KEY::cells(num_cells[2])};
   const float inv_r = 1.0f / radius;
   const float inv[3] = {inv_r, inv_r, inv_r};
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_dst * 9; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t j = i / 9;
     const int o = (int)(i - j * 9);
-    const int64_t s = order ? order[j] : j;  // a cloud against itself: samples in cell order (see ball_query_count_impl)
-    int cell[3], b;
-    cell_of(pts_dst, batch_dst, aabb_min, nc, inv, s, cell, b);
-    const int x = cell[0] + o / 3 - 1, y = cell[1] + o % 3 - 1;
-    int2 r = make_int2(0, 0);
-    if (x >= 0 && x < nc[0] && y >= 0 && y < nc[1]) {
-      const int z0 = max(cell[2] - 1, 0), z1 = min(cell[2] + 1, nc[2] - 1);
-      const int64_t base = (((int64_t)b * nc[0] + x) * nc[1] + y) * nc[2];
-      r.x = lower_bound_key(skeys, n_src, base + z0);
-      r.y = lower_bound_key(skeys, n_src, base + z1 + 1);
-    }
-    ranges[s * 9 + o] = r;
-  }
-}
-
-// ---- 32-bit keys for the ball query (one or two batch elements) ---------------------------------------------------
-// The reference's key (grid_utils.cuh:79-93) multiplies the true cell counts; how many bits it needs is only known on
-// the device, so the radix sort has to walk all 64 (8 passes over 8-byte keys; at 9 k points those passes are latency:
-// ~10 us each).  The ball query's own keys need not be the reference's -- only the edge SET is defined -- so for
-// n_batches <= 2 they are built with a fixed stride of 1024 cells per dimension: 30 + 1 bits, 4 passes over 4-byte
-// keys.  Cell indices beyond 1023 are clamped to 1023 (points of the far cells share one cell: candidates are a
-// superset there, the distance test decides), so any extent / radius ratio stays exact.
-constexpr int kBq32Cells = 1024;
-__device__ __forceinline__ uint32_t key32_of(const int cell[3], int b) {
-  return ((((uint32_t)b * kBq32Cells + (uint32_t)cell[0]) * kBq32Cells) + (uint32_t)cell[1]) * kBq32Cells + (uint32_t)cell[2];
-}
-__global__ void compute_keys32_kernel(const float* __restrict__ pts, const int32_t* __restrict__ batch_ids,
-                                      const float* __restrict__ aabb_min, const int32_t* __restrict__ num_cells,
-                                      float cell_scalar, int64_t n, uint32_t* __restrict__ keys,
-                                      int32_t* __restrict__ iota) {
-  const int nc[3] = {min(num_cells[0], kBq32Cells), min(num_cells[1], kBq32Cells), min(num_cells[2], kBq32Cells)};
-  const float inv[3] = {1.0f / cell_scalar, 1.0f / cell_scalar, 1.0f / cell_scalar};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int cell[3], b;
-    cell_of(pts, batch_ids, aabb_min, nc, inv, i, cell, b);
-    keys[i] = key32_of(cell, b);
-    iota[i] = (int32_t)i;
-  }
-}
-__device__ __forceinline__ int lower_bound_key32(const uint32_t* __restrict__ keys, int n, uint32_t v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (keys[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-__global__ void find_ranges32_kernel(const float* __restrict__ pts_dst, const int32_t* __restrict__ batch_dst,
-                                     const float* __restrict__ aabb_min, const int32_t* __restrict__ num_cells,
-                                     float radius, const uint32_t* __restrict__ skeys, int n_src, int64_t n_dst,
-                                     int2* __restrict__ ranges, const int32_t* __restrict__ order) {
-  const int nc[3] = {min(num_cells[0], kBq32Cells), min(num_cells[1], kBq32Cells), min(num_cells[2], kBq32Cells)};
-  const float inv_r = 1.0f / radius;
-  const float inv[3] = {inv_r, inv_r, inv_r};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_dst * 9; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t j = i / 9;
-    const int o = (int)(i - j * 9);
-    const int64_t s = order ? order[j] : j;  // a cloud against itself: samples in cell order (see ball_query_count_impl)
+    const int64_t s = order ? order[j] : j;  // a cloud against itself: samples in cell order (see BqPlan::ordered)
     int cell[3], b;
     cell_of(pts_dst, batch_dst, aabb_min, nc, inv, s, cell, b);
     const int x = cell[0] + o / 3 - 1, y = cell[1] + o % 3 - 1;
@@ -146,9 +113,9 @@ __global__ void find_ranges32_kernel(const float* __restrict__ pts_dst, const in
     if (x >= 0 && x < nc[0] && y >= 0 && y < nc[1]) {
       const int z0 = max(cell[2] - 1, 0), z1 = min(cell[2] + 1, nc[2] - 1);
       const int c0[3] = {x, y, z0};
-      const uint32_t base = key32_of(c0, b);
-      r.x = lower_bound_key32(skeys, n_src, base);
-      r.y = lower_bound_key32(skeys, n_src, base + (uint32_t)(z1 - z0) + 1u);
+      const typename KEY::type base = KEY::key(c0, nc, b);
+      r.x = lower_bound_key(skeys, n_src, base);
+      r.y = lower_bound_key(skeys, n_src, (typename KEY::type)(base + (typename KEY::type)(z1 - z0) + 1));
     }
     ranges[s * 9 + o] = r;
   }
@@ -220,15 +187,23 @@ struct CapKept {
   }
 };
 
-// One wavefront per sample.  MODE 0: counts[s] = #hits.  MODE 1: neighbors[base + j] = (s, source id) for the j-th hit
-// in candidate order, base from the inclusive offsets `ends`.  MODE 2 (capacity-bounded call): the same, slots at or
-// beyond `limit` dropped, the sample's own offset clamped to `limit` in place (its neighbour reads ends[s-1] either
-// way and clamps what it reads), the last sample records the true total and the overflow flag in `info`, and
-// `sources` (optional) receives the source ids alone -- the source-major list of a cloud against itself.
-// CAPPED (store modes of se3_ball_query_capped): a hit is stored iff its key is at most tau[s], the sample's threshold
+// The passes of a ball query.  One wavefront per sample scans the sample's candidates 64 at a time, in both kernels below.
+// CAPPED (store passes of se3_ball_query_capped): a hit is stored iff its key is at most tau[s], the sample's threshold
 // from the threshold pass (kCapNoKey for a sample under the cap); `counts` / `ends` then already hold the capped degrees.
-// MODE 4 (CAPPED only) is that threshold pass: after the count pass it writes degrees[s] = c (optional), and for c > m
-// finds the m smallest keys of the sample's hits, leaves the m-th in tau[s] and replaces counts[s] by m.
+enum class BqPass {
+  kCount,         // counts[s] = #hits
+  kStore,         // neighbors[base + j] = (s, source id) for the j-th hit in candidate order, base from the inclusive
+                  // offsets `ends` (the store call of the two-phase ABI)
+  kStoreBounded,  // capacity-bounded call: the same, slots at or beyond `limit` dropped, the sample's own offset clamped to
+                  // `limit` in place (its neighbour reads ends[s-1] either way and clamps what it reads), the last sample
+                  // records the true total and the overflow flag in `info`, and `sources` (optional) receives the source
+                  // ids alone -- the source-major list of a cloud against itself
+  kStoreBoundedInlinePrefix,  // bounded all-pairs call with few samples: no scan launch at all -- every wavefront sums the
+                  // counts in front of its sample itself (n_dst / 64 loads per lane), writes the sample's clamped
+                  // inclusive offset, stores, and the last sample records total + overflow flag
+  kThreshold,     // CAPPED only, after the count pass: degrees[s] = c (optional), and for c > m finds the m smallest keys of
+                  // the sample's hits, leaves the m-th in tau[s] and replaces counts[s] by m
+};
 struct CapArgs {
   int m;
   uint32_t seed;
@@ -236,58 +211,133 @@ struct CapArgs {
   uint64_t* tau;
   int32_t* degrees;
 };
-template <int MODE, bool CAPPED = false>
-__global__ __launch_bounds__(256) void scan_candidates_kernel(const float* __restrict__ pts_dst, float inv_r,
-                                                              const float4* __restrict__ spts,
-                                                              const int2* __restrict__ ranges, int64_t n_dst,
-                                                              int32_t* __restrict__ counts, int32_t* __restrict__ ends,
-                                                              int32_t* __restrict__ neighbors, int limit,
-                                                              int32_t* __restrict__ sources, int32_t* __restrict__ info,
-                                                              const int32_t* __restrict__ order, CapArgs cap = CapArgs{}) {
-  static_assert(MODE != 4 || CAPPED, "the threshold pass belongs to the capped query");
-  constexpr bool STORE = MODE != 0 && MODE != 4;
+// What a scan kernel is handed.  A pass reads only what it needs: the rest may be NULL.
+struct BqScanArgs {
+  const float* pts_dst;
+  const int32_t* batch_dst;  // all-pairs path: the batch test
+  float inv_r;
+  int64_t n_dst;
+  int32_t* counts;     // per-sample hit counts (workspace)
+  int32_t* ends;       // inclusive offsets: read by the store passes, written by the inline prefix
+  int32_t* neighbors;
+  int limit;           // rows of `neighbors`
+  int32_t* sources;
+  int32_t* info;
+  CapArgs cap;
+  // grid path: (x, y, z, source id) in sorted-key order, the nine windows of every sample, the samples' cell order (or NULL)
+  // all-pairs path: `recs` holds (x, y, z, batch id) per source, written by the count pass from pts_src / batch_src
+  float4* recs;
+  const int2* ranges;
+  const int32_t* order;
+  const float* pts_src;
+  const int32_t* batch_src;
+  int n_src;
+};
+
+// One sample of one pass, in the lanes of its wavefront: begin, consume 64 candidates at a time in candidate order, finish.
+template <BqPass PASS, bool CAPPED>
+struct BqSample {
+  static constexpr bool kThreshold = PASS == BqPass::kThreshold;
+  static constexpr bool kStore = PASS != BqPass::kCount && !kThreshold;
+  static constexpr bool kBounded = PASS == BqPass::kStoreBounded || PASS == BqPass::kStoreBoundedInlinePrefix;
+  int64_t s;
+  int lane, found, base;
+  uint32_t sample_hash;
+  uint64_t tau;
+  CapKept kept;
+
+  // false: the sample is settled without a look at its candidates (threshold pass: it is under the cap)
+  __device__ __forceinline__ bool begin(const BqScanArgs& a, int64_t sample, int lane_of_wave) {
+    s = sample, lane = lane_of_wave, found = 0, base = 0;
+    sample_hash = 0;
+    tau = kCapNoKey;
+    if (CAPPED) {
+      sample_hash = cap_sample_hash(a.cap.seed, a.cap.seed_device, s);
+      if (kThreshold) {
+        const int c = a.counts[s];
+        if (lane == 0) {
+          if (a.cap.degrees) a.cap.degrees[s] = c;
+          if (c <= a.cap.m) a.cap.tau[s] = kCapNoKey;
+        }
+        if (c <= a.cap.m) return false;
+        kept.init();
+      } else {
+        tau = a.cap.tau[s];
+      }
+    }
+    if (PASS == BqPass::kStore || PASS == BqPass::kStoreBounded) base = s > 0 ? a.ends[s - 1] : 0;
+    if (PASS == BqPass::kStoreBounded) {  // offsets from the scan: clamped in place
+      base = min(base, a.limit);
+      if (lane == 0) {
+        const int e = a.ends[s];
+        if (s == a.n_dst - 1) a.info[0] = e, a.info[1] = e > a.limit ? 1 : 0;
+        if (e > a.limit) a.ends[s] = a.limit;
+      }
+    }
+    if (PASS == BqPass::kStoreBoundedInlinePrefix) {
+      int acc = 0;
+      for (int64_t j = lane; j < s; j += 64) acc += a.counts[j];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+      const int e = acc + a.counts[s];
+      base = min(acc, a.limit);
+      if (lane == 0) {
+        a.ends[s] = min(e, a.limit);
+        if (s == a.n_dst - 1) a.info[0] = e, a.info[1] = e > a.limit ? 1 : 0;
+      }
+    }
+    return true;
+  }
+
+  // this lane's candidate: a hit or not, and its source id
+  __device__ __forceinline__ void consume(const BqScanArgs& a, bool hit, int id) {
+    if (kThreshold) {
+      kept.add(hit ? cap_key(sample_hash, id) : kCapNoKey, lane, a.cap.m);
+      return;
+    }
+    if (CAPPED) hit = hit && cap_key(sample_hash, id) <= tau;
+    const unsigned long long mask = __ballot(hit);
+    if (kStore && hit) {
+      const int slot = base + found + __popcll(mask & ((1ull << lane) - 1ull));
+      if (slot < a.limit) {
+        a.neighbors[(int64_t)slot * 2] = (int32_t)s;
+        a.neighbors[(int64_t)slot * 2 + 1] = id;
+        if (kBounded && a.sources) a.sources[slot] = id;
+      }
+    }
+    found += __popcll(mask);
+  }
+
+  __device__ __forceinline__ void finish(const BqScanArgs& a) {
+    if (kThreshold) {
+      if (lane == 0) a.cap.tau[s] = kept.tau, a.counts[s] = a.cap.m;
+      return;
+    }
+    if (!kStore && lane == 0) a.counts[s] = found;
+  }
+};
+
+// Grid path: a sample's candidates are its nine key windows, flattened.
+template <BqPass PASS, bool CAPPED = false>
+__global__ __launch_bounds__(256) void scan_candidates_kernel(const BqScanArgs a) {
+  static_assert(PASS != BqPass::kThreshold || CAPPED, "the threshold pass belongs to the capped query");
+  static_assert(PASS != BqPass::kStoreBoundedInlinePrefix, "the inline prefix belongs to the all-pairs path");
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= n_dst) return;
-  const int64_t s = order ? order[w] : w;  // the wavefronts of a workgroup then share their candidate windows
-  uint32_t sample_hash = 0;
-  uint64_t tau = kCapNoKey;
-  CapKept kept;
-  if (CAPPED) {
-    sample_hash = cap_sample_hash(cap.seed, cap.seed_device, s);
-    if (MODE == 4) {
-      const int c = counts[s];
-      if (lane == 0) {
-        if (cap.degrees) cap.degrees[s] = c;
-        if (c <= cap.m) cap.tau[s] = kCapNoKey;
-      }
-      if (c <= cap.m) return;
-      kept.init();
-    } else {
-      tau = cap.tau[s];
-    }
-  }
-  const float sx = pts_dst[s * 3], sy = pts_dst[s * 3 + 1], sz = pts_dst[s * 3 + 2];
+  if (w >= a.n_dst) return;
+  const int64_t s = a.order ? a.order[w] : w;  // the wavefronts of a workgroup then share their candidate windows
+  BqSample<PASS, CAPPED> sample;
+  if (!sample.begin(a, s, lane)) return;
+  const float sx = a.pts_dst[s * 3], sy = a.pts_dst[s * 3 + 1], sz = a.pts_dst[s * 3 + 2];
   int lo[9], pre[10];
   pre[0] = 0;
 #pragma unroll
   for (int o = 0; o < 9; ++o) {
-    const int2 r = ranges[s * 9 + o];
+    const int2 r = a.ranges[s * 9 + o];
     lo[o] = r.x;
     pre[o + 1] = pre[o] + (r.y - r.x);
   }
   const int total = pre[9];
-  int found = 0;
-  int base = 0;
-  if (STORE) base = s > 0 ? ends[s - 1] : 0;
-  if (MODE == 2) {
-    base = min(base, limit);
-    if (lane == 0) {
-      const int e = ends[s];
-      if (s == n_dst - 1) info[0] = e, info[1] = e > limit ? 1 : 0;
-      if (e > limit) ends[s] = limit;
-    }
-  }
   for (int c0 = 0; c0 < total; c0 += 64) {
     const int c = c0 + lane;
     bool hit = false;
@@ -300,134 +350,51 @@ __global__ __launch_bounds__(256) void scan_candidates_kernel(const float* __res
 #pragma unroll
       for (int t = 0; t < 9; ++t)
         if (t == o) pos = lo[t] + (c - pre[t]);
-      const float4 p = spts[pos];
-      hit = within_ball(sx, sy, sz, p, inv_r);
+      const float4 p = a.recs[pos];
+      hit = within_ball(sx, sy, sz, p, a.inv_r);
       id = __float_as_int(p.w);
     }
-    if (CAPPED && MODE == 4) {
-      kept.add(hit ? cap_key(sample_hash, id) : kCapNoKey, lane, cap.m);
-      continue;
-    }
-    if (CAPPED) hit = hit && cap_key(sample_hash, id) <= tau;
-    const unsigned long long mask = __ballot(hit);
-    if (STORE && hit) {
-      const int slot = base + found + __popcll(mask & ((1ull << lane) - 1ull));
-      if (slot < limit) {
-        neighbors[(int64_t)slot * 2] = (int32_t)s;
-        neighbors[(int64_t)slot * 2 + 1] = id;
-        if (MODE == 2 && sources) sources[slot] = id;
-      }
-    }
-    found += __popcll(mask);
+    sample.consume(a, hit, id);
   }
-  if (CAPPED && MODE == 4) {
-    if (lane == 0) cap.tau[s] = kept.tau, counts[s] = cap.m;
-    return;
-  }
-  if (!STORE && lane == 0) counts[s] = found;
+  sample.finish(a);
 }
 
 // Small source sets (n_src <= kBqScanAllMax): one wavefront per sample tests every source, 64 at a time -- no boxes,
 // keys, sort or windows, i.e. 3 launches instead of 16 where the launches are all there is to the cost.  Same
 // predicate, same batch test; hits of a sample come out in ascending source id.
 constexpr int64_t kBqScanAllMax = 2048;
-// MODE 0 (count) also leaves (x, y, z, batch id) records of the sources in the workspace: the store phase of the C ABI
-// is not handed the source arrays again.  MODE 1: store behind the caller's inclusive offsets.  MODE 2 (bounded call):
-// the same with clamping / info / sources as scan_candidates_kernel<2>.  MODE 3 (bounded call, few samples): no scan
-// launch at all -- every wavefront sums the counts in front of its sample itself (n_dst / 64 loads per lane), writes the
-// sample's clamped inclusive offset, stores, and the last sample records total + overflow flag.
-// CAPPED / MODE 4: as in scan_candidates_kernel.
-constexpr int64_t kBqInlinePrefixMax = 4096;
-template <int MODE, bool CAPPED = false>
-__global__ __launch_bounds__(256) void scan_all_kernel(const float* __restrict__ pts_src, const int32_t* __restrict__ batch_src,
-                                                       float4* __restrict__ recs, const float* __restrict__ pts_dst,
-                                                       const int32_t* __restrict__ batch_dst, float inv_r, int n_src,
-                                                       int64_t n_dst, int32_t* __restrict__ counts,
-                                                       int32_t* __restrict__ ends, int32_t* __restrict__ neighbors,
-                                                       int limit, int32_t* __restrict__ sources, int32_t* __restrict__ info,
-                                                       CapArgs cap = CapArgs{}) {
-  static_assert(MODE != 4 || CAPPED, "the threshold pass belongs to the capped query");
-  constexpr bool STORE = MODE != 0 && MODE != 4;
+constexpr int64_t kBqInlinePrefixMax = 4096;  // samples up to which the bounded call forms its offsets in the store pass
+// All-pairs path: a sample's candidates are the sources c0 + lane of its batch element.  The count pass also leaves the
+// (x, y, z, batch id) records of the sources in the workspace: the store call of the C ABI is not handed the source
+// arrays again.
+template <BqPass PASS, bool CAPPED = false>
+__global__ __launch_bounds__(256) void scan_all_kernel(const BqScanArgs a) {
+  static_assert(PASS != BqPass::kThreshold || CAPPED, "the threshold pass belongs to the capped query");
   const int lane = threadIdx.x & 63;
-  if (MODE == 0) {
+  if (PASS == BqPass::kCount) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n_src) recs[t] = make_float4(pts_src[t * 3], pts_src[t * 3 + 1], pts_src[t * 3 + 2], __int_as_float(batch_src[t]));
+    if (t < a.n_src)
+      a.recs[t] = make_float4(a.pts_src[t * 3], a.pts_src[t * 3 + 1], a.pts_src[t * 3 + 2], __int_as_float(a.batch_src[t]));
   }
   const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (s >= n_dst) return;
-  const float sx = pts_dst[s * 3], sy = pts_dst[s * 3 + 1], sz = pts_dst[s * 3 + 2];
-  const int sb = batch_dst[s];
-  uint32_t sample_hash = 0;
-  uint64_t tau = kCapNoKey;
-  CapKept kept;
-  if (CAPPED) {
-    sample_hash = cap_sample_hash(cap.seed, cap.seed_device, s);
-    if (MODE == 4) {
-      const int c = counts[s];
-      if (lane == 0) {
-        if (cap.degrees) cap.degrees[s] = c;
-        if (c <= cap.m) cap.tau[s] = kCapNoKey;
-      }
-      if (c <= cap.m) return;
-      kept.init();
-    } else {
-      tau = cap.tau[s];
-    }
-  }
-  int found = 0;
-  int base = 0;
-  if (MODE == 1 || MODE == 2) base = s > 0 ? ends[s - 1] : 0;
-  if (MODE == 2) {  // offsets from the scan: clamp in place like scan_candidates_kernel<2>
-    base = min(base, limit);
-    if (lane == 0) {
-      const int e = ends[s];
-      if (s == n_dst - 1) info[0] = e, info[1] = e > limit ? 1 : 0;
-      if (e > limit) ends[s] = limit;
-    }
-  }
-  if (MODE == 3) {
-    int acc = 0;
-    for (int64_t j = lane; j < s; j += 64) acc += counts[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    const int e = acc + counts[s];
-    base = min(acc, limit);
-    if (lane == 0) {
-      ends[s] = min(e, limit);
-      if (s == n_dst - 1) info[0] = e, info[1] = e > limit ? 1 : 0;
-    }
-  }
-  for (int c0 = 0; c0 < n_src; c0 += 64) {
+  if (s >= a.n_dst) return;
+  BqSample<PASS, CAPPED> sample;
+  if (!sample.begin(a, s, lane)) return;
+  const float sx = a.pts_dst[s * 3], sy = a.pts_dst[s * 3 + 1], sz = a.pts_dst[s * 3 + 2];
+  const int sb = a.batch_dst[s];
+  for (int c0 = 0; c0 < a.n_src; c0 += 64) {
     const int id = c0 + lane;
     bool hit = false;
-    if (id < n_src) {
-      float4 p;
-      if (STORE || MODE == 4) p = recs[id];
-      else p = make_float4(pts_src[(int64_t)id * 3], pts_src[(int64_t)id * 3 + 1], pts_src[(int64_t)id * 3 + 2],
-                           __int_as_float(batch_src[id]));
-      hit = __float_as_int(p.w) == sb && within_ball(sx, sy, sz, p, inv_r);
+    if (id < a.n_src) {
+      float4 p;  // (the count pass cannot read the records other workgroups are still writing)
+      if (PASS != BqPass::kCount) p = a.recs[id];
+      else p = make_float4(a.pts_src[(int64_t)id * 3], a.pts_src[(int64_t)id * 3 + 1], a.pts_src[(int64_t)id * 3 + 2],
+                           __int_as_float(a.batch_src[id]));
+      hit = __float_as_int(p.w) == sb && within_ball(sx, sy, sz, p, a.inv_r);
     }
-    if (CAPPED && MODE == 4) {
-      kept.add(hit ? cap_key(sample_hash, id) : kCapNoKey, lane, cap.m);
-      continue;
-    }
-    if (CAPPED) hit = hit && cap_key(sample_hash, id) <= tau;
-    const unsigned long long mask = __ballot(hit);
-    if (STORE && hit) {
-      const int slot = base + found + __popcll(mask & ((1ull << lane) - 1ull));
-      if (slot < limit) {
-        neighbors[(int64_t)slot * 2] = (int32_t)s;
-        neighbors[(int64_t)slot * 2 + 1] = id;
-        if (MODE >= 2 && sources) sources[slot] = id;
-      }
-    }
-    found += __popcll(mask);
+    sample.consume(a, hit, id);
   }
-  if (CAPPED && MODE == 4) {
-    if (lane == 0) cap.tau[s] = kept.tau, counts[s] = cap.m;
-    return;
-  }
-  if (!STORE && lane == 0) counts[s] = found;
+  sample.finish(a);
 }
 
 // Per-batch bounding boxes (BallQuery.py:35-36 / BoundingBox.py:17-18 use torch_scatter's scatter_min/max).
@@ -744,7 +711,7 @@ extern "C" int se3_compute_keys(const float* pts, const int32_t* batch_ids, cons
   if (n < 0 || (n > 0 && (!pts || !batch_ids || !aabb_min || !num_cells || !cell_size || !keys)))
     return SE3_ERR_INVALID_ARGUMENT;
   if (n == 0) return SE3_OK;
-  hipLaunchKernelGGL(compute_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pts, batch_ids,
+  hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pts, batch_ids,
                      aabb_min, num_cells, cell_size, 0.f, n, keys, (int32_t*)nullptr);
   return check_launch();
 }
@@ -923,7 +890,7 @@ extern "C" int se3_knn_query_grid(const float* pts, const int32_t* batch_ids, co
   if (int rc = se3::launch_fill_words(list_count, 0u, 1, stream)) return rc;
   {
     ProfScope prof("knn_sort", stream);
-    hipLaunchKernelGGL(compute_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, aabb_min, num_cells,
+    hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, aabb_min, num_cells,
                        cell_size, 0.f, n, keys, ids);
     if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sids, (int)n, 0, 64, stream) !=
         hipSuccess)
@@ -946,162 +913,198 @@ extern "C" int se3_knn_query_grid(const float* pts, const int32_t* batch_ids, co
   return launch_knn_listed(pts, batch_ids, n, (int)k, out, list, list_count, stream);
 }
 
+// ---- ball query, host side: one plan per call --------------------------------------------------------------------------
+// What an entry point was handed (the clouds, grid parameters, sizes and workspace in the order of the C ABI's arguments).
+struct BqCall {
+  const float *pts_src, *pts_dst;
+  const int32_t *batch_src, *batch_dst;
+  const float* aabb_min;
+  const int32_t* num_cells;
+  float radius;
+  int64_t n_src, n_dst;
+  void* workspace;
+  size_t workspace_bytes;
+  hipStream_t stream;
+  // (may be NULL = inside the workspace) the source cloud's part of the layout -- keys, sorted keys / ids / records -- in a
+  // buffer of its own that outlives the call
+  void* grid;
+  int32_t *ends, *neighbors, *sources, *info;
+  int limit;  // rows of `neighbors`
+  CapArgs cap;
+};
+
+// Every decision about a call's shape, taken once per entry-point call and read by the count, threshold and store stages.
+// The two calls of the two-phase ABI (se3_ball_query_count, then se3_ball_query_store) each build it from what they are
+// given: they agree on everything the store pass reads (path and layout).
+struct BqPlan {
+  bool all_pairs;      // n_src <= kBqScanAllMax: every source is tested (scan_all_kernel); else the grid path
+  int key_bits;        // grid path: 0 = the 64-bit keys of the two-phase path; else 32-bit keys with that many bits in use
+  bool inline_prefix;  // bounded all-pairs call with few samples: no scan launch, the store pass forms the offsets itself
+  // Grid path, a cloud against itself (pts_src == pts_dst && n_src == n_dst && batch_src == batch_dst): the samples are
+  // walked in the cell order the sort produced (`sids`), so that neighbouring threads search for neighbouring keys and the
+  // wavefronts of a workgroup read the same candidate windows.  Results are stored at the sample's own index: nothing
+  // changes but the order of the work (the store call of the two-phase ABI, which is not told the sources, does without).
+  bool ordered;
+  // Grid path: the key, sort and gather launches run.  Not when `grid` already holds this source cloud's grid for this
+  // radius (built by an earlier call with the same pts_src / batch_src / aabb_min / num_cells / radius / key width).
+  bool build_grid;
+  // Capped call.  threshold: the threshold pass runs (degrees, and with a cap the thresholds) -- BETWEEN the count pass and
+  // the scan, so that every offset formed afterwards, by the scan or by the inline prefix of the store pass, is a capped
+  // one.  capped: the store pass keeps the hits at or below the thresholds.
+  bool threshold, capped;
+  BqLayout l;
+  size_t tau_offset;  // capped call: one 64-bit threshold per sample behind the workspace of the bounded query
+};
+
+static size_t bq_tau_offset(const BqLayout& l) { return align_up(l.total, 256); }
+static size_t bq_capped_bytes(const BqLayout& l, int64_t n_dst) { return bq_tau_offset(l) + (size_t)(n_dst > 0 ? n_dst : 1) * 8; }
+
+static BqPlan bq_plan(const BqCall& c, int32_t n_batches, bool bounded, bool grid_valid, bool threshold = false,
+                      bool capped = false) {
+  BqPlan p{};
+  p.all_pairs = c.n_src <= kBqScanAllMax;
+  // one or two batch elements (only the bounded calls are told the count): 30 + 1 key bits (Key32; the window's upper
+  // bound base + 3 then cannot wrap)
+  if (!p.all_pairs && n_batches >= 1 && n_batches <= 2) p.key_bits = 30 + (n_batches > 1 ? 1 : 0);
+  // (count + prefix + store as one launch with a decoupled look-back was measured in round 4: slower, removed --
+  // profiles/r04_ball_query_onepass_ab.txt)
+  p.inline_prefix = bounded && p.all_pairs && c.n_dst <= kBqInlinePrefixMax;
+  p.ordered = !p.all_pairs && c.pts_src && c.pts_src == c.pts_dst && c.n_src == c.n_dst && c.batch_src == c.batch_dst;
+  p.build_grid = !p.all_pairs && !grid_valid;
+  p.threshold = threshold, p.capped = capped;
+  p.l = bq_layout(c.n_src, c.n_dst);
+  p.tau_offset = bq_tau_offset(p.l);
+  return p;
+}
+
+static BqScanArgs bq_scan_args(const BqCall& c, const BqPlan& p) {
+  char* ws = (char*)c.workspace;
+  char* gws = c.grid ? (char*)c.grid : ws;
+  BqScanArgs a{};
+  a.pts_dst = c.pts_dst, a.batch_dst = c.batch_dst, a.inv_r = 1.0f / c.radius, a.n_dst = c.n_dst;
+  a.counts = (int32_t*)(ws + p.l.counts);
+  a.ends = c.ends, a.neighbors = c.neighbors, a.limit = c.limit, a.sources = c.sources, a.info = c.info;
+  a.cap = c.cap;
+  a.recs = (float4*)(gws + p.l.spts);
+  a.ranges = (const int2*)(ws + p.l.ranges);
+  a.order = p.ordered ? (const int32_t*)(gws + p.l.sids) : nullptr;
+  a.pts_src = c.pts_src, a.batch_src = c.batch_src, a.n_src = (int)c.n_src;
+  return a;
+}
+
+// One launch helper per kernel: the instantiation of a pass.  The combinations that exist are the ones a call can ask for:
+// the count pass is never capped (a capped call counts all hits first) and neither is the two-phase store.
+using BqScanKernel = void (*)(BqScanArgs);
+static int launch_scan(BqScanKernel kernel, int64_t blocks, const BqScanArgs& a, hipStream_t stream) {
+  if (!kernel) return SE3_ERR_INVALID_ARGUMENT;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return SE3_OK;
+}
+static int launch_scan_candidates(BqPass pass, bool capped, const BqScanArgs& a, hipStream_t stream) {
+  BqScanKernel k = nullptr;
+  if (pass == BqPass::kCount && !capped) k = scan_candidates_kernel<BqPass::kCount>;
+  if (pass == BqPass::kStore && !capped) k = scan_candidates_kernel<BqPass::kStore>;
+  if (pass == BqPass::kStoreBounded) k = capped ? scan_candidates_kernel<BqPass::kStoreBounded, true> : scan_candidates_kernel<BqPass::kStoreBounded>;
+  if (pass == BqPass::kThreshold && capped) k = scan_candidates_kernel<BqPass::kThreshold, true>;
+  return launch_scan(k, (a.n_dst + 3) / 4, a, stream);
+}
+static int launch_scan_all(BqPass pass, bool capped, const BqScanArgs& a, hipStream_t stream) {
+  BqScanKernel k = nullptr;
+  if (pass == BqPass::kCount && !capped) k = scan_all_kernel<BqPass::kCount>;
+  if (pass == BqPass::kStore && !capped) k = scan_all_kernel<BqPass::kStore>;
+  if (pass == BqPass::kStoreBounded) k = capped ? scan_all_kernel<BqPass::kStoreBounded, true> : scan_all_kernel<BqPass::kStoreBounded>;
+  if (pass == BqPass::kStoreBoundedInlinePrefix)
+    k = capped ? scan_all_kernel<BqPass::kStoreBoundedInlinePrefix, true> : scan_all_kernel<BqPass::kStoreBoundedInlinePrefix>;
+  if (pass == BqPass::kThreshold && capped) k = scan_all_kernel<BqPass::kThreshold, true>;
+  // (the count pass also copies the sources, one per thread)
+  const int64_t blocks = pass == BqPass::kCount ? std::max((a.n_dst + 3) / 4, ((int64_t)a.n_src + 255) / 256) : (a.n_dst + 3) / 4;
+  return launch_scan(k, blocks, a, stream);
+}
+static int launch_scan_pass(const BqPlan& p, BqPass pass, bool capped, const BqScanArgs& a, hipStream_t stream) {
+  return p.all_pairs ? launch_scan_all(pass, capped, a, stream) : launch_scan_candidates(pass, capped, a, stream);
+}
+
+// Grid path, in front of the count pass: the source cloud's grid (unless it is reused) and the nine windows of every sample.
+template <class KEY>
+static int bq_grid_windows(const BqCall& c, const BqPlan& p, int key_bits) {
+  using K = typename KEY::type;
+  char* ws = (char*)c.workspace;
+  char* gws = c.grid ? (char*)c.grid : ws;
+  K* skeys = (K*)(gws + p.l.skeys);
+  int32_t* sids = (int32_t*)(gws + p.l.sids);
+  if (p.build_grid) {
+    K* keys = (K*)(gws + p.l.keys);
+    int32_t* ids = (int32_t*)(gws + p.l.ids);
+    // cell size = radius in every dimension (BallQuery.py:39-40)
+    hipLaunchKernelGGL(compute_keys_kernel<KEY>, dim3(blocks_for(c.n_src)), dim3(256), 0, c.stream, c.pts_src, c.batch_src,
+                       c.aabb_min, c.num_cells, (const float*)nullptr, c.radius, c.n_src, keys, ids);
+    size_t temp_bytes = p.l.temp_bytes;
+    if (sort_pairs_no_scratch(ws + p.l.temp, temp_bytes, keys, skeys, ids, sids, (int)c.n_src, 0, key_bits, c.stream) != hipSuccess)
+      return SE3_ERR_LAUNCH;
+    hipLaunchKernelGGL(gather_sorted_points_kernel, dim3(blocks_for(c.n_src)), dim3(256), 0, c.stream, c.pts_src, sids,
+                       c.n_src, (float4*)(gws + p.l.spts));
+  }
+  hipLaunchKernelGGL(find_ranges_kernel<KEY>, dim3(blocks_for(c.n_dst * 9)), dim3(256), 0, c.stream, c.pts_dst, c.batch_dst,
+                     c.aabb_min, c.num_cells, c.radius, skeys, (int)c.n_src, c.n_dst, (int2*)(ws + p.l.ranges),
+                     p.ordered ? sids : (const int32_t*)nullptr);
+  return SE3_OK;
+}
+
+// Count stage: [grid, windows,] count pass, [threshold pass,] scan of the counts into `ends` (unless the store pass forms
+// the offsets itself).
+static int bq_count_stage(const BqCall& c, const BqPlan& p) {
+  if (c.n_src < 0 || c.n_dst < 0 || !(c.radius > 0.f)) return SE3_ERR_INVALID_ARGUMENT;
+  if (c.n_src >= (1ll << 31) || c.n_dst >= (1ll << 31) / 9) return SE3_ERR_UNSUPPORTED;
+  if (c.n_dst == 0) return SE3_OK;
+  if (!c.pts_dst || !c.batch_dst || !c.workspace || !c.ends || (c.n_src > 0 && (!c.pts_src || !c.batch_src)) ||
+      (!p.all_pairs && (!c.aabb_min || !c.num_cells)))
+    return SE3_ERR_INVALID_ARGUMENT;
+  if (c.workspace_bytes < p.l.total) return SE3_ERR_WORKSPACE;
+  if (!p.all_pairs)
+    if (int rc = p.key_bits ? bq_grid_windows<Key32>(c, p, p.key_bits) : bq_grid_windows<Key64>(c, p, 64)) return rc;
+  const BqScanArgs a = bq_scan_args(c, p);
+  if (int rc = launch_scan_pass(p, BqPass::kCount, false, a, c.stream)) return rc;
+  if (p.threshold)
+    if (int rc = launch_scan_pass(p, BqPass::kThreshold, true, a, c.stream)) return rc;
+  if (p.inline_prefix) return check_launch();
+  size_t temp_bytes = p.l.temp_bytes;
+  if (hipcub::DeviceScan::InclusiveSum((char*)c.workspace + p.l.temp, temp_bytes, a.counts, c.ends, (int)c.n_dst, c.stream) != hipSuccess)
+    return SE3_ERR_LAUNCH;
+  return check_launch();
+}
+
+// Store stage: one launch.  The bounded passes also clamp the offsets to the buffer and record total + overflow flag.
+static int bq_store_stage(const BqCall& c, const BqPlan& p, BqPass pass) {
+  if (c.workspace_bytes < p.l.total) return SE3_ERR_WORKSPACE;
+  if (p.all_pairs && !c.batch_dst) return SE3_ERR_INVALID_ARGUMENT;  // (the count stage left the source records)
+  if (int rc = launch_scan_pass(p, pass, p.capped, bq_scan_args(c, p), c.stream)) return rc;
+  return check_launch();
+}
+
+// The bounded calls: count stage, then the bounded store pass.
+static int bq_bounded(BqCall& c, const BqPlan& p, int64_t capacity) {
+  if (capacity < 0 || capacity >= (1ll << 31) || !c.info) return SE3_ERR_INVALID_ARGUMENT;
+  // no sample, no wavefront: `info`, which the store pass's last sample writes, is filled here
+  if (c.n_dst == 0) return se3::launch_fill_words(c.info, 0u, 2, c.stream);
+  if (capacity > 0 && !c.neighbors) return SE3_ERR_INVALID_ARGUMENT;
+  c.limit = (int)capacity;
+  if (int rc = bq_count_stage(c, p)) return rc;
+  return bq_store_stage(c, p, p.inline_prefix ? BqPass::kStoreBoundedInlinePrefix : BqPass::kStoreBounded);
+}
+
 extern "C" int se3_ball_query_needs_grid(int64_t n_src) { return n_src > kBqScanAllMax ? 1 : 0; }
 
 extern "C" size_t se3_ball_query_workspace_bytes(int64_t n_src, int64_t n_dst) {
   return bq_layout(n_src, n_dst).total;
 }
 
-// skip_scan: the all-pairs path of the bounded call with few samples leaves the per-sample counts in the workspace and
-// lets the store kernel form the offsets itself (scan_all_kernel<3>)
-// grid (may be NULL = inside the workspace): the source cloud's part of the layout -- keys, sorted keys / ids / records --
-// in a buffer of its own that outlives the call; grid_valid: it already holds this source cloud's grid for this radius
-// (built by an earlier call with the same pts_src / batch_src / aabb_min / num_cells / radius / key width), so the key,
-// sort and gather launches are skipped.
-// cap (capped call, may be NULL): the threshold pass runs between the count pass and the scan, so that every offset formed
-// afterwards -- by the scan or by the inline prefix of the store pass -- is a capped one.
-static int ball_query_count_impl(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
-                                 const int32_t* batch_dst, const float* aabb_min, const int32_t* num_cells,
-                                 float radius, int64_t n_src, int64_t n_dst, void* workspace,
-                                 size_t workspace_bytes, int32_t* ends, bool skip_scan, int key_bits, void* stream_,
-                                 void* grid = nullptr, bool grid_valid = false, const CapArgs* cap = nullptr) {
-  if (n_src < 0 || n_dst < 0 || !(radius > 0.f)) return SE3_ERR_INVALID_ARGUMENT;
-  if (n_src >= (1ll << 31) || n_dst >= (1ll << 31) / 9) return SE3_ERR_UNSUPPORTED;
-  if (n_dst == 0) return SE3_OK;
-  const bool scan_all = n_src <= kBqScanAllMax;
-  if (!pts_dst || !batch_dst || !workspace || !ends || (n_src > 0 && (!pts_src || !batch_src)) ||
-      (!scan_all && (!aabb_min || !num_cells)))
-    return SE3_ERR_INVALID_ARGUMENT;
-  const BqLayout l = bq_layout(n_src, n_dst);
-  if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  char* ws = (char*)workspace;
-  char* gws = grid ? (char*)grid : ws;
-  if (scan_all) {
-    int32_t* counts = (int32_t*)(ws + l.counts);
-    size_t temp_bytes = l.temp_bytes;
-    const int64_t blocks = std::max((n_dst + 3) / 4, (n_src + 255) / 256);
-    hipLaunchKernelGGL(scan_all_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, stream, pts_src, batch_src,
-                       (float4*)(gws + l.spts), pts_dst, batch_dst, 1.0f / radius, (int)n_src, n_dst, counts,
-                       (int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr, (int32_t*)nullptr);
-    if (cap)
-      hipLaunchKernelGGL((scan_all_kernel<4, true>), dim3((unsigned)((n_dst + 3) / 4)), dim3(256), 0, stream,
-                         (const float*)nullptr, (const int32_t*)nullptr, (float4*)(gws + l.spts), pts_dst, batch_dst,
-                         1.0f / radius, (int)n_src, n_dst, counts, (int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr,
-                         (int32_t*)nullptr, *cap);
-    if (skip_scan) return check_launch();
-    if (hipcub::DeviceScan::InclusiveSum(ws + l.temp, temp_bytes, counts, ends, (int)n_dst, stream) != hipSuccess)
-      return SE3_ERR_LAUNCH;
-    return check_launch();
-  }
-  int64_t* keys = (int64_t*)(gws + l.keys);
-  int64_t* skeys = (int64_t*)(gws + l.skeys);
-  int32_t* ids = (int32_t*)(gws + l.ids);
-  int32_t* sids = (int32_t*)(gws + l.sids);
-  float4* spts = (float4*)(gws + l.spts);
-  int2* ranges = (int2*)(ws + l.ranges);
-  int32_t* counts = (int32_t*)(ws + l.counts);
-  size_t temp_bytes = l.temp_bytes;
-  const bool build = n_src > 0 && !grid_valid;
-  // A cloud against itself: the samples are walked in the cell order the sort just produced (`sids`), so that
-  // neighbouring threads search for neighbouring keys and the wavefronts of a workgroup read the same candidate
-  // windows.  Results are stored at the sample's own index: nothing changes but the order of the work.
-  const int32_t* order = (pts_src == pts_dst && n_src == n_dst && batch_src == batch_dst) ? sids : nullptr;
-
-  // key_bits > 0 (the bounded call, which knows the batch count): 32-bit keys with a fixed cell stride, see key32_of
-  if (key_bits > 0) {
-    uint32_t* keys32 = (uint32_t*)keys;
-    uint32_t* skeys32 = (uint32_t*)skeys;
-    if (build) {
-      hipLaunchKernelGGL(compute_keys32_kernel, dim3(blocks_for(n_src)), dim3(256), 0, stream, pts_src, batch_src,
-                         aabb_min, num_cells, radius, n_src, keys32, ids);
-      if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys32, skeys32, ids, sids, (int)n_src, 0, key_bits,
-                                             stream) != hipSuccess)
-        return SE3_ERR_LAUNCH;
-      hipLaunchKernelGGL(gather_sorted_points_kernel, dim3(blocks_for(n_src)), dim3(256), 0, stream, pts_src, sids,
-                         n_src, spts);
-    }
-    hipLaunchKernelGGL(find_ranges32_kernel, dim3(blocks_for(n_dst * 9)), dim3(256), 0, stream, pts_dst, batch_dst,
-                       aabb_min, num_cells, radius, skeys32, (int)n_src, n_dst, ranges, order);
-  } else {
-    if (build) {
-      // cell size = radius in every dimension (BallQuery.py:39-40)
-      hipLaunchKernelGGL(compute_keys_kernel, dim3(blocks_for(n_src)), dim3(256), 0, stream, pts_src, batch_src, aabb_min,
-                         num_cells, (const float*)nullptr, radius, n_src, keys, ids);
-      if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sids, (int)n_src, 0, 64,
-                                             stream) != hipSuccess)
-        return SE3_ERR_LAUNCH;
-      hipLaunchKernelGGL(gather_sorted_points_kernel, dim3(blocks_for(n_src)), dim3(256), 0, stream, pts_src, sids, n_src,
-                         spts);
-    }
-    hipLaunchKernelGGL(find_ranges_kernel, dim3(blocks_for(n_dst * 9)), dim3(256), 0, stream, pts_dst, batch_dst,
-                       aabb_min, num_cells, radius, skeys, (int)n_src, n_dst, ranges, order);
-  }
-  hipLaunchKernelGGL(scan_candidates_kernel<0>, dim3((unsigned)((n_dst + 3) / 4)), dim3(256), 0, stream, pts_dst,
-                     1.0f / radius, spts, ranges, n_dst, counts, (int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr,
-                     (int32_t*)nullptr, order);
-  if (cap)
-    hipLaunchKernelGGL((scan_candidates_kernel<4, true>), dim3((unsigned)((n_dst + 3) / 4)), dim3(256), 0, stream, pts_dst,
-                       1.0f / radius, spts, ranges, n_dst, counts, (int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr,
-                       (int32_t*)nullptr, order, *cap);
-  temp_bytes = l.temp_bytes;
-  if (hipcub::DeviceScan::InclusiveSum(ws + l.temp, temp_bytes, counts, ends, (int)n_dst, stream) != hipSuccess)
-    return SE3_ERR_LAUNCH;
-  return check_launch();
-}
-
 extern "C" int se3_ball_query_count(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
                                     const int32_t* batch_dst, const float* aabb_min, const int32_t* num_cells,
                                     float radius, int64_t n_src, int64_t n_dst, void* workspace,
                                     size_t workspace_bytes, int32_t* ends, void* stream) {
-  return ball_query_count_impl(pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst,
-                               workspace, workspace_bytes, ends, false, 0, stream);
-}
-
-// mode 1: two-phase store; 2: bounded (clamp, info, sources); 3: bounded all-pairs with the offsets formed in the kernel
-static int ball_query_store_impl(const float* pts_dst, const int32_t* batch_dst, float radius, int64_t n_src,
-                                 int64_t n_dst, const void* workspace, size_t workspace_bytes, int32_t* ends,
-                                 int32_t* neighbors, int limit, int mode, int32_t* sources, int32_t* info, bool ordered,
-                                 void* stream, const void* grid = nullptr, const CapArgs* cap = nullptr) {
-  const BqLayout l = bq_layout(n_src, n_dst);
-  if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
-  const char* ws = (const char*)workspace;
-  const char* gws = grid ? (const char*)grid : ws;
-  const dim3 wgrid((unsigned)((n_dst + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (n_src <= kBqScanAllMax) {  // the count phase took the all-pairs path (and left the source records)
-    if (!batch_dst) return SE3_ERR_INVALID_ARGUMENT;
-    float4* recs = (float4*)(gws + l.spts);
-    int32_t* counts = (int32_t*)(ws + l.counts);
-#define SE3_SCAN_ALL(M)                                                                                                 \
-  hipLaunchKernelGGL(scan_all_kernel<M>, wgrid, block, 0, st, (const float*)nullptr, (const int32_t*)nullptr, recs, pts_dst, \
-                     batch_dst, 1.0f / radius, (int)n_src, n_dst, counts, ends, neighbors, limit, sources, info)
-    if (cap) {  // (the capped call is a bounded one: modes 2 and 3)
-      if (mode == 2)
-        hipLaunchKernelGGL((scan_all_kernel<2, true>), wgrid, block, 0, st, (const float*)nullptr, (const int32_t*)nullptr, recs,
-                           pts_dst, batch_dst, 1.0f / radius, (int)n_src, n_dst, counts, ends, neighbors, limit, sources, info, *cap);
-      else
-        hipLaunchKernelGGL((scan_all_kernel<3, true>), wgrid, block, 0, st, (const float*)nullptr, (const int32_t*)nullptr, recs,
-                           pts_dst, batch_dst, 1.0f / radius, (int)n_src, n_dst, counts, ends, neighbors, limit, sources, info, *cap);
-    } else if (mode == 1) SE3_SCAN_ALL(1);
-    else if (mode == 2) SE3_SCAN_ALL(2);
-    else SE3_SCAN_ALL(3);
-#undef SE3_SCAN_ALL
-    return check_launch();
-  }
-  if (cap)
-    hipLaunchKernelGGL((scan_candidates_kernel<2, true>), wgrid, block, 0, st, pts_dst, 1.0f / radius,
-                       (const float4*)(gws + l.spts), (const int2*)(ws + l.ranges), n_dst, (int32_t*)nullptr, ends, neighbors,
-                       limit, sources, info, ordered ? (const int32_t*)(gws + l.sids) : (const int32_t*)nullptr, *cap);
-  else if (mode == 1)
-    hipLaunchKernelGGL(scan_candidates_kernel<1>, wgrid, block, 0, st, pts_dst, 1.0f / radius, (const float4*)(gws + l.spts),
-                       (const int2*)(ws + l.ranges), n_dst, (int32_t*)nullptr, ends, neighbors, limit, sources, info,
-                       ordered ? (const int32_t*)(gws + l.sids) : (const int32_t*)nullptr);
-  else
-    hipLaunchKernelGGL(scan_candidates_kernel<2>, wgrid, block, 0, st, pts_dst, 1.0f / radius, (const float4*)(gws + l.spts),
-                       (const int2*)(ws + l.ranges), n_dst, (int32_t*)nullptr, ends, neighbors, limit, sources, info,
-                       ordered ? (const int32_t*)(gws + l.sids) : (const int32_t*)nullptr);
-  return check_launch();
+  BqCall c{pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, workspace, workspace_bytes,
+           (hipStream_t)stream, nullptr, ends};
+  return bq_count_stage(c, bq_plan(c, 0, false, false));
 }
 
 extern "C" int se3_ball_query_store(const float* pts_dst, const int32_t* batch_dst, float radius, int64_t n_src,
@@ -1110,35 +1113,10 @@ extern "C" int se3_ball_query_store(const float* pts_dst, const int32_t* batch_d
   if (n_src < 0 || n_dst < 0 || n_edges < 0 || !(radius > 0.f)) return SE3_ERR_INVALID_ARGUMENT;
   if (n_dst == 0 || n_edges == 0) return SE3_OK;
   if (!pts_dst || !workspace || !ends || !neighbors) return SE3_ERR_INVALID_ARGUMENT;
-  return ball_query_store_impl(pts_dst, batch_dst, radius, n_src, n_dst, workspace, workspace_bytes,
-                               const_cast<int32_t*>(ends), neighbors, 0x7fffffff, 1, nullptr, nullptr, false, stream);
-}
-
-static int ball_query_bounded_impl(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
-                                   const int32_t* batch_dst, const float* aabb_min, const int32_t* num_cells,
-                                   float radius, int64_t n_src, int64_t n_dst, int32_t n_batches, void* workspace,
-                                   size_t workspace_bytes, int64_t capacity, int32_t* neighbors, int32_t* sources,
-                                   int32_t* ends, int32_t* info, void* stream, void* grid, bool grid_valid,
-                                   const CapArgs* threshold = nullptr, const CapArgs* cap = nullptr) {
-  // threshold: run the capped query's threshold pass (degrees, and with a cap the thresholds); cap: store under them
-  if (capacity < 0 || capacity >= (1ll << 31) || !info) return SE3_ERR_INVALID_ARGUMENT;
-  if (n_dst == 0) return se3::launch_fill_words(info, 0u, 2, (hipStream_t)stream);
-  if (capacity > 0 && !neighbors) return SE3_ERR_INVALID_ARGUMENT;
-  const bool inline_prefix = n_src <= kBqScanAllMax && n_dst <= kBqInlinePrefixMax;
-  // one or two batch elements: 30 + 1 key bits (key32_of; the window's upper bound base + 3 then cannot wrap);
-  // more: the 64-bit keys of the two-phase path
-  int key_bits = 0;
-  if (n_batches >= 1 && n_batches <= 2) key_bits = 30 + (n_batches > 1 ? 1 : 0);
-  // (count + prefix + store as one launch with a decoupled look-back was measured in round 4: slower, removed --
-  // profiles/r04_ball_query_onepass_ab.txt)
-  if (int rc = ball_query_count_impl(pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst,
-                                     workspace, workspace_bytes, ends, inline_prefix, key_bits, stream, grid, grid_valid,
-                                     threshold))
-    return rc;
-  // one store launch also clamps the offsets to the buffer and records total + overflow flag
-  return ball_query_store_impl(pts_dst, batch_dst, radius, n_src, n_dst, workspace, workspace_bytes, ends, neighbors,
-                               (int)capacity, inline_prefix ? 3 : 2, sources, info,
-                               pts_src == pts_dst && n_src == n_dst && batch_src == batch_dst, stream, grid, cap);
+  BqCall c{nullptr, pts_dst, nullptr, batch_dst, nullptr, nullptr, radius, n_src, n_dst, const_cast<void*>(workspace),
+           workspace_bytes, (hipStream_t)stream, nullptr, const_cast<int32_t*>(ends), neighbors};
+  c.limit = 0x7fffffff;
+  return bq_store_stage(c, bq_plan(c, 0, false, false), BqPass::kStore);
 }
 
 extern "C" int se3_ball_query_bounded(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
@@ -1146,8 +1124,9 @@ extern "C" int se3_ball_query_bounded(const float* pts_src, const float* pts_dst
                                       float radius, int64_t n_src, int64_t n_dst, int32_t n_batches, void* workspace,
                                       size_t workspace_bytes, int64_t capacity, int32_t* neighbors, int32_t* sources,
                                       int32_t* ends, int32_t* info, void* stream) {
-  return ball_query_bounded_impl(pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, n_batches,
-                                 workspace, workspace_bytes, capacity, neighbors, sources, ends, info, stream, nullptr, false);
+  BqCall c{pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, workspace, workspace_bytes,
+           (hipStream_t)stream, nullptr, ends, neighbors, sources, info};
+  return bq_bounded(c, bq_plan(c, n_batches, true, false), capacity);
 }
 
 extern "C" size_t se3_ball_query_grid_bytes(int64_t n_src) { return bq_layout(n_src, 0).ranges; }
@@ -1158,18 +1137,16 @@ extern "C" int se3_ball_query_bounded_shared(const float* pts_src, const float* 
                                              size_t grid_bytes, int32_t grid_valid, void* workspace, size_t workspace_bytes,
                                              int64_t capacity, int32_t* neighbors, int32_t* sources, int32_t* ends,
                                              int32_t* info, void* stream) {
-  if (!grid || grid_bytes < bq_layout(n_src, 0).ranges) return SE3_ERR_WORKSPACE;
-  return ball_query_bounded_impl(pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, n_batches,
-                                 workspace, workspace_bytes, capacity, neighbors, sources, ends, info, stream, grid,
-                                 grid_valid != 0);
+  BqCall c{pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, workspace, workspace_bytes,
+           (hipStream_t)stream, grid, ends, neighbors, sources, info};
+  const BqPlan p = bq_plan(c, n_batches, true, grid_valid != 0);
+  if (!grid || grid_bytes < p.l.ranges) return SE3_ERR_WORKSPACE;  // (the source cloud's part of the layout ends at `ranges`)
+  return bq_bounded(c, p, capacity);
 }
 
 // ---- capped query (include/se3conv_capped.h) ----------------------------------------------------------------------------
-// the workspace of the bounded query, then one 64-bit threshold per sample
-static size_t capped_tau_offset(int64_t n_src, int64_t n_dst) { return align_up(bq_layout(n_src, n_dst).total, 256); }
-
 extern "C" size_t se3_ball_query_capped_workspace_bytes(int64_t n_src, int64_t n_dst) {
-  return capped_tau_offset(n_src, n_dst) + (size_t)(n_dst > 0 ? n_dst : 1) * 8;
+  return bq_capped_bytes(bq_layout(n_src, n_dst), n_dst);
 }
 
 extern "C" int se3_ball_query_capped(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
@@ -1180,14 +1157,15 @@ extern "C" int se3_ball_query_capped(const float* pts_src, const float* pts_dst,
                                      int32_t max_neighbors, uint32_t seed, const uint32_t* seed_device, int32_t* degrees) {
   if (n_src < 0 || n_dst < 0) return SE3_ERR_INVALID_ARGUMENT;
   if (max_neighbors > kCapMax) return SE3_ERR_UNSUPPORTED;
-  if (grid && grid_bytes < bq_layout(n_src, 0).ranges) return SE3_ERR_WORKSPACE;
-  if (workspace && workspace_bytes < se3_ball_query_capped_workspace_bytes(n_src, n_dst)) return SE3_ERR_WORKSPACE;
   const bool capped = max_neighbors > 0;
-  CapArgs cap{capped ? max_neighbors : 0x7fffffff, seed, seed_device,
-              workspace ? (uint64_t*)((char*)workspace + capped_tau_offset(n_src, n_dst)) : nullptr, degrees};
-  return ball_query_bounded_impl(pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, n_batches,
-                                 workspace, workspace_bytes, capacity, neighbors, sources, ends, info, stream, grid,
-                                 grid && grid_valid != 0, capped || degrees ? &cap : nullptr, capped ? &cap : nullptr);
+  BqCall c{pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_src, n_dst, workspace, workspace_bytes,
+           (hipStream_t)stream, grid, ends, neighbors, sources, info};
+  const BqPlan p = bq_plan(c, n_batches, true, grid && grid_valid != 0, capped || degrees, capped);
+  if (grid && grid_bytes < p.l.ranges) return SE3_ERR_WORKSPACE;
+  if (workspace && workspace_bytes < bq_capped_bytes(p.l, n_dst)) return SE3_ERR_WORKSPACE;
+  c.cap = CapArgs{capped ? max_neighbors : 0x7fffffff, seed, seed_device,
+                  workspace ? (uint64_t*)((char*)workspace + p.tau_offset) : nullptr, degrees};
+  return bq_bounded(c, p, capacity);
 }
 
 // ---- source-major copy of an edge list (se3_csr_transpose*) -----------------------------------------------------------
@@ -1595,7 +1573,7 @@ extern "C" int se3_grid_subsample(const float* pts, const int32_t* batch_ids, in
   if (int rc = batch_aabb_impl(pts, batch_ids, n, n_batches, box_min, box_max, num_cells, stream)) return rc;
   hipLaunchKernelGGL(grid_params_kernel, dim3((n_batches * 3 + 255) / 256), dim3(256), 0, stream, box_min, box_max,
                      n_batches, cell_size, 1e-6f, num_cells);
-  hipLaunchKernelGGL(compute_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, box_min, num_cells,
+  hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, box_min, num_cells,
                      (const float*)nullptr, cell_size, n, keys, ids);
   size_t temp_bytes = l.temp_bytes;
   if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sorted_ids, (int)n, 0, 64, stream) !=

@@ -202,9 +202,9 @@ def ball_query(pts_src, pts_dst, batch_src, batch_dst, radius: float,
         return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(n_dst, dtype=torch.int32, device=dev)
     ends = _empty(n_dst, dtype=torch.int32, device=dev)  # every entry is written by the count phase
     # small source sets are searched all-pairs by the library: no boxes / cell grid to prepare
-    mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if lib.se3_ball_query_needs_grid(n_src) else (None, None)
-    nbytes = lib.se3_ball_query_workspace_bytes(n_src, n_dst)
-    ws = _workspace(nbytes, dev)
+    needs_grid, ws_bytes, _ = _ball_query_sizes(n_src, n_dst)
+    mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if needs_grid else (None, None)
+    ws = _workspace(ws_bytes, dev)
     f32, i32 = torch.float32, torch.int32
     _lib.check(lib.se3_ball_query_count(
         _ptr(pts_src, f32, "pts_src"), _ptr(pts_dst, f32, "pts_dst", dev), _ptr(bs, i32, "batch_src", dev),
@@ -286,6 +286,68 @@ def forget_source_grids(cloud) -> None:
         holder.params.clear()
 
 
+def _bounded_query(who, entries, pts_src, pts_dst, batch_src, batch_dst, radius, capacity, n_batches, neighbors_out, out_error,
+                   src_box, grids, rows_per_sample=0, want_sources=False, want_degrees=False, workspace_bytes=None, tail=None):
+    """What ``ball_query_bounded`` and ``ball_query_capped`` share: conversions and validation, the result buffers, the
+    workspace, the source cloud's shared grid (slot, parameters, commit) and the library call itself.  ``entries``: the C
+    entry point without and with the grid arguments (the first None: the second is called either way, with a NULL grid).
+    ``capacity=None``: ``n_dst * rows_per_sample`` rows.  ``workspace_bytes(n_src, n_dst)``: where the call needs more
+    than the bounded query.  ``tail(dev, degrees)``: checks and C arguments behind the stream.  Returns ``(neighbors, ends,
+    info, sources, degrees)``."""
+    lib = _lib.load()
+    src_own, batch_own = pts_src, batch_src  # (what a source grid is keyed on: the caller's tensors, not their conversions)
+    pts_src = _as(pts_src, torch.float32)
+    pts_dst = _as(pts_dst, torch.float32)
+    if pts_src.dim() != 2 or pts_src.shape[1] != 3 or pts_dst.dim() != 2 or pts_dst.shape[1] != 3:
+        raise ValueError("ball_query: only [N,3] point sets are supported")
+    if not (radius > 0) or (capacity is not None and capacity < 0):
+        raise ValueError(f"{who}: radius must be positive and capacity non-negative")
+    dev = pts_src.device
+    f32, i32 = torch.float32, torch.int32
+    bs, bd = _as(batch_src, i32), _as(batch_dst, i32)
+    n_src, n_dst = pts_src.shape[0], pts_dst.shape[0]
+    rows = n_dst * rows_per_sample if capacity is None else int(capacity)
+    if neighbors_out is not None:
+        if capacity is None or neighbors_out.shape != (rows, 2) or neighbors_out.dtype != i32 or not neighbors_out.is_contiguous():
+            raise ValueError(out_error)
+        neighbors = neighbors_out
+    else:
+        neighbors = _empty((rows, 2), dtype=i32, device=dev)
+    sources = _empty(rows, dtype=i32, device=dev) if want_sources else None
+    ends = _empty(n_dst, dtype=i32, device=dev)
+    degrees = _empty(n_dst, dtype=i32, device=dev) if want_degrees else None
+    extra = tail(dev, degrees) if tail is not None else ()
+    if n_dst == 0:
+        return neighbors, ends, torch.zeros(2, dtype=i32, device=dev), sources, degrees
+    info = _empty(2, dtype=i32, device=dev)  # both words are written by the store pass
+    needs_grid, ws_bytes, grid_bytes = _ball_query_sizes(n_src, n_dst)
+    ws = _workspace(workspace_bytes(n_src, n_dst) if workspace_bytes is not None else ws_bytes, dev)
+    grid, valid, key = None, False, None
+    if grids is not None and needs_grid and src_box is not None and SHARED_GRIDS and not torch.cuda.is_current_stream_capturing():
+        # (src_box: the grid parameters are then a pure function of the cloud's cached boxes and the radius, so two calls
+        # with the same key search the same cells -- and the parameters themselves are kept with the grid)
+        key = SourceGrids.key(src_own, batch_own, n_batches)
+        grid, valid = grids.slot(key, radius, grid_bytes, dev)
+        params = grids.params.get(float(radius)) if valid else None
+        if params is None:
+            valid, params = False, _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box)
+        mn, nc = params
+    else:
+        mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if needs_grid else (None, None)
+    with_grid = grid is not None or entries[0] is None
+    entry = entries[1] if with_grid else entries[0]
+    grid_args = (C.c_void_p(grid.data_ptr() if grid is not None else 0), grid.numel() if grid is not None else 0,
+                 int(valid)) if with_grid else ()
+    _lib.check(getattr(lib, entry)(
+        _ptr(pts_src, f32, "pts_src"), _ptr(pts_dst, f32, "pts_dst", dev), _ptr(bs, i32, "batch_src", dev),
+        _ptr(bd, i32, "batch_dst", dev), _ptr(mn, f32, "aabb_min"), _ptr(nc, i32, "num_cells"), float(radius), n_src,
+        n_dst, int(n_batches or 0), *grid_args, C.c_void_p(ws.data_ptr()), ws.numel(), rows, _ptr(neighbors, i32, "neighbors"),
+        _ptr(sources, i32, "sources"), _ptr(ends, i32, "ends"), _ptr(info, i32, "info"), _stream(dev), *extra), entry)
+    if grid is not None and not valid:
+        grids.commit(key, radius, grid, params)
+    return neighbors, ends, info, sources, degrees
+
+
 def ball_query_bounded(pts_src, pts_dst, batch_src, batch_dst, radius: float, capacity: int,
                        n_batches: Optional[int] = None, want_sources: bool = False,
                        neighbors_out: Optional[torch.Tensor] = None, src_box=None, grids: Optional[SourceGrids] = None):
@@ -298,57 +360,10 @@ def ball_query_bounded(pts_src, pts_dst, batch_src, batch_dst, radius: float, ca
     ``[capacity, 2]`` int32 buffer to write into (e.g. a slice of a larger arena) instead of a fresh allocation.
     ``grids``: the source cloud's ``SourceGrids`` -- its cell grid for this radius is then built once and shared by every
     query that passes the holder (not while a HIP graph is being captured: a replay must not depend on what ran before)."""
-    lib = _lib.load()
-    src_own, batch_own = pts_src, batch_src  # (what a source grid is keyed on: the caller's tensors, not their conversions)
-    pts_src = _as(pts_src, torch.float32)
-    pts_dst = _as(pts_dst, torch.float32)
-    if pts_src.dim() != 2 or pts_src.shape[1] != 3 or pts_dst.dim() != 2 or pts_dst.shape[1] != 3:
-        raise ValueError("ball_query: only [N,3] point sets are supported")
-    if not (radius > 0) or capacity < 0:
-        raise ValueError("ball_query_bounded: radius must be positive and capacity non-negative")
-    dev = pts_src.device
-    bs, bd = _as(batch_src, torch.int32), _as(batch_dst, torch.int32)
-    n_src, n_dst = pts_src.shape[0], pts_dst.shape[0]
-    f32, i32 = torch.float32, torch.int32
-    if neighbors_out is not None:
-        if neighbors_out.shape != (int(capacity), 2) or neighbors_out.dtype != i32 or not neighbors_out.is_contiguous():
-            raise ValueError(f"neighbors_out must be a contiguous int32 [{int(capacity)}, 2] tensor")
-        neighbors = neighbors_out
-    else:
-        neighbors = _empty((int(capacity), 2), dtype=i32, device=dev)
-    sources = _empty(int(capacity), dtype=i32, device=dev) if want_sources else None
-    ends = _empty(n_dst, dtype=i32, device=dev)
-    if n_dst == 0:
-        info = torch.zeros(2, dtype=i32, device=dev)
-        return (neighbors, ends, info, sources) if want_sources else (neighbors, ends, info)
-    info = _empty(2, dtype=i32, device=dev)  # both words are written by the store pass
-    needs_grid, ws_bytes, grid_bytes = _ball_query_sizes(n_src, n_dst)
-    ws = _workspace(ws_bytes, dev)
-    if grids is not None and needs_grid and src_box is not None and SHARED_GRIDS and not torch.cuda.is_current_stream_capturing():
-        # (src_box: the grid parameters are then a pure function of the cloud's cached boxes and the radius, so two calls
-        # with the same key search the same cells -- and the parameters themselves are kept with the grid)
-        key = SourceGrids.key(src_own, batch_own, n_batches)
-        grid, valid = grids.slot(key, radius, grid_bytes, dev)
-        params = grids.params.get(float(radius)) if valid else None
-        if params is None:
-            valid, params = False, _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box)
-        mn, nc = params
-        _lib.check(lib.se3_ball_query_bounded_shared(
-            _ptr(pts_src, f32, "pts_src"), _ptr(pts_dst, f32, "pts_dst", dev), _ptr(bs, i32, "batch_src", dev),
-            _ptr(bd, i32, "batch_dst", dev), _ptr(mn, f32, "aabb_min"), _ptr(nc, i32, "num_cells"), float(radius), n_src,
-            n_dst, int(n_batches or 0), C.c_void_p(grid.data_ptr()), grid.numel(), int(valid), C.c_void_p(ws.data_ptr()),
-            ws.numel(), int(capacity), _ptr(neighbors, i32, "neighbors"), _ptr(sources, i32, "sources"), _ptr(ends, i32, "ends"),
-            _ptr(info, i32, "info"), _stream(dev)), "se3_ball_query_bounded_shared")
-        if not valid:
-            grids.commit(key, radius, grid, params)
-        return (neighbors, ends, info, sources) if want_sources else (neighbors, ends, info)
-    mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if needs_grid else (None, None)
-    _lib.check(lib.se3_ball_query_bounded(
-        _ptr(pts_src, f32, "pts_src"), _ptr(pts_dst, f32, "pts_dst", dev), _ptr(bs, i32, "batch_src", dev),
-        _ptr(bd, i32, "batch_dst", dev), _ptr(mn, f32, "aabb_min"), _ptr(nc, i32, "num_cells"), float(radius), n_src,
-        n_dst, int(n_batches or 0), C.c_void_p(ws.data_ptr()), ws.numel(), int(capacity), _ptr(neighbors, i32, "neighbors"),
-        _ptr(sources, i32, "sources"), _ptr(ends, i32, "ends"), _ptr(info, i32, "info"), _stream(dev)),
-        "se3_ball_query_bounded")
+    neighbors, ends, info, sources, _ = _bounded_query(
+        "ball_query_bounded", ("se3_ball_query_bounded", "se3_ball_query_bounded_shared"), pts_src, pts_dst, batch_src,
+        batch_dst, radius, capacity, n_batches, neighbors_out, f"neighbors_out must be a contiguous int32 [{int(capacity)}, 2] tensor",
+        src_box, grids, want_sources=want_sources)
     return (neighbors, ends, info, sources) if want_sources else (neighbors, ends, info)
 
 
@@ -381,64 +396,22 @@ def ball_query_capped(pts_src, pts_dst, batch_src, batch_dst, radius: float, max
     if m > MAX_CAPPED_NEIGHBORS:
         raise NotImplementedError(f"ball_query_capped: max_neighbors = {m}; the HIP kernel keeps at most "
                                   f"{MAX_CAPPED_NEIGHBORS} neighbours per sample (one per lane of a wavefront)")
-    src_own, batch_own = pts_src, batch_src
-    pts_src = _as(pts_src, torch.float32)
-    pts_dst = _as(pts_dst, torch.float32)
-    if pts_src.dim() != 2 or pts_src.shape[1] != 3 or pts_dst.dim() != 2 or pts_dst.shape[1] != 3:
-        raise ValueError("ball_query: only [N,3] point sets are supported")
-    if not (radius > 0) or (capacity is not None and capacity < 0):
-        raise ValueError("ball_query_capped: radius must be positive and capacity non-negative")
-    dev = pts_src.device
-    n_src, n_dst = pts_src.shape[0], pts_dst.shape[0]
-    f32, i32 = torch.float32, torch.int32
     exact = capacity is None
     if exact and m <= 0:  # no cap and no buffer to size from it: the two-phase query
         nb, ends = ball_query(pts_src, pts_dst, batch_src, batch_dst, radius, n_batches, src_box)
         return (nb, ends, torch.diff(ends, prepend=ends.new_zeros(1))) if want_degrees else (nb, ends)
-    rows = n_dst * m if exact else int(capacity)
-    bs, bd = _as(batch_src, i32), _as(batch_dst, i32)
-    if neighbors_out is not None:
-        if exact or neighbors_out.shape != (rows, 2) or neighbors_out.dtype != i32 or not neighbors_out.is_contiguous():
-            raise ValueError("neighbors_out must be a contiguous int32 [capacity, 2] tensor (and needs a capacity)")
-        neighbors = neighbors_out
-    else:
-        neighbors = _empty((rows, 2), dtype=i32, device=dev)
-    ends = _empty(n_dst, dtype=i32, device=dev)
-    degrees = _empty(n_dst, dtype=i32, device=dev) if want_degrees else None
-    if seed_tensor is not None and (seed_tensor.numel() != 1 or seed_tensor.dtype != i32):
-        raise ValueError("seed_tensor must be a 1-element int32 tensor")
-    if n_dst == 0:
-        info = torch.zeros(2, dtype=i32, device=dev)
-    else:
-        info = _empty(2, dtype=i32, device=dev)  # both words are written by the store pass
-        needs_grid = bool(_ball_query_sizes(n_src, n_dst)[0])
-        grid_bytes = _ball_query_sizes(n_src, n_dst)[2]
-        ws = _workspace(lib.se3_ball_query_capped_workspace_bytes(n_src, n_dst), dev)
-        grid, valid, key = None, False, None
-        if grids is not None and needs_grid and src_box is not None and SHARED_GRIDS and not torch.cuda.is_current_stream_capturing():
-            # the source cloud's grid for this radius, shared with the uncapped queries (see ball_query_bounded)
-            key = SourceGrids.key(src_own, batch_own, n_batches)
-            grid, valid = grids.slot(key, radius, grid_bytes, dev)
-            params = grids.params.get(float(radius)) if valid else None
-            if params is None:
-                valid, params = False, _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box)
-            mn, nc = params
-        else:
-            mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if needs_grid else (None, None)
-        _lib.check(lib.se3_ball_query_capped(
-            _ptr(pts_src, f32, "pts_src"), _ptr(pts_dst, f32, "pts_dst", dev), _ptr(bs, i32, "batch_src", dev),
-            _ptr(bd, i32, "batch_dst", dev), _ptr(mn, f32, "aabb_min"), _ptr(nc, i32, "num_cells"), float(radius), n_src,
-            n_dst, int(n_batches or 0), C.c_void_p(grid.data_ptr() if grid is not None else 0),
-            grid.numel() if grid is not None else 0, int(valid), C.c_void_p(ws.data_ptr()), ws.numel(), rows,
-            _ptr(neighbors, i32, "neighbors"), C.c_void_p(0), _ptr(ends, i32, "ends"), _ptr(info, i32, "info"), _stream(dev),
-            m, int(seed) & 0xFFFFFFFF, _ptr(seed_tensor, i32, "seed_tensor", dev), _ptr(degrees, i32, "degrees")),
-            "se3_ball_query_capped")
-        if grid is not None and not valid:
-            grids.commit(key, radius, grid, params)
-    if exact:
-        res = (neighbors[:int(info[0].item())], ends)
-    else:
-        res = (neighbors, ends, info)
+
+    def tail(dev, degrees):
+        if seed_tensor is not None and (seed_tensor.numel() != 1 or seed_tensor.dtype != torch.int32):
+            raise ValueError("seed_tensor must be a 1-element int32 tensor")
+        return (m, int(seed) & 0xFFFFFFFF, _ptr(seed_tensor, torch.int32, "seed_tensor", dev), _ptr(degrees, torch.int32, "degrees"))
+
+    neighbors, ends, info, _, degrees = _bounded_query(
+        "ball_query_capped", (None, "se3_ball_query_capped"), pts_src, pts_dst, batch_src, batch_dst, radius, capacity,
+        n_batches, neighbors_out, "neighbors_out must be a contiguous int32 [capacity, 2] tensor (and needs a capacity)",
+        src_box, grids, rows_per_sample=m, want_degrees=want_degrees,
+        workspace_bytes=lib.se3_ball_query_capped_workspace_bytes, tail=tail)
+    res = (neighbors[:int(info[0].item())], ends) if exact else (neighbors, ends, info)
     return res + (degrees,) if want_degrees else res
 
 

@@ -33,6 +33,15 @@ class Se3Prepared(C.Structure):
                 ("geom_in_valid", C.c_int32), ("geom_out_valid", C.c_int32), ("feat_words_valid", C.c_int32)]
 
 
+class Se3Level(C.Structure):
+    """struct se3_level (include/se3conv_levels.h): one level of a ``se3_grid_levels`` chain."""
+
+    _fields_ = [("cell_size", C.c_float), ("capacity", C.c_int64),
+                ("cell_ids", C.c_void_p), ("sorted_ids", C.c_void_p), ("cell_ends", C.c_void_p),
+                ("pts", C.c_void_p), ("batch_ids", C.c_void_p),
+                ("u", C.c_void_p), ("ids", C.c_void_p), ("picked", C.c_void_p)]
+
+
 class Se3LibraryError(RuntimeError):
     pass
 
@@ -115,6 +124,14 @@ CAPPED_SIGNATURES = {
                                         _P, _I32, C.c_uint32, _P, _P]),
 }
 
+# the chain of grid sub-sampling levels with device-side sizes, declared in include/se3conv_levels.h (additions inside ABI
+# version 6 as well); must list every symbol that header declares
+_LVL = C.POINTER(Se3Level)
+LEVEL_SIGNATURES = {
+    "se3_grid_levels_workspace_bytes": (_SZ, [_I64, _I32, _LVL, _I32]),
+    "se3_grid_levels": (C.c_int, [_P, _P, _I64, _P, _I32, _LVL, _I32, _P, _P, _SZ, _P]),
+}
+
 _lib = None
 
 
@@ -132,7 +149,7 @@ def load() -> C.CDLL:
     if lib.se3_abi_version() != ABI_VERSION:  # (checked before the symbols: an older library lacks some of them)
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
-    for name, (res, args) in list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so

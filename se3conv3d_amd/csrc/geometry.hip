@@ -11,13 +11,20 @@
 #include <hipcub/hipcub.hpp>
 
 #include <cstdlib>
+#include <limits>
 
 #include "common.h"
 #include "../../include/se3conv_capped.h"
+#include "../../include/se3conv_levels.h"
 
 namespace se3 {
 
 namespace {
+
+// The number of present rows of an array of `n`: the device word `n_valid` clamped to [0, n], or n without one.
+__device__ __forceinline__ int64_t present_rows(const int32_t* __restrict__ n_valid, int64_t n) {
+  return n_valid ? max(min((int64_t)*n_valid, n), (int64_t)0) : n;
+}
 
 __device__ __forceinline__ void cell_of(const float* __restrict__ pts, const int32_t* __restrict__ batch_ids,
                                         const float* __restrict__ aabb_min, const int nc[3], const float inv[3],
@@ -61,15 +68,23 @@ template <class KEY>
 __global__ void compute_keys_kernel(const float* __restrict__ pts, const int32_t* __restrict__ batch_ids,
                                     const float* __restrict__ aabb_min, const int32_t* __restrict__ num_cells,
                                     const float* __restrict__ cell_size, float cell_scalar, int64_t n,
-                                    typename KEY::type* __restrict__ keys, int32_t* __restrict__ iota) {
+                                    typename KEY::type* __restrict__ keys, int32_t* __restrict__ iota,
+                                    const int32_t* __restrict__ n_valid) {
   // cell_size == nullptr: the same cell size `cell_scalar` in every dimension (ball query: cell = radius)
   const int nc[3] = {KEY::cells(num_cells[0]), KEY::cells(num_cells[1]), KEY::cells(num_cells[2])};
   const float inv[3] = {1.0f / (cell_size ? cell_size[0] : cell_scalar), 1.0f / (cell_size ? cell_size[1] : cell_scalar),
                         1.0f / (cell_size ? cell_size[2] : cell_scalar)};
+  // n_valid (device, may be NULL = n): rows from *n_valid on are absent (se3_grid_levels).  They are not read and get
+  // the largest key, which a stable sort puts behind every present row, in input order
+  const int64_t valid = present_rows(n_valid, n);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int cell[3], b;
-    cell_of(pts, batch_ids, aabb_min, nc, inv, i, cell, b);
-    keys[i] = KEY::key(cell, nc, b);
+    if (i < valid) {
+      int cell[3], b;
+      cell_of(pts, batch_ids, aabb_min, nc, inv, i, cell, b);
+      keys[i] = KEY::key(cell, nc, b);
+    } else {
+      keys[i] = std::numeric_limits<typename KEY::type>::max();
+    }
     if (iota) iota[i] = (int32_t)i;
   }
 }
@@ -425,7 +440,9 @@ __global__ void batch_aabb_init_kernel(float* __restrict__ mn, float* __restrict
 // of a single 65 k-point cloud.  64-point groups that straddle two elements fall back to per-point atomics.
 __global__ __launch_bounds__(256) void batch_aabb_kernel(const float* __restrict__ pts,
                                                          const int32_t* __restrict__ batch_ids, int64_t n,
-                                                         float* __restrict__ mn, float* __restrict__ mx) {
+                                                         const int32_t* __restrict__ n_valid, float* __restrict__ mn,
+                                                         float* __restrict__ mx) {
+  n = present_rows(n_valid, n);  // rows from *n_valid on are absent (se3_grid_levels): never read
   const float inf = __int_as_float(0x7f800000);
   float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
   int cur = -1;  // wave-uniform: batch element of the running values
@@ -712,19 +729,20 @@ extern "C" int se3_compute_keys(const float* pts, const int32_t* batch_ids, cons
     return SE3_ERR_INVALID_ARGUMENT;
   if (n == 0) return SE3_OK;
   hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pts, batch_ids,
-                     aabb_min, num_cells, cell_size, 0.f, n, keys, (int32_t*)nullptr);
+                     aabb_min, num_cells, cell_size, 0.f, n, keys, (int32_t*)nullptr, (const int32_t*)nullptr);
   return check_launch();
 }
 
 static int batch_aabb_impl(const float* pts, const int32_t* batch_ids, int64_t n, int32_t n_batches, float* aabb_min,
-                           float* aabb_max, int32_t* num_cells_to_zero, hipStream_t stream) {
+                           float* aabb_max, int32_t* num_cells_to_zero, hipStream_t stream,
+                           const int32_t* n_valid = nullptr) {
   hipLaunchKernelGGL(batch_aabb_init_kernel, dim3((n_batches * 3 + 255) / 256), dim3(256), 0, stream, aabb_min, aabb_max,
                      n_batches * 3, num_cells_to_zero);
   if (n > 0) {
     int64_t blocks = (n + 1023) / 1024;  // 4 groups of 64 points per wavefront before it issues its 6 atomics
     if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(batch_aabb_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, pts, batch_ids, n, aabb_min,
-                       aabb_max);
+    hipLaunchKernelGGL(batch_aabb_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, pts, batch_ids, n, n_valid,
+                       aabb_min, aabb_max);
   }
   return check_launch();
 }
@@ -891,7 +909,7 @@ extern "C" int se3_knn_query_grid(const float* pts, const int32_t* batch_ids, co
   {
     ProfScope prof("knn_sort", stream);
     hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, aabb_min, num_cells,
-                       cell_size, 0.f, n, keys, ids);
+                       cell_size, 0.f, n, keys, ids, (const int32_t*)nullptr);
     if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sids, (int)n, 0, 64, stream) !=
         hipSuccess)
       return SE3_ERR_LAUNCH;
@@ -1037,7 +1055,7 @@ static int bq_grid_windows(const BqCall& c, const BqPlan& p, int key_bits) {
     int32_t* ids = (int32_t*)(gws + p.l.ids);
     // cell size = radius in every dimension (BallQuery.py:39-40)
     hipLaunchKernelGGL(compute_keys_kernel<KEY>, dim3(blocks_for(c.n_src)), dim3(256), 0, c.stream, c.pts_src, c.batch_src,
-                       c.aabb_min, c.num_cells, (const float*)nullptr, c.radius, c.n_src, keys, ids);
+                       c.aabb_min, c.num_cells, (const float*)nullptr, c.radius, c.n_src, keys, ids, (const int32_t*)nullptr);
     size_t temp_bytes = p.l.temp_bytes;
     if (sort_pairs_no_scratch(ws + p.l.temp, temp_bytes, keys, skeys, ids, sids, (int)c.n_src, 0, key_bits, c.stream) != hipSuccess)
       return SE3_ERR_LAUNCH;
@@ -1413,37 +1431,63 @@ extern "C" int se3_csr_transpose(const int32_t* neighbors, int64_t n_edges, int6
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-__global__ void cell_heads_kernel(const int64_t* __restrict__ skeys, int64_t n, int32_t* __restrict__ flags) {
+// n_valid (device, may be NULL = n) in the kernels below: the present rows of se3_grid_levels.  The sort has put the
+// absent rows behind position *n_valid, so a head flag is set only below it.
+__global__ void cell_heads_kernel(const int64_t* __restrict__ skeys, int64_t n, const int32_t* __restrict__ n_valid,
+                                  int32_t* __restrict__ flags) {
+  const int64_t valid = present_rows(n_valid, n);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    flags[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1 : 0;
+    flags[i] = (i < valid && (i == 0 || skeys[i] != skeys[i - 1])) ? 1 : 0;
 }
 
-// ranks = inclusive scan of the head flags: position i of the sorted order belongs to cell ranks[i] - 1
+// ranks = inclusive scan of the head flags: position i of the sorted order belongs to cell ranks[i] - 1.
+// overflow == nullptr (se3_grid_subsample): every cell is kept and nothing beyond the cells is written.  Otherwise
+// (se3_grid_levels) cell_ends has `capacity` entries: cells from `capacity` on are dropped (their rows and the absent
+// rows get the cell id -1), n_cells[0] receives the true cell count, *overflow whether it exceeds the capacity, and
+// the entries of cell_ends behind the kept cells receive the number of present rows.
 __global__ void cell_scatter_kernel(const int32_t* __restrict__ sids, const int32_t* __restrict__ ranks,
-                                    const int32_t* __restrict__ flags, int64_t n, int32_t* __restrict__ cell_ids,
-                                    int32_t* __restrict__ cell_ends, int32_t* __restrict__ n_cells) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = ranks[i] - 1;
-    cell_ids[sids[i]] = r;
-    if (i == n - 1 || flags[i + 1]) cell_ends[r] = (int32_t)(i + 1);
-    if (i == n - 1) *n_cells = r + 1;
+                                    const int32_t* __restrict__ flags, int64_t n, const int32_t* __restrict__ n_valid,
+                                    int64_t capacity, int32_t* __restrict__ cell_ids, int32_t* __restrict__ cell_ends,
+                                    int32_t* __restrict__ n_cells, int32_t* __restrict__ overflow) {
+  const int64_t valid = present_rows(n_valid, n);
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = first; i < n; i += step) {
+    const int r = i < valid ? ranks[i] - 1 : -1;
+    const bool kept = r >= 0 && (!overflow || r < capacity);
+    cell_ids[sids[i]] = kept ? r : -1;
+    if (kept && (i == valid - 1 || flags[i + 1])) cell_ends[r] = (int32_t)(i + 1);
+    if (i == valid - 1) {
+      *n_cells = r + 1;
+      if (overflow) *overflow = r + 1 > capacity ? 1 : 0;
+    }
   }
+  if (!overflow) return;
+  const int64_t total = valid > 0 ? ranks[valid - 1] : 0;
+  if (valid == 0 && first == 0) *n_cells = 0, *overflow = 0;
+  for (int64_t j = min(total, capacity) + first; j < capacity; j += step) cell_ends[j] = (int32_t)valid;
 }
 
 enum { kPoolAvg = 0, kPoolMax = 1, kPoolMin = 2, kPoolSum = 3 };
 
 // out[cell, ch] = reduce over the cell's rows (sorted_ids[start .. end)) of src[row, ch]; thread = (cell, channel),
 // channels fastest, so a cell's row is read with consecutive lanes.  n_cells_dev != nullptr: the cell count is still
-// on the device (inside se3_grid_subsample); the grid is sized for the upper bound.
+// on the device (inside se3_grid_subsample); the grid is sized for the upper bound.  capacity > 0 (se3_grid_levels): `out`
+// has that many rows, the cells from `capacity` on are dropped and the rows behind the kept cells are set to zero.
 template <int MODE>
 __global__ void segment_pool_kernel(const float* __restrict__ src, const int32_t* __restrict__ sorted_ids,
                                     const int32_t* __restrict__ cell_ends, int64_t n_cells, const int32_t* n_cells_dev,
-                                    int c, float* __restrict__ out, int32_t* __restrict__ arg) {
+                                    int c, float* __restrict__ out, int32_t* __restrict__ arg, int64_t capacity) {
   if (n_cells_dev) n_cells = *n_cells_dev;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n_cells * c;
+  if (capacity > 0) n_cells = min(n_cells, capacity);
+  const int64_t rows = capacity > 0 ? capacity : n_cells;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < rows * c;
        idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t cell = idx / c;
     const int ch = (int)(idx - cell * c);
+    if (cell >= n_cells) {
+      out[idx] = 0.f;
+      continue;
+    }
     const int start = cell > 0 ? cell_ends[cell - 1] : 0, end = cell_ends[cell];
     float acc = 0.f;
     int best = -1;
@@ -1481,10 +1525,12 @@ __global__ void segment_unpool_kernel(const float* __restrict__ cell_vals, const
 
 __global__ void cell_batch_ids_kernel(const int32_t* __restrict__ batch_ids, const int32_t* __restrict__ sorted_ids,
                                       const int32_t* __restrict__ cell_ends, const int32_t* __restrict__ n_cells_dev,
-                                      int32_t* __restrict__ out) {
-  const int64_t n_cells = *n_cells_dev;
-  for (int64_t cell = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; cell < n_cells; cell += (int64_t)gridDim.x * blockDim.x)
-    out[cell] = batch_ids[sorted_ids[cell > 0 ? cell_ends[cell - 1] : 0]];  // the batch id is part of the key
+                                      int32_t* __restrict__ out, int64_t capacity) {
+  // capacity > 0 (se3_grid_levels): `out` has that many rows; those behind the kept cells are set to -1
+  const int64_t n_cells = capacity > 0 ? min((int64_t)*n_cells_dev, capacity) : (int64_t)*n_cells_dev;
+  const int64_t rows = capacity > 0 ? capacity : n_cells;
+  for (int64_t cell = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; cell < rows; cell += (int64_t)gridDim.x * blockDim.x)
+    out[cell] = cell < n_cells ? batch_ids[sorted_ids[cell > 0 ? cell_ends[cell - 1] : 0]] : -1;  // the batch id is part of the key
 }
 
 // Frame pooling (scope row f-3, pc/PointcloudRotEquiv.py:224-251): rows point*F + frame -> one row per point
@@ -1546,6 +1592,40 @@ GsLayout gs_layout(int64_t n, int n_batches) {
 
 }  // namespace
 
+// The stages se3_grid_subsample and se3_grid_levels share: boxes, cell counts, keys, sort, cell heads, scan, scatter.
+// `l` is the layout of a workspace for at least `n` rows.  n_valid / capacity / overflow: see cell_scatter_kernel
+// (se3_grid_subsample: nullptr, n, nullptr).  n == 0 launches the scatter alone, for its pads and counts.
+static int grid_cells_impl(const float* pts, const int32_t* batch_ids, int64_t n, const int32_t* n_valid, int32_t n_batches,
+                           float cell_size, char* ws, const GsLayout& l, int32_t* cell_ids, int32_t* sorted_ids,
+                           int32_t* cell_ends, int64_t capacity, int32_t* n_cells, int32_t* overflow, hipStream_t stream) {
+  float* box_min = (float*)(ws + l.box_min);
+  float* box_max = (float*)(ws + l.box_max);
+  int32_t* num_cells = (int32_t*)(ws + l.num_cells);
+  int64_t* keys = (int64_t*)(ws + l.keys);
+  int64_t* skeys = (int64_t*)(ws + l.skeys);
+  int32_t* ids = (int32_t*)(ws + l.ids);
+  int32_t* flags = (int32_t*)(ws + l.flags);
+  int32_t* ranks = (int32_t*)(ws + l.ranks);
+  if (n > 0) {
+    if (int rc = batch_aabb_impl(pts, batch_ids, n, n_batches, box_min, box_max, num_cells, stream, n_valid)) return rc;
+    hipLaunchKernelGGL(grid_params_kernel, dim3((n_batches * 3 + 255) / 256), dim3(256), 0, stream, box_min, box_max,
+                       n_batches, cell_size, 1e-6f, num_cells);
+    hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, box_min,
+                       num_cells, (const float*)nullptr, cell_size, n, keys, ids, n_valid);
+    size_t temp_bytes = l.temp_bytes;
+    if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sorted_ids, (int)n, 0, 64, stream) !=
+        hipSuccess)
+      return SE3_ERR_LAUNCH;
+    hipLaunchKernelGGL(cell_heads_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, skeys, n, n_valid, flags);
+    temp_bytes = l.temp_bytes;
+    if (hipcub::DeviceScan::InclusiveSum(ws + l.temp, temp_bytes, flags, ranks, (int)n, stream) != hipSuccess)
+      return SE3_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(cell_scatter_kernel, dim3(blocks_for(n > capacity ? n : capacity)), dim3(256), 0, stream, sorted_ids,
+                     ranks, flags, n, n_valid, capacity, cell_ids, cell_ends, n_cells, overflow);
+  return check_launch();
+}
+
 extern "C" size_t se3_grid_subsample_workspace_bytes(int64_t n, int32_t n_batches) { return gs_layout(n, n_batches).total; }
 
 extern "C" int se3_grid_subsample(const float* pts, const int32_t* batch_ids, int64_t n, int32_t n_batches,
@@ -1561,35 +1641,14 @@ extern "C" int se3_grid_subsample(const float* pts, const int32_t* batch_ids, in
     return SE3_ERR_INVALID_ARGUMENT;
   const GsLayout l = gs_layout(n, n_batches);
   if (workspace_bytes < l.total) return SE3_ERR_WORKSPACE;
-  char* ws = (char*)workspace;
-  float* box_min = (float*)(ws + l.box_min);
-  float* box_max = (float*)(ws + l.box_max);
-  int32_t* num_cells = (int32_t*)(ws + l.num_cells);
-  int64_t* keys = (int64_t*)(ws + l.keys);
-  int64_t* skeys = (int64_t*)(ws + l.skeys);
-  int32_t* ids = (int32_t*)(ws + l.ids);
-  int32_t* flags = (int32_t*)(ws + l.flags);
-  int32_t* ranks = (int32_t*)(ws + l.ranks);
-  if (int rc = batch_aabb_impl(pts, batch_ids, n, n_batches, box_min, box_max, num_cells, stream)) return rc;
-  hipLaunchKernelGGL(grid_params_kernel, dim3((n_batches * 3 + 255) / 256), dim3(256), 0, stream, box_min, box_max,
-                     n_batches, cell_size, 1e-6f, num_cells);
-  hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, box_min, num_cells,
-                     (const float*)nullptr, cell_size, n, keys, ids);
-  size_t temp_bytes = l.temp_bytes;
-  if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sorted_ids, (int)n, 0, 64, stream) !=
-      hipSuccess)
-    return SE3_ERR_LAUNCH;
-  hipLaunchKernelGGL(cell_heads_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, skeys, n, flags);
-  temp_bytes = l.temp_bytes;
-  if (hipcub::DeviceScan::InclusiveSum(ws + l.temp, temp_bytes, flags, ranks, (int)n, stream) != hipSuccess)
-    return SE3_ERR_LAUNCH;
-  hipLaunchKernelGGL(cell_scatter_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, sorted_ids, ranks, flags, n, cell_ids,
-                     cell_ends, n_cells);
+  if (int rc = grid_cells_impl(pts, batch_ids, n, nullptr, n_batches, cell_size, (char*)workspace, l, cell_ids, sorted_ids,
+                               cell_ends, n, n_cells, nullptr, stream))
+    return rc;
   // level points = cell means (first n_cells rows of cell_pts), level batch ids
   hipLaunchKernelGGL(segment_pool_kernel<kPoolAvg>, dim3(blocks_for(n * 3)), dim3(256), 0, stream, pts, sorted_ids,
-                     cell_ends, (int64_t)0, n_cells, 3, cell_pts, (int32_t*)nullptr);
+                     cell_ends, (int64_t)0, n_cells, 3, cell_pts, (int32_t*)nullptr, (int64_t)0);
   hipLaunchKernelGGL(cell_batch_ids_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, batch_ids, sorted_ids, cell_ends,
-                     n_cells, cell_batch_ids);
+                     n_cells, cell_batch_ids, (int64_t)0);
   return check_launch();
 }
 
@@ -1603,7 +1662,7 @@ extern "C" int se3_segment_pool(const float* src, const int32_t* sorted_ids, con
   const dim3 grid(blocks_for(n_cells * channels)), block(256);
 #define SE3_POOL(M)                                                                                                   \
   hipLaunchKernelGGL(segment_pool_kernel<M>, grid, block, 0, stream, src, sorted_ids, cell_ends, n_cells,                 \
-                     (const int32_t*)nullptr, channels, out, arg)
+                     (const int32_t*)nullptr, channels, out, arg, (int64_t)0)
   if (mode == kPoolAvg) SE3_POOL(kPoolAvg);
   else if (mode == kPoolMax) SE3_POOL(kPoolMax);
   else if (mode == kPoolMin) SE3_POOL(kPoolMin);
@@ -1670,17 +1729,35 @@ namespace {
 // ids[c] = start(c) + floor(u[c] * count(c))  (a position in the cell-sorted point list, GridSubSample.py:52-54);
 // picked[c] = sorted_ids[ids[c]] (the point that represents the cell, :67).  The product is clamped to count - 1:
 // u * count can round up to count in fp32, which in the reference selects the first point of the NEXT cell.
+// capacity > 0 (se3_grid_levels): the cell count is the device word *n_cells_dev cut to `capacity`, the outputs have
+// `capacity` rows, the picked row's point and batch id are gathered into out_pts / out_bid, and the rows behind the kept
+// cells are set to -1 (points: 0).
 __global__ void grid_pick_kernel(const int32_t* __restrict__ cell_ends, const int32_t* __restrict__ sorted_ids,
                                  const float* __restrict__ u, int64_t n_cells, int32_t* __restrict__ ids,
-                                 int32_t* __restrict__ picked) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n_cells) return;
-  const int start = c > 0 ? cell_ends[c - 1] : 0;
-  const int count = cell_ends[c] - start;
-  int off = (int)floorf(u[c] * (float)count);
-  off = min(max(off, 0), count - 1);
-  ids[c] = start + off;
-  picked[c] = sorted_ids[start + off];
+                                 int32_t* __restrict__ picked, const int32_t* __restrict__ n_cells_dev, int64_t capacity,
+                                 const float* __restrict__ src_pts, const int32_t* __restrict__ src_bid,
+                                 float* __restrict__ out_pts, int32_t* __restrict__ out_bid) {
+  if (capacity > 0) n_cells = min((int64_t)*n_cells_dev, capacity);
+  const int64_t rows = capacity > 0 ? capacity : n_cells;
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < rows; c += (int64_t)gridDim.x * blockDim.x) {
+    if (c >= n_cells) {
+      ids[c] = -1, picked[c] = -1, out_bid[c] = -1;
+      out_pts[c * 3] = 0.f, out_pts[c * 3 + 1] = 0.f, out_pts[c * 3 + 2] = 0.f;
+      continue;
+    }
+    const int start = c > 0 ? cell_ends[c - 1] : 0;
+    const int count = cell_ends[c] - start;
+    int off = (int)floorf(u[c] * (float)count);
+    off = min(max(off, 0), count - 1);
+    const int row = sorted_ids[start + off];
+    ids[c] = start + off;
+    picked[c] = row;
+    if (capacity > 0) {
+      out_bid[c] = src_bid[row];
+      out_pts[c * 3] = src_pts[(int64_t)row * 3], out_pts[c * 3 + 1] = src_pts[(int64_t)row * 3 + 1];
+      out_pts[c * 3 + 2] = src_pts[(int64_t)row * 3 + 2];
+    }
+  }
 }
 
 // out[r] = src[idx[r]] for rows of `row_words` 4-byte words (gather) / out[idx[r]] = src[r] (scatter; idx unique)
@@ -1704,8 +1781,68 @@ extern "C" int se3_grid_pick(const int32_t* cell_ends, const int32_t* sorted_ids
   if (n_cells == 0) return SE3_OK;
   if (!cell_ends || !sorted_ids || !u || !ids || !picked) return SE3_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(grid_pick_kernel, dim3(blocks_for(n_cells)), dim3(256), 0, (hipStream_t)stream, cell_ends, sorted_ids,
-                     u, n_cells, ids, picked);
+                     u, n_cells, ids, picked, (const int32_t*)nullptr, (int64_t)0, (const float*)nullptr,
+                     (const int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr);
   return check_launch();
+}
+
+// ---- a chain of levels in one call, sizes on the device (include/se3conv_levels.h) --------------------------------------
+namespace {
+int64_t levels_max_rows(int64_t n_rows, const se3_level* levels, int32_t n_levels) {
+  int64_t n_max = n_rows;
+  for (int32_t l = 0; l + 1 < n_levels; ++l) n_max = std::max(n_max, levels[l].capacity);
+  return n_max;
+}
+}  // namespace
+
+extern "C" size_t se3_grid_levels_workspace_bytes(int64_t n_rows, int32_t n_batches, const se3_level* levels,
+                                                  int32_t n_levels) {
+  if (n_rows < 0 || n_batches < 1 || !levels || n_levels < 1) return 0;
+  return gs_layout(levels_max_rows(n_rows, levels, n_levels), n_batches).total;
+}
+
+extern "C" int se3_grid_levels(const float* pts, const int32_t* batch_ids, int64_t n_rows, const int32_t* n_valid,
+                               int32_t n_batches, const se3_level* levels, int32_t n_levels, int32_t* info, void* workspace,
+                               size_t workspace_bytes, void* stream_) {
+  if (n_rows < 0 || n_batches < 1 || n_levels < 1 || !levels || !info || !workspace) return SE3_ERR_INVALID_ARGUMENT;
+  if (n_rows > 0 && (!pts || !batch_ids)) return SE3_ERR_INVALID_ARGUMENT;
+  for (int32_t l = 0; l < n_levels; ++l) {
+    const se3_level& v = levels[l];
+    if (!(v.cell_size > 0.f) || v.capacity < 1) return SE3_ERR_INVALID_ARGUMENT;
+    if (!v.cell_ends || !v.pts || !v.batch_ids) return SE3_ERR_INVALID_ARGUMENT;
+    if ((l > 0 || n_rows > 0) && (!v.cell_ids || !v.sorted_ids)) return SE3_ERR_INVALID_ARGUMENT;  // [n_in]: may be empty
+    if ((v.u || v.ids || v.picked) && !(v.u && v.ids && v.picked)) return SE3_ERR_INVALID_ARGUMENT;
+  }
+  if (n_rows >= (1ll << 31) / 3) return SE3_ERR_UNSUPPORTED;
+  for (int32_t l = 0; l < n_levels; ++l)
+    if (levels[l].capacity >= (1ll << 31) / 3) return SE3_ERR_UNSUPPORTED;
+  // one region for the largest input of the chain; every level lays its arrays out from the same offsets
+  const GsLayout lay = gs_layout(levels_max_rows(n_rows, levels, n_levels), n_batches);
+  if (workspace_bytes < lay.total) return SE3_ERR_WORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const float* src_pts = pts;
+  const int32_t* src_bid = batch_ids;
+  int64_t n_in = n_rows;
+  for (int32_t l = 0; l < n_levels; ++l) {
+    const se3_level& v = levels[l];
+    int32_t* count = info + 2 * l;
+    if (int rc = grid_cells_impl(src_pts, src_bid, n_in, n_valid, n_batches, v.cell_size, (char*)workspace, lay, v.cell_ids,
+                                 v.sorted_ids, v.cell_ends, v.capacity, count, count + 1, stream))
+      return rc;
+    if (v.u) {
+      hipLaunchKernelGGL(grid_pick_kernel, dim3(blocks_for(v.capacity)), dim3(256), 0, stream, v.cell_ends, v.sorted_ids, v.u,
+                         (int64_t)0, v.ids, v.picked, count, v.capacity, src_pts, src_bid, v.pts, v.batch_ids);
+    } else {
+      hipLaunchKernelGGL(segment_pool_kernel<kPoolAvg>, dim3(blocks_for(v.capacity * 3)), dim3(256), 0, stream, src_pts,
+                         v.sorted_ids, v.cell_ends, (int64_t)0, count, 3, v.pts, (int32_t*)nullptr, v.capacity);
+      hipLaunchKernelGGL(cell_batch_ids_kernel, dim3(blocks_for(v.capacity)), dim3(256), 0, stream, src_bid, v.sorted_ids,
+                         v.cell_ends, count, v.batch_ids, v.capacity);
+    }
+    if (int rc = check_launch()) return rc;
+    // the next level reads this one in place; its present rows are the kept cells (the count word, cut to the capacity)
+    src_pts = v.pts, src_bid = v.batch_ids, n_in = v.capacity, n_valid = count;
+  }
+  return SE3_OK;
 }
 
 static int rows_move(bool scatter, const void* src, const int32_t* idx, int64_t n_rows, int64_t row_bytes, void* out,

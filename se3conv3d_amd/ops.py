@@ -499,6 +499,123 @@ def grid_subsample(pts, batch_ids, cell_size: float, n_batches: Optional[int] = 
     return GridCells(cell_ids, sorted_ids, cell_ends[:m], m, cell_pts[:m], cell_bid[:m])
 
 
+class LevelOverflow(RuntimeError):
+    """A level of ``grid_levels_bounded`` has more cells than its capacity: ``level`` is the first such level and
+    ``needed`` the row count it needs (the counts of deeper levels belong to the truncated hierarchy)."""
+
+    def __init__(self, level: int, needed: int, capacity: int):
+        super().__init__(f"level {level} of the bounded hierarchy has {needed} cells but a capacity of {capacity} rows: "
+                         f"run again with a capacity of at least {needed}")
+        self.level, self.needed, self.capacity = level, needed, capacity
+
+
+class BoundedLevels:
+    """What ``grid_levels_bounded`` returns: per level the padded tensors of ``struct se3_level``
+    (include/se3conv_levels.h) as a dict -- ``cell_ids``, ``sorted_ids`` ``[n_in]``, ``cell_ends``, ``pts``, ``batch_ids``
+    ``[capacity]`` and, on random levels, ``u``, ``ids``, ``picked`` ``[capacity]`` -- and ``info [n_levels, 2]`` (true cell
+    count, overflow flag), all on the device.  Nothing here has been read by the host until ``trim()``."""
+
+    def __init__(self, levels, info, counts, n_rows, has_n_valid, keep):
+        self.levels, self.info, self.n_rows = levels, info, n_rows
+        self.capacities = [lv["pts"].shape[0] for lv in levels]
+        self._counts, self._has_n_valid, self._keep = counts, has_n_valid, keep
+
+    def trim(self):
+        """The ONE device-to-host copy of a bounded build: reads every level size, raises ``LevelOverflow`` for the first
+        level that did not fit, and otherwise returns one ``GridCells`` per level -- views of the padded buffers, no
+        copies -- as ``grid_subsample`` builds them (``ids`` / ``picked`` are set on random levels and None otherwise; a
+        random level's ``pts`` / ``batch_ids`` are those of its picked rows)."""
+        counts = self._counts.cpu().tolist()
+        present = self.n_rows
+        if self._has_n_valid:
+            present = min(max(counts[0][0], 0), self.n_rows)
+            counts = counts[1:]
+        for l, ((m, flag), cap) in enumerate(zip(counts, self.capacities)):
+            if flag:
+                raise LevelOverflow(l, m, cap)
+        out = []
+        for lv, (m, _) in zip(self.levels, counts):
+            cells = GridCells(lv["cell_ids"][:present], lv["sorted_ids"][:present], lv["cell_ends"][:m], m, lv["pts"][:m],
+                              lv["batch_ids"][:m])
+            cells.ids = lv["ids"][:m] if "ids" in lv else None
+            cells.picked = lv["picked"][:m] if "picked" in lv else None
+            out.append(cells)
+            present = m
+        return out
+
+
+def grid_levels_bounded(pts, batch_ids, cell_sizes, capacities, n_batches: int, n_valid: Optional[torch.Tensor] = None,
+                        rnd=None, rnd_values=None) -> BoundedLevels:
+    """A chain of grid sub-sampling levels in one library call (``se3_grid_levels``, include/se3conv_levels.h): level l is
+    written into buffers of ``capacities[l]`` rows (``"input"``: the row count of ``pts`` for every level, which cannot
+    overflow), the level sizes stay on the device, and nothing synchronises with the host -- the call can be captured into a
+    HIP graph and replayed on another batch.  ``n_valid`` (int32 device word, optional): only rows ``[0, n_valid)`` of
+    ``pts`` / ``batch_ids`` are present.  ``rnd[l]`` true: level l is one random point per cell, drawn with
+    ``rnd_values[l]`` (``[capacities[l]]`` uniform numbers in [0,1); default: ``torch.rand`` on the device).
+    ``pts`` float32 ``[N,3]`` and ``batch_ids`` int32 ``[N]`` are taken as they are (a conversion would be a launch of
+    its own): anything else is a ValueError."""
+    lib = _lib.load()
+    f32, i32 = torch.float32, torch.int32
+    n_levels = len(cell_sizes)
+    if n_levels < 1:
+        raise ValueError("grid_levels_bounded: at least one level")
+    if not isinstance(pts, torch.Tensor) or pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("grid_levels_bounded: only [N,3] point sets are supported")
+    dev, n = pts.device, pts.shape[0]
+    p_pts = _ptr(pts, f32, "pts")
+    p_bid = _ptr(batch_ids, i32, "batch_ids", dev)
+    if tuple(batch_ids.shape) != (n,):
+        raise ValueError(f"grid_levels_bounded: batch_ids of shape {tuple(batch_ids.shape)} for {n} points")
+    if not all(c > 0 for c in cell_sizes):
+        raise ValueError("grid_levels_bounded: cell sizes must be positive")
+    if isinstance(capacities, str):
+        if capacities != "input":
+            raise ValueError(f"grid_levels_bounded: capacities {capacities!r}; expected 'input' or one row count per level")
+        capacities = [max(n, 1)] * n_levels
+    capacities = [int(c) for c in capacities]
+    if len(capacities) != n_levels or min(capacities) < 1:
+        raise ValueError("grid_levels_bounded: one capacity >= 1 per level")
+    if int(n_batches) < 1:
+        raise ValueError("grid_levels_bounded: n_batches must be at least 1")
+    p_valid = _ptr(n_valid, i32, "n_valid", dev)
+    if n_valid is not None and n_valid.numel() != 1:
+        raise ValueError("grid_levels_bounded: n_valid is one int32 word on the device")
+    rnd = [bool(r) for r in rnd] if rnd is not None else [False] * n_levels
+    rnd_values = list(rnd_values) if rnd_values is not None else [None] * n_levels
+    if len(rnd) != n_levels or len(rnd_values) != n_levels:
+        raise ValueError("grid_levels_bounded: rnd / rnd_values take one entry per level")
+    for l in range(n_levels):
+        u = rnd_values[l]
+        if u is not None:
+            _ptr(u, f32, f"rnd_values[{l}]", dev)
+            if not rnd[l] or tuple(u.shape) != (capacities[l],):
+                raise ValueError(f"grid_levels_bounded: rnd_values[{l}] takes [{capacities[l]}] numbers of a random level")
+    levels, structs, n_in = [], (_lib.Se3Level * n_levels)(), n
+    for l, cap in enumerate(capacities):
+        lv = {"cell_ids": _empty(n_in, dtype=i32, device=dev), "sorted_ids": _empty(n_in, dtype=i32, device=dev),
+              "cell_ends": _empty(cap, dtype=i32, device=dev), "pts": _empty((cap, 3), dtype=f32, device=dev),
+              "batch_ids": _empty(cap, dtype=i32, device=dev)}
+        if rnd[l]:
+            lv["u"] = rnd_values[l] if rnd_values[l] is not None else torch.rand(cap, device=dev)
+            lv["ids"], lv["picked"] = _empty(cap, dtype=i32, device=dev), _empty(cap, dtype=i32, device=dev)
+        s = structs[l]
+        s.cell_size, s.capacity = float(cell_sizes[l]), cap
+        for name in ("cell_ids", "sorted_ids", "cell_ends", "pts", "batch_ids", "u", "ids", "picked"):
+            setattr(s, name, lv[name].data_ptr() if name in lv else None)
+        levels.append(lv)
+        n_in = cap
+    # the level sizes, behind the caller's n_valid word when there is one: trim() reads them all with one copy
+    counts = _empty((n_levels + (n_valid is not None), 2), dtype=i32, device=dev)
+    info = counts[1:] if n_valid is not None else counts
+    ws = _workspace(lib.se3_grid_levels_workspace_bytes(n, int(n_batches), structs, n_levels), dev)
+    _lib.check(lib.se3_grid_levels(p_pts, p_bid, n, p_valid, int(n_batches), structs, n_levels,
+                                   C.c_void_p(info.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)),
+               "se3_grid_levels")
+    if n_valid is not None:
+        counts[0].copy_(n_valid.reshape(1).expand(2))
+    return BoundedLevels(levels, info, counts, n, n_valid is not None, (pts, batch_ids, n_valid, ws))
+
+
 def _rows2d(t):
     return t.reshape(t.shape[0], -1) if t.dim() != 2 else t
 

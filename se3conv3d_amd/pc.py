@@ -486,6 +486,25 @@ class GridSubSample(object):
         if self.rnd_sample_:
             self.ids_, self.picked_ = ops.grid_pick(self.cells_, p_rnd_values)
 
+    @classmethod
+    def from_cells(cls, p_pc_src, p_cell_size, p_cells, p_rnd_sample=False):
+        """The object the constructor builds, from ``ops.GridCells`` that exist already (one level of
+        ``ops.grid_levels_bounded(...).trim()``; a random level carries its ``ids`` / ``picked``)."""
+        self = cls.__new__(cls)
+        self.pc_src_ = p_pc_src
+        self.cell_size_ = p_cell_size
+        self.rnd_sample_ = bool(p_rnd_sample)
+        self.cells_ = p_cells
+        self.cell_ids_ = p_cells.cell_ids
+        self.sorted_ids_ = p_cells.sorted_ids
+        self.num_out_ = p_cells.n_cells
+        self.ids_ = None
+        if self.rnd_sample_:
+            if getattr(p_cells, "picked", None) is None:
+                raise ValueError("GridSubSample.from_cells: a random sub-sample needs the cells' ids / picked")
+            self.ids_, self.picked_ = p_cells.ids, p_cells.picked
+        return self
+
     def __subsample_tensor__(self, p_tensor, p_method="avg"):
         if self.rnd_sample_:
             return ops.RowsGather.apply(p_tensor, self.picked_)
@@ -522,22 +541,44 @@ def _make_sub_sample(p_point_cloud, p_samp_method, p_id, **kwargs):
 
 
 class PointHierarchy(object):
-    def __init__(self, p_point_cloud, p_num_sub_samples, p_subsample_method="grid_avg", **kwargs):
+    """``p_capacities`` (extension): None builds level after level, each with its own read-back of the level size.
+    ``"input"`` or one row count per level builds ALL levels with one library call into buffers of those sizes
+    (``ops.grid_levels_bounded``; ``"input"``: the row count of level 0, which cannot overflow) and reads every level size
+    back with one copy; the clouds and sub-sample objects are the same, bit for bit.  ``ops.LevelOverflow`` when a level
+    does not fit.  Neighbourhoods and frames are built on the trimmed levels either way."""
+
+    def __init__(self, p_point_cloud, p_num_sub_samples, p_subsample_method="grid_avg", p_capacities=None, **kwargs):
         self.sub_sampled_objs_ = []
         self.pcs_ = [p_point_cloud]
         cur = p_point_cloud
-        for i in range(p_num_sub_samples):
-            new_pc, samp = self.__create_sub_sample__(cur, p_subsample_method, i, **kwargs)
-            self.sub_sampled_objs_.append(samp)
-            self.pcs_.append(new_pc)
-            cur = new_pc
+        if p_capacities is None:
+            for i in range(p_num_sub_samples):
+                new_pc, samp = self.__create_sub_sample__(cur, p_subsample_method, i, **kwargs)
+                self.sub_sampled_objs_.append(samp)
+                self.pcs_.append(new_pc)
+                cur = new_pc
+        elif p_num_sub_samples > 0:
+            if p_subsample_method not in ("grid_avg", "grid_rnd"):
+                _make_sub_sample(p_point_cloud, p_subsample_method, 0, **kwargs)  # (raises: the methods' one error text)
+            rnd = p_subsample_method == "grid_rnd"
+            radii = [kwargs["grid_radii"][i] for i in range(p_num_sub_samples)]
+            levels = ops.grid_levels_bounded(ops._as(cur.pts_, torch.float32), ops._as(cur.batch_ids_, torch.int32), radii,
+                                             p_capacities, cur.num_batches(), rnd=[rnd] * p_num_sub_samples).trim()
+            for i, cells in enumerate(levels):
+                samp = GridSubSample.from_cells(cur, radii[i], cells, rnd)
+                cur = self.__level_cloud__(cur, samp)
+                self.sub_sampled_objs_.append(samp)
+                self.pcs_.append(cur)
         self.neigh_cache_ = {}
 
     def __create_sub_sample__(self, p_point_cloud, p_samp_method, p_id, **kwargs):
         samp = _make_sub_sample(p_point_cloud, p_samp_method, p_id, **kwargs)
-        new_pts = samp.__subsample_tensor__(p_point_cloud.pts_, "avg")
-        new_bid = samp.__subsample_tensor__(p_point_cloud.batch_ids_, "max")
-        return Pointcloud(new_pts, new_bid, num_batches=_batches_of(p_point_cloud)), samp
+        return self.__level_cloud__(p_point_cloud, samp), samp
+
+    def __level_cloud__(self, p_point_cloud, p_samp):
+        new_pts = p_samp.__subsample_tensor__(p_point_cloud.pts_, "avg")
+        new_bid = p_samp.__subsample_tensor__(p_point_cloud.batch_ids_, "max")
+        return Pointcloud(new_pts, new_bid, num_batches=_batches_of(p_point_cloud))
 
     def create_neighborhood(self, p_pc_src_id, p_pc_dest_id, p_neigh_method, **kwargs):
         """Memoised per (source level, destination level, method + its parameter), pc/PointHierarchy.py:60-79 (the k-NN
@@ -574,9 +615,8 @@ class PointHierarchy(object):
 class PointHierarchyRotEquiv(PointHierarchy):
     """Every level gets its own freshly sampled frames (pc/PointHierarchyRotEquiv.py:31-44)."""
 
-    def __create_sub_sample__(self, p_point_cloud, p_samp_method, p_id, **kwargs):
-        samp = _make_sub_sample(p_point_cloud, p_samp_method, p_id, **kwargs)
-        new_pts = samp.__subsample_tensor__(p_point_cloud.pts_, "avg")
-        new_bid = samp.__subsample_tensor__(p_point_cloud.batch_ids_, "max")
+    def __level_cloud__(self, p_point_cloud, p_samp):
+        new_pts = p_samp.__subsample_tensor__(p_point_cloud.pts_, "avg")
+        new_bid = p_samp.__subsample_tensor__(p_point_cloud.batch_ids_, "max")
         return PointcloudRotEquiv(new_pts, new_bid, p_point_cloud.local_frames_config_,
-                                  num_batches=_batches_of(p_point_cloud)), samp
+                                  num_batches=_batches_of(p_point_cloud))

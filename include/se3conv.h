@@ -423,8 +423,10 @@ int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, const float*
  *     covariance of the k neighbours (missing ones = the point itself), symmetric 3x3 eigen-decomposition,
  *     right-handed orientation fix and the sign-flipped copies.  axis_fixed < 0: frames [n,4,9] (eigenvalues
  *     ascending, column c scaled by the patterns (1,1,1),(1,-1,-1),(-1,1,-1),(-1,-1,1)); axis_fixed = 1 or 2:
- *     frames [n,2,9] (that coordinate zeroed, eigenvalues descending, patterns (1,1,1),(-1,-1,1), the fixed axis
- *     as +e_axis -- its sign is implementation-defined in the reference's LAPACK call).
+ *     frames [n,2,9] (that coordinate zeroed, in-plane eigenvalues descending, patterns (1,1,1),(-1,-1,1), the fixed
+ *     axis as +e_axis for every point, degenerate neighbourhoods included -- its sign and, on degenerate input, its
+ *     column are implementation-defined in the reference's LAPACK call; in-plane axes of a neighbourhood without
+ *     in-plane extent are e of the remaining coordinates in a fixed order).
  * ------------------------------------------------------------------------------------------- */
 int se3_knn_query(const float* pts, const int32_t* batch_ids, int64_t n, int32_t k, int32_t* out,
                   void* stream);

@@ -184,6 +184,15 @@ __global__ void pca_frames_kernel(const float* __restrict__ pts, const int32_t* 
       if (ev[ord[t]] > ev[ord[t + 1]]) { const int tmp = ord[t]; ord[t] = ord[t + 1]; ord[t + 1] = tmp; }
   float f[3][3];  // columns = frame axes
   const bool fixed = axis_fixed >= 0;
+  if (fixed) {
+    // the up axis is not found by sorting: row and column axis_fixed of the covariance are exactly 0, jacobi3 skips every
+    // pair with that index, so v[:, axis_fixed] is exactly e_axis -- also where an in-plane eigenvalue is 0 or came out
+    // slightly negative (one point, duplicates, collinear neighbours).  Only the in-plane pair is ordered (the larger
+    // eigenvalue last here, first after the flip below; equal ones as the sort above leaves them: q last).
+    const int q = axis_fixed == 2 ? 1 : 2;  // the in-plane indices are 0 and q (axis_fixed is 1 or 2)
+    const bool p_larger = ev[0] > (q == 1 ? ev[1] : ev[2]);
+    ord[0] = axis_fixed, ord[1] = p_larger ? q : 0, ord[2] = p_larger ? 0 : q;
+  }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int src = fixed ? ord[2 - c] : ord[c];

@@ -132,6 +132,12 @@ LEVEL_SIGNATURES = {
     "se3_grid_levels": (C.c_int, [_P, _P, _I64, _P, _I32, _LVL, _I32, _P, _P, _SZ, _P]),
 }
 
+# the host-only query of the kernel forms a call takes, declared in include/se3conv_forms.h (an addition inside ABI version 6
+# as well); must list every symbol that header declares
+FORMS_SIGNATURES = {
+    "se3conv_forms": (C.c_int, [_SHP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _SZ]),
+}
+
 _lib = None
 
 
@@ -149,7 +155,7 @@ def load() -> C.CDLL:
     if lib.se3_abi_version() != ABI_VERSION:  # (checked before the symbols: an older library lacks some of them)
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
-    for name, (res, args) in list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items()) + list(FORMS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so
@@ -165,3 +171,13 @@ def check(code: int, what: str) -> None:
     if code != SE3_OK:
         msg = load().se3_error_string(code).decode()
         raise Se3LibraryError(f"{what} failed with code {code}: {msg}")
+
+
+def forms(shape: Se3Shape, backward: bool, want_feat: bool = True, want_params: bool = True, have_t: bool = False,
+          cu_count: int = 256) -> list:
+    """The "stage:form" lines of se3conv_forms (include/se3conv_forms.h): which kernel form every launch of a forward call
+    (`have_t`: it keeps T) or of a backward call with that request would take.  Host only."""
+    buf = C.create_string_buffer(4096)
+    check(load().se3conv_forms(C.byref(shape), int(backward), int(want_feat), int(want_params), int(have_t), cu_count, buf,
+                               len(buf)), "se3conv_forms")
+    return buf.value.decode().split()

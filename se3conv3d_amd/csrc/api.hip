@@ -1,4 +1,6 @@
 // extern "C" entry points of the fused operator + the API-parity ops (see include/se3conv.h).
+#include <cstdarg>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -8,8 +10,29 @@
 #include <vector>
 
 #include "common.h"
+#include "../../include/se3conv_forms.h"
 
 namespace se3 {
+
+// ---- the forms query (common.h): while `t_forms` is set on a thread the entry points launch nothing and the launchers
+// report which form they chose ---------------------------------------------------------------------------------------------
+namespace {
+struct FormSink { std::string lines, tag; int n_cu; };
+thread_local FormSink* t_forms = nullptr;
+}  // namespace
+bool forms_only() { return t_forms != nullptr; }
+int forms_cu_count() { return t_forms ? t_forms->n_cu : 0; }
+int form_report(const char* tag, const char* fmt, ...) {  // tag == nullptr: a launch inside the stage reported last
+  if (!t_forms) return SE3_OK;
+  if (tag) t_forms->tag = tag;
+  char name[160];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(name, sizeof(name), fmt, ap);
+  va_end(ap);
+  t_forms->lines += t_forms->tag + ":" + name + "\n";
+  return SE3_OK;
+}
 
 namespace {
 
@@ -664,6 +687,10 @@ extern "C" int se3conv_fwd(const float* pts_in, const float* pts_out, const floa
                               rho, nu, s, out, t_save, workspace, workspace_bytes, stream_, nullptr);
 }
 
+// NOTE for whoever adds a device call to se3conv_fwd_prepared / se3conv_bwd_prepared or to a launcher below them: the
+// se3conv_forms query (end of this file) runs these very functions with dummy pointers while forms_only() is true.  Every
+// launch, event, memset or runtime query on that path must sit behind `if (!forms_only())` (or inside a launcher, after its
+// form_report); pointers derived from the workspace may be computed but never dereferenced on the host.
 extern "C" int se3conv_fwd_prepared(const float* pts_in, const float* pts_out, const float* frames_in, const float* frames_out,
                                     const int32_t* neighbors, const int32_t* ends, const float* feat, const float* proj_axes,
                                     const float* proj_biases, const float* conv_weights, const float* rho, const float* nu,
@@ -683,13 +710,14 @@ extern "C" int se3conv_fwd_prepared(const float* pts_in, const float* pts_out, c
     float *a32 = (float*)(ws + l.a32), *b32 = (float*)(ws + l.b32), *w32 = (float*)(ws + l.w32);
     for (int sl = 0; sl < l.slices; ++sl) {
       const int k0 = sl * kBasis, kn = s->num_basis - k0 < kBasis ? s->num_basis - k0 : kBasis;
-      hipLaunchKernelGGL(slice_params_kernel, dim3(grid_for(slice_items(s))), dim3(256), 0, stream,
-                         proj_axes, proj_biases, conv_weights, s->num_basis, k0, kn, s->c_in, s->c_out, a32, b32, w32);
+      if (!forms_only())
+        hipLaunchKernelGGL(slice_params_kernel, dim3(grid_for(slice_items(s))), dim3(256), 0, stream,
+                           proj_axes, proj_biases, conv_weights, s->num_basis, k0, kn, s->c_in, s->c_out, a32, b32, w32);
       float* dst = sl == 0 ? out : (float*)(ws + l.out_tmp);
       if (int rc = se3conv_fwd(pts_in, pts_out, frames_in, frames_out, neighbors, ends, feat, a32, b32, w32, rho, nu, &s32, dst,
                                nullptr, ws + l.inner, l.total - l.inner, stream_))
         return rc;
-      if (sl > 0)
+      if (sl > 0 && !forms_only())
         hipLaunchKernelGGL(add_into_kernel, dim3(grid_for(n_out_el)), dim3(256), 0, stream, out, dst, n_out_el);
     }
     return check_launch();
@@ -789,12 +817,14 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
     const dim3 pgrid(grid_for(slice_items(s)));
     for (int sl = 0; sl < l.slices; ++sl) {
       const int k0 = sl * kBasis, kn = s->num_basis - k0 < kBasis ? s->num_basis - k0 : kBasis;
-      hipLaunchKernelGGL(slice_params_kernel, pgrid, dim3(256), 0, stream, proj_axes, proj_biases, conv_weights,
-                         s->num_basis, k0, kn, s->c_in, s->c_out, a32, b32, w32);
+      if (!forms_only())
+        hipLaunchKernelGGL(slice_params_kernel, pgrid, dim3(256), 0, stream, proj_axes, proj_biases, conv_weights,
+                           s->num_basis, k0, kn, s->c_in, s->c_out, a32, b32, w32);
       float* dx = !wf ? nullptr : (sl == 0 ? grad_feat : (float*)(ws + l.out_tmp));
       if (int rc = se3conv_bwd(pts_in, pts_out, frames_in, frames_out, neighbors, ends, t_samples, t_ends, t_edge_ids, feat, a32, b32, w32, rho,
                                nu, nullptr, grad_out, &s32, dx, da32, db32, dw32, ws + l.inner, l.total - l.inner, stream_))
         return rc;
+      if (forms_only()) continue;
       if (wf && sl > 0 && n_in_el > 0)
         hipLaunchKernelGGL(add_into_kernel, dim3(grid_for(n_in_el)), dim3(256), 0, stream, grad_feat, dx, n_in_el);
       if (wp)
@@ -838,16 +868,18 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
     if (want_params) {
       // gT[m,(i,k)] = alpha * sum_o g[m,o] W[i,k,o]
       float* wt = (float*)(ws + p.wt);
-      hipLaunchKernelGGL(transpose_kernel, dim3(grid_for((int64_t)ck * s->c_out)), dim3(256), 0, stream, conv_weights,
-                         wt, ck, s->c_out);
+      if (!forms_only())
+        hipLaunchKernelGGL(transpose_kernel, dim3(grid_for((int64_t)ck * s->c_out)), dim3(256), 0, stream, conv_weights,
+                           wt, ck, s->c_out);
       if (int rc = launch_gemm_nn("gemm_gradT", grad_out, wt, big, rows_out, ck, s->c_out, nu, inv_fin, stream)) return rc;
       if (grad_axes || grad_biases) {
         int n_part = 0;
         if (int rc = launch_edge_param_grad("edge_param_grad", g, feat, s->c_in, rows_in, axes_ext, rho, big, partials,
                                             p.n_param_partials, &n_part, stream))
           return rc;
-        hipLaunchKernelGGL(reduce_param_partials_kernel, dim3(kDescExt * kBasis), dim3(256), 0, stream, partials,
-                           n_part, grad_axes, grad_biases, 1.0f);
+        if (!forms_only())
+          hipLaunchKernelGGL(reduce_param_partials_kernel, dim3(kDescExt * kBasis), dim3(256), 0, stream, partials,
+                             n_part, grad_axes, grad_biases, 1.0f);
       }
       if (grad_weights) {
         const float* t = t_save;
@@ -868,8 +900,9 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
       float* u = (float*)(ws + p.u);
       if (int rc = launch_edge_t("edge_t_transposed", gt, grad_out, s->c_out, rows_out, axes_ext, rho, u, stream)) return rc;
       float* w2 = (float*)(ws + p.w2);
-      hipLaunchKernelGGL(permute_weights_oki_kernel, dim3(grid_for((int64_t)ck * s->c_out)), dim3(256), 0, stream,
-                         conv_weights, w2, s->c_in, kb, s->c_out);
+      if (!forms_only())
+        hipLaunchKernelGGL(permute_weights_oki_kernel, dim3(grid_for((int64_t)ck * s->c_out)), dim3(256), 0, stream,
+                           conv_weights, w2, s->c_in, kb, s->c_out);
       if (int rc = launch_gemm_nn("gemm_gradX", u, w2, grad_feat, rows_in, s->c_in, s->c_out * kb, nu, inv_fin, stream,
                                   (float*)(ws + p.split_x)))
         return rc;
@@ -957,6 +990,31 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
   return final_sums.launch(stream);
 }
 
+// Host only: the call itself with every launch replaced by its launcher's report (common.h: forms_only).  The pointers are
+// one dummy address nobody dereferences; the workspace check is passed by claiming all of it.
+extern "C" int se3conv_forms(const se3conv_shape* s, int pass, int want_feat, int want_params, int have_t, int cu_count, char* buf,
+                             size_t len) {
+  if (!shape_ok(s) || !buf || len == 0 || cu_count < 1 || (pass != SE3_PASS_FWD && pass != SE3_PASS_BWD)) return SE3_ERR_INVALID_ARGUMENT;
+  alignas(256) static char dummy[256];
+  float* const f = reinterpret_cast<float*>(dummy);
+  int32_t* const i = reinterpret_cast<int32_t*>(dummy);
+  FormSink sink;
+  sink.n_cu = cu_count;
+  t_forms = &sink;
+  int rc;
+  if (pass == SE3_PASS_FWD)
+    rc = se3conv_fwd_prepared(f, f, f, f, i, i, f, f, f, f, f, f, s, f, have_t ? f : nullptr, dummy, SIZE_MAX, nullptr, nullptr);
+  else
+    rc = se3conv_bwd_prepared(f, f, f, f, i, i, i, i, i, f, f, f, f, f, f, have_t ? f : nullptr, f, s, want_feat ? f : nullptr,
+                              want_params ? f : nullptr, want_params ? f : nullptr, want_params ? f : nullptr, dummy, SIZE_MAX,
+                              nullptr, nullptr);
+  t_forms = nullptr;
+  if (rc != SE3_OK) return rc;
+  if (sink.lines.size() + 1 > len) return SE3_ERR_WORKSPACE;
+  std::memcpy(buf, sink.lines.c_str(), sink.lines.size() + 1);
+  return SE3_OK;
+}
+
 // ---- optional per-kernel timing ------------------------------------------------------------------
 
 namespace se3 {
@@ -984,7 +1042,7 @@ void prof_drain_locked() {
 }  // namespace
 
 void prof_begin(const char* tag, hipStream_t stream) {
-  if (!g_prof_on) return;
+  if (!g_prof_on || forms_only()) return;
   std::lock_guard<std::mutex> lk(g_prof_mu);
   ProfRec r;
   r.tag = tag;
@@ -995,7 +1053,7 @@ void prof_begin(const char* tag, hipStream_t stream) {
 }
 
 void prof_end(hipStream_t stream) {
-  if (!g_prof_on) return;
+  if (!g_prof_on || forms_only()) return;
   std::lock_guard<std::mutex> lk(g_prof_mu);
   if (g_prof_open) (void)hipEventRecord(g_prof_open->stop, stream);
   g_prof_open = nullptr;

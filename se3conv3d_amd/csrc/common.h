@@ -377,9 +377,25 @@ __device__ __forceinline__ void rotate_priority(int step_plus_slot) {
 }
 __device__ __forceinline__ int wave_slot_id() { return (int)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (3 << 11)) ; }  // HW_ID[3:0]
 
+// ---- which kernel form a launch takes (se3conv_forms, include/se3conv_forms.h) ---------------------------------------------
+// Every launcher that chooses between instantiations has ONE decision function (`*_form`): a pure function of the shape
+// it is given that returns the chosen form as a small struct, and the launcher switches on that value.  While a
+// se3conv_forms query runs on the calling thread (api.hip) the entry points walk their ordinary stage sequence, the
+// launchers decide as always, report "stage:form" and launch nothing: the query has no conditions of its own.
+bool forms_only();                                         // a query is running on this thread: no device call of any kind
+int forms_cu_count();                                      // the CU count the query was given (resident grids are sized by it)
+int form_report(const char* tag, const char* fmt, ...) __attribute__((format(printf, 2, 3)));  // one line; returns SE3_OK
+
 inline int check_launch() {
+  if (forms_only()) return SE3_OK;
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SE3_OK : SE3_ERR_LAUNCH;
+}
+// neighbour frame count as a shift (the kernels' POW2 / P2 forms), -1: not a power of two, the division forms
+inline int frame_shift(int f_nb) {
+  for (int sft = 0; sft < 8; ++sft)
+    if ((1 << sft) == f_nb) return sft;
+  return -1;
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

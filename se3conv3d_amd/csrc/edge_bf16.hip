@@ -1406,6 +1406,7 @@ static int edge_stream_min_items() {
 }
 
 static int device_cu_count() {  // of the current device (the resident grids are sized by it); <= 0: the query failed
+  if (forms_only()) return forms_cu_count();
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0;
@@ -1416,208 +1417,278 @@ static int device_cu_count() {  // of the current device (the resident grids are
   return n_cu;
 }
 
-int launch_edge_t_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat, int channels, int64_t feat_rows,
-                       const float* axes_ext, const float* rho, uint32_t* t_out, hipStream_t stream, int rowfmt) {
-  const bool t24 = rowfmt == 1;
+// Which kernel, which instantiation and which grid an edge pass takes (launch_edge_t_bf16 switches on it).
+struct EdgeTBf16Form {
+  enum Kind { stream_pair, pair, stream1, single } kind;
+  int ct, nf;        // pair: channel tiles per wavefront (CT), centre frames per item (NF)
+  int vw, fc;        // single / stream1: channels per lane (VW), centre frames per item (FC)
+  bool full, p2, t24;  // FULL: whole channel passes; P2: power-of-two neighbour frame count (pair); T24: 3-byte rows (single)
+  int tr;            // pair: -1 without P2, else the graph's side (0 forward, 1 transposed); stream kernels: the side
+  int shift, rowfmt;
+  int64_t items, wgs;  // items of FC / NF centre frames; stream kernels: resident workgroups
+};
+static EdgeTBf16Form edge_t_bf16_form(const EdgeGeom& g, int channels, int rowfmt, int n_cu) {
+  EdgeTBf16Form f{};
   const int64_t rows = g.n_ctr * g.f_ctr;
-  if (rows == 0) return SE3_OK;
-  if (t24 && !edge_t_bf16_t24_rows(g, channels)) return SE3_ERR_UNSUPPORTED;
-  if (rowfmt == 2 && !edge_t_bf16_t16_rows(g, channels)) return SE3_ERR_UNSUPPORTED;
-  // 32-bit byte offsets into the gathered operand; kOobOffset must lie beyond it
-  if (feat_rows * (int64_t)channels * 4 >= (int64_t)kOobOffset) return SE3_ERR_UNSUPPORTED;
-  ProfScope prof(tag, stream);
+  f.rowfmt = rowfmt, f.shift = frame_shift(g.f_nb), f.tr = g.transposed ? 1 : 0;
+  const bool t24 = rowfmt == 1;
   // two frames per wavefront share the gather; with 4 channel tiles per frame that would spill, so VW = 4 stays at 1
-  const int fc = g.f_ctr % 2 == 0 && channels % 128 != 0 ? 2 : 1;
-  const int64_t items = rows / fc;
-  int shift = -1;
-  for (int sft = 0; sft < 8; ++sft)
-    if ((1 << sft) == g.f_nb) shift = sft;
-  const dim3 block(256);
+  f.fc = g.f_ctr % 2 == 0 && channels % 128 != 0 ? 2 : 1;
+  const bool reach = g.n_edges > 0 && g.n_edges * g.nbr_stride * 4 < (int64_t)kOobOffset;  // the stream kernels bounds-check ids
   if (edge_t_bf16_uses_pair(g, channels)) {
     // a 128-thread workgroup per two frames of a point (even F) or per single row (odd F)
     const bool two = g.f_ctr % 2 == 0;
-    const int64_t pair_items = two ? rows / 2 : rows;
+    f.nf = two ? 2 : 1, f.items = two ? rows / 2 : rows;
     // chunk-stream form (resident workgroups, the chunk pipeline running across item boundaries): 64-channel rows, two
     // frames per item, power-of-two neighbour frame count, 3-byte rows; SE3_EDGE_STREAM=0 keeps the one-item workgroups
-    if (channels == 64 && two && shift >= 0 && rowfmt == 1 && pair_items >= edge_stream_min_items() && g.n_edges > 0 &&
-        g.n_edges * g.nbr_stride * 4 < (int64_t)kOobOffset && pair_items < (1ll << 31)) {
-      const int n_cu = device_cu_count();
-      if (n_cu <= 0) return SE3_ERR_LAUNCH;
+    if (channels == 64 && two && f.shift >= 0 && rowfmt == 1 && f.items >= edge_stream_min_items() && reach && f.items < (1ll << 31)) {
       constexpr int per_cu = 2 * SE3_PAIR_WAVES;  // 18 KB of LDS and <= 128 VGPRs: eight two-wavefront workgroups per CU
-      int64_t wgs = (int64_t)n_cu * per_cu;  // resident workgroups only, whatever the level's size (windows of 64 items inside)
-      if (wgs > pair_items) wgs = pair_items;
-      const dim3 sgrid((unsigned)wgs), sblock(128);
-      if (g.transposed)
-        hipLaunchKernelGGL((edge_t_stream_bf16_kernel<1>), sgrid, sblock, 0, stream, g, feat, feat_rows, axes_ext, rho,
-                           reinterpret_cast<char*>(t_out), 0u, (uint32_t)pair_items, shift);
-      else
-        hipLaunchKernelGGL((edge_t_stream_bf16_kernel<0>), sgrid, sblock, 0, stream, g, feat, feat_rows, axes_ext, rho,
-                           reinterpret_cast<char*>(t_out), 0u, (uint32_t)pair_items, shift);
-      return check_launch();
+      f.kind = EdgeTBf16Form::stream_pair;
+      f.wgs = (int64_t)n_cu * per_cu;  // resident workgroups only, whatever the level's size (windows of 64 items inside)
+      if (f.wgs > f.items) f.wgs = f.items;
+      return f;
     }
-    const dim3 pgrid((unsigned)pair_items), pblock(128);
-#define SE3_PAIR_T(CT, FULL, NF, P2, TR)                                                                                \
-  hipLaunchKernelGGL((edge_t_pair_bf16_kernel<CT, FULL, NF, P2, TR>), pgrid, pblock, 0, stream, g, feat, channels, feat_rows, \
-                     axes_ext, rho, t_out, 0, pair_items, shift, rowfmt)
-#define SE3_PAIR_L(CT, FULL, NF, P2)                 \
-  do {                                               \
-    if (!(P2)) SE3_PAIR_T(CT, FULL, NF, P2, -1);     \
-    else if (g.transposed) SE3_PAIR_T(CT, FULL, NF, P2, 1); \
-    else SE3_PAIR_T(CT, FULL, NF, P2, 0);            \
-  } while (0)
-#define SE3_PAIR(CT, FULL)                                   \
-  do {                                                       \
-    if (two && shift >= 0) SE3_PAIR_L(CT, FULL, 2, true);    \
-    else if (two) SE3_PAIR_L(CT, FULL, 2, false);            \
-    else if (shift >= 0) SE3_PAIR_L(CT, FULL, 1, true);      \
-    else SE3_PAIR_L(CT, FULL, 1, false);                     \
-  } while (0)
-    if (channels == 64) SE3_PAIR(1, true);
-    else if (channels % 128 == 0) SE3_PAIR(2, true);
-    else SE3_PAIR(2, false);
-#undef SE3_PAIR
-#undef SE3_PAIR_L
-#undef SE3_PAIR_T
-    return check_launch();
+    f.kind = EdgeTBf16Form::pair;
+    f.ct = channels == 64 ? 1 : 2, f.full = channels == 64 || channels % 128 == 0;
+    f.p2 = f.shift >= 0;
+    if (!f.p2) f.tr = -1;
+    return f;
   }
+  f.items = rows / f.fc;
   // chunk-stream form of the single-wavefront kernel: rows of 32 channels, two frames per item.  Measured per form
   // (profiles/r06_edge_stream1_ab.txt): <1, 2> -8 % at two frames (items of ~2 chunks: dfaust_f2 0.191 -> 0.177 ms), -1 % at
   // four; <2, 1> (64-channel rows at one frame, the ScanNet scene: items of ONE chunk, so every chunk ends in its stores
   // and there is no pipeline to carry across) +1 %, and +6 % when squeezed to four wavefronts per SIMD (7 spilled
   // registers) -- those rows keep the one-item form.
-  if (t24 && shift >= 0 && channels == 32 && fc == 2 && items >= edge_stream_min_items() && g.n_edges > 0 &&
-      g.n_edges * g.nbr_stride * 4 < (int64_t)kOobOffset && items < (1ll << 31)) {
-    const int n_cu = device_cu_count();
-    if (n_cu <= 0) return SE3_ERR_LAUNCH;
+  if (t24 && f.shift >= 0 && channels == 32 && f.fc == 2 && f.items >= edge_stream_min_items() && reach && f.items < (1ll << 31)) {
     constexpr int per_cu = 3;  // = the kernel's launch bounds: resident workgroups only
-    int64_t wgs = (int64_t)n_cu * per_cu;
-    if (wgs > (items + 3) / 4) wgs = (items + 3) / 4;
-    const dim3 sgrid((unsigned)wgs);
-    if (g.transposed)
-      hipLaunchKernelGGL((edge_t_stream1_bf16_kernel<1, 2, 1>), sgrid, block, 0, stream, g, feat, feat_rows, axes_ext, rho,
-                         reinterpret_cast<char*>(t_out), 0u, (uint32_t)items, shift);
-    else
-      hipLaunchKernelGGL((edge_t_stream1_bf16_kernel<1, 2, 0>), sgrid, block, 0, stream, g, feat, feat_rows, axes_ext, rho,
-                         reinterpret_cast<char*>(t_out), 0u, (uint32_t)items, shift);
-    return check_launch();
+    f.kind = EdgeTBf16Form::stream1, f.vw = 1;
+    f.wgs = (int64_t)n_cu * per_cu;
+    if (f.wgs > (f.items + 3) / 4) f.wgs = (f.items + 3) / 4;
+    return f;
   }
-  const dim3 grid((unsigned)((items + 3) / 4));
+  f.kind = EdgeTBf16Form::single;
+  f.vw = channels % 128 == 0 ? 4 : channels % 64 == 0 ? 2 : 1;
+  f.full = channels % 32 == 0;
+  f.t24 = t24 && f.vw != 4;  // (rows of a multiple of 128 channels have no 3-byte form here: edge_t_bf16_t24_rows)
+  f.p2 = f.shift >= 0;
+  return f;
+}
+static int edge_t_bf16_form_report(const char* tag, const EdgeTBf16Form& f) {
+  switch (f.kind) {
+    case EdgeTBf16Form::stream_pair: return form_report(tag, "edge_t_stream_pair<tr=%d>", f.tr);
+    case EdgeTBf16Form::pair:
+      return form_report(tag, "edge_t_pair<ct=%d,full=%d,nf=%d,p2=%d,tr=%d>/fmt%d", f.ct, f.full, f.nf, f.p2, f.tr, f.rowfmt);
+    case EdgeTBf16Form::stream1: return form_report(tag, "edge_t_stream1<vw=1,fc=2,tr=%d>", f.tr);
+    default: return form_report(tag, "edge_t_single<vw=%d,fc=%d,full=%d,t24=%d>/p2=%d", f.vw, f.fc, f.full, f.t24, f.p2);
+  }
+}
+
+int launch_edge_t_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat, int channels, int64_t feat_rows,
+                       const float* axes_ext, const float* rho, uint32_t* t_out, hipStream_t stream, int rowfmt) {
+  const int64_t rows = g.n_ctr * g.f_ctr;
+  if (rows == 0) return SE3_OK;
+  if (rowfmt == 1 && !edge_t_bf16_t24_rows(g, channels)) return SE3_ERR_UNSUPPORTED;
+  if (rowfmt == 2 && !edge_t_bf16_t16_rows(g, channels)) return SE3_ERR_UNSUPPORTED;
+  // 32-bit byte offsets into the gathered operand; kOobOffset must lie beyond it
+  if (feat_rows * (int64_t)channels * 4 >= (int64_t)kOobOffset) return SE3_ERR_UNSUPPORTED;
+  const int n_cu = device_cu_count();
+  const EdgeTBf16Form f = edge_t_bf16_form(g, channels, rowfmt, n_cu);
+  const bool stream_form = f.kind == EdgeTBf16Form::stream_pair || f.kind == EdgeTBf16Form::stream1;
+  if (stream_form && n_cu <= 0) return SE3_ERR_LAUNCH;
+  if (forms_only()) return edge_t_bf16_form_report(tag, f);
+  ProfScope prof(tag, stream);
+  const int shift = f.shift;
+  const int64_t items = f.items;
+  const dim3 block(256);
+  switch (f.kind) {
+    case EdgeTBf16Form::stream_pair: {
+      const dim3 sgrid((unsigned)f.wgs), sblock(128);
+      if (f.tr)
+        hipLaunchKernelGGL((edge_t_stream_bf16_kernel<1>), sgrid, sblock, 0, stream, g, feat, feat_rows, axes_ext, rho,
+                           reinterpret_cast<char*>(t_out), 0u, (uint32_t)items, shift);
+      else
+        hipLaunchKernelGGL((edge_t_stream_bf16_kernel<0>), sgrid, sblock, 0, stream, g, feat, feat_rows, axes_ext, rho,
+                           reinterpret_cast<char*>(t_out), 0u, (uint32_t)items, shift);
+      break;
+    }
+    case EdgeTBf16Form::pair: {
+      const dim3 pgrid((unsigned)items), pblock(128);
+      const int64_t pair_items = items;
+#define SE3_PAIR_T(CT, FULL, NF, P2, TR)                                                                                \
+  if (f.ct == CT && f.full == FULL && f.nf == NF && f.p2 == P2 && f.tr == TR)                                             \
+    hipLaunchKernelGGL((edge_t_pair_bf16_kernel<CT, FULL, NF, P2, TR>), pgrid, pblock, 0, stream, g, feat, channels, feat_rows, \
+                       axes_ext, rho, t_out, 0, pair_items, shift, rowfmt)
+#define SE3_PAIR_L(CT, FULL, NF)                \
+  SE3_PAIR_T(CT, FULL, NF, false, -1);          \
+  else SE3_PAIR_T(CT, FULL, NF, true, 1);       \
+  else SE3_PAIR_T(CT, FULL, NF, true, 0)
+#define SE3_PAIR(CT, FULL)    \
+  SE3_PAIR_L(CT, FULL, 2);    \
+  else SE3_PAIR_L(CT, FULL, 1)
+      SE3_PAIR(1, true);
+      else SE3_PAIR(2, true);
+      else SE3_PAIR(2, false);
+      else return SE3_ERR_UNSUPPORTED;
+#undef SE3_PAIR
+#undef SE3_PAIR_L
+#undef SE3_PAIR_T
+      break;
+    }
+    case EdgeTBf16Form::stream1: {
+      const dim3 sgrid((unsigned)f.wgs);
+      if (f.tr)
+        hipLaunchKernelGGL((edge_t_stream1_bf16_kernel<1, 2, 1>), sgrid, block, 0, stream, g, feat, feat_rows, axes_ext, rho,
+                           reinterpret_cast<char*>(t_out), 0u, (uint32_t)items, shift);
+      else
+        hipLaunchKernelGGL((edge_t_stream1_bf16_kernel<1, 2, 0>), sgrid, block, 0, stream, g, feat, feat_rows, axes_ext, rho,
+                           reinterpret_cast<char*>(t_out), 0u, (uint32_t)items, shift);
+      break;
+    }
+    case EdgeTBf16Form::single: {
+      const dim3 grid((unsigned)((items + 3) / 4));
 #define SE3_LAUNCH(VW, FC, FULL, T24)                                                                                 \
-  hipLaunchKernelGGL((edge_t_bf16_kernel<VW, FC, FULL, T24>), grid, block, 0, stream, g, feat, channels, feat_rows,     \
-                     axes_ext, rho, t_out, items, shift, 0)
-#define SE3_LAUNCH_T(VW, FC, FULL)                   \
-  do {                                               \
-    if (t24) SE3_LAUNCH(VW, FC, FULL, true);         \
-    else SE3_LAUNCH(VW, FC, FULL, false);            \
-  } while (0)
-  if (channels % 128 == 0) {
-    SE3_LAUNCH(4, 1, true, false);
-  } else if (channels % 64 == 0) {
-    if (fc == 2) SE3_LAUNCH_T(2, 2, true); else SE3_LAUNCH_T(2, 1, true);
-  } else if (channels % 32 == 0) {
-    if (fc == 2) SE3_LAUNCH_T(1, 2, true); else SE3_LAUNCH_T(1, 1, true);
-  } else {
-    if (fc == 2) SE3_LAUNCH_T(1, 2, false); else SE3_LAUNCH_T(1, 1, false);
-  }
+  if (f.vw == VW && f.fc == FC && f.full == FULL && f.t24 == T24)                                                      \
+    hipLaunchKernelGGL((edge_t_bf16_kernel<VW, FC, FULL, T24>), grid, block, 0, stream, g, feat, channels, feat_rows,   \
+                       axes_ext, rho, t_out, items, shift, 0)
+#define SE3_LAUNCH_T(VW, FULL)              \
+  SE3_LAUNCH(VW, 2, FULL, true);            \
+  else SE3_LAUNCH(VW, 2, FULL, false);      \
+  else SE3_LAUNCH(VW, 1, FULL, true);       \
+  else SE3_LAUNCH(VW, 1, FULL, false)
+      SE3_LAUNCH(4, 1, true, false);
+      else SE3_LAUNCH_T(2, true);
+      else SE3_LAUNCH_T(1, true);
+      else SE3_LAUNCH_T(1, false);
+      else return SE3_ERR_UNSUPPORTED;
 #undef SE3_LAUNCH_T
 #undef SE3_LAUNCH
+      break;
+    }
+  }
   return check_launch();
 }
 
 // partials: room for n_partials x edge_param_grad_bf16_channel_blocks(channels) slots of 320 floats; *n_used = slots written
 int edge_param_grad_bf16_channel_blocks(int channels) { return channels > 64 && channels % 16 == 0 ? (channels + 63) / 64 : 1; }
 
-int launch_edge_param_grad_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat, int channels,
-                                int64_t feat_rows, const float* axes_ext, const float* rho, const uint32_t* grad_t,
-                                float* partials, int n_partials, int* n_used, hipStream_t stream) {
+// Which parameter-gradient kernel a shape takes, its instantiation and its grid (launch_edge_param_grad_bf16 switches on it).
+struct ParamGradBf16Form {
+  enum Kind { pair, wave, generic } kind;  // pair: two wavefronts share an item; wave: the 512- / 256-thread form
+  int ch16, nfr;     // 16-channel k-steps per channel block (CH16), frames per wavefront (NFR)
+  bool p2;
+  int shift, pipe, blocks_y;
+  int64_t items, wgs;  // wgs: workgroups of grid.x
+};
+static ParamGradBf16Form edge_param_grad_bf16_form(const EdgeGeom& g, int channels, int n_partials, int n_cu) {
+  ParamGradBf16Form f{};
   const int64_t rows = g.n_ctr * g.f_ctr;
-  if (feat_rows * (int64_t)channels * 4 >= (int64_t)kOobOffset) return SE3_ERR_UNSUPPORTED;
-  ProfScope prof(tag, stream);
-  *n_used = n_partials;
+  f.shift = frame_shift(g.f_nb), f.p2 = f.shift >= 0, f.blocks_y = 1;
   // Rows of fewer than 16 channels (the networks' first layers: C_in = 1 for DFaust, 3 for ScanNet colours) take the MFMA
   // form with one k-step too (round 6): a lane's eight feature words then run past its own row into the next rows', and meet
   // grad_T fragments that are zero there (the row's buffer ends behind its channels: out-of-range loads return 0), so
   // gphi = f . gT is exact -- 0.153 -> see profiles/r06_faust_network_convs.txt for call 00 -- instead of the generic kernel's
   // scalar loads and VALU outer products.
-  if (channels > 0 && (channels % 16 == 0 || channels < 16)) {
-    int shift = -1;
-    for (int sft = 0; sft < 8; ++sft)
-      if ((1 << sft) == g.f_nb) shift = sft;
-    // two frames per wavefront share the gather (2 waves/SIMD: 16 KB of gT fragments per wavefront); one row per
-    // wavefront (odd F, or SE3_PG_SINGLE for any F) gathers each neighbour row once per centre frame but runs at 3
-    static const bool force_single = getenv("SE3_PG_SINGLE") != nullptr;
-    const bool two = g.f_ctr % 2 == 0 && !force_single;
-    const int64_t items = two ? rows / 2 : rows;
-    if (items <= 0) {
-      *n_used = 0;
-      return SE3_OK;
-    }
-    const int blocks_y = edge_param_grad_bf16_channel_blocks(channels);
-    // pair form (two wavefronts share an item and its grad_T image, 3 wavefronts per SIMD).  32-channel rows (DFaust's
-    // first level) take it too, with half the grad_T image (CH16 = 2): 0.258 against 0.284 ms for the 512-thread form on
-    // the DFaust F = 2 batch (profiles/r03_c32_pair_forms_ab.txt).  (The same idea for the edge_t kernel -- a split-K wave
-    // pair for 32-channel rows -- measured 7-10 % SLOWER than the single-wavefront kernel and is not kept, same file.)
-    if (two && (channels >= 64 || channels == 32)) {
-      const int n_cu = device_cu_count();
-      if (n_cu <= 0) return SE3_ERR_LAUNCH;
-      constexpr int per_cu = 6;  // 26 KB of LDS per workgroup
-      int64_t wgs = (int64_t)n_cu * per_cu;
-      // extents in lane registers (pipe) where a resident workgroup walks at most 64 items; the per-item extent loads
-      // otherwise -- never more workgroups than the chip holds at once for the registers' sake: 3 450 workgroups of 64 items
-      // on dfaust_f4's level 0 ran as 2.25 rounds of 1 536 and took 1.52 instead of 1.23 ms, and the extent loads were never
-      // what the kernel waited on (profiles/r06_param_grad_pipeline_ab.txt)
-      if (wgs > n_partials) wgs = n_partials;
-      if (wgs > items) wgs = items;
-      if (wgs < 1) wgs = 1;
-      const int pipe = (items + wgs - 1) / wgs <= 64 && items < (1ll << 31) ? 1 : 0;
-      *n_used = (int)wgs * blocks_y;
-      const dim3 pgrid((unsigned)wgs, (unsigned)blocks_y);
-      if (channels == 32 && shift >= 0)
-        hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<2, 2, true, true>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe);
-      else if (channels == 32)
-        hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<2, 2, true, false>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe);
-      else if (shift >= 0)
-        hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<4, 2, true, true>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe);
-      else
-        hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<4, 2, true, false>), pgrid, dim3(128), 0, stream, g, feat, channels,
-                           feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe);
-      return check_launch();
-    }
-    const int n_blocks = n_partials < 512 ? n_partials : 512;  // the 512-thread form: one workgroup per CU and round
-    *n_used = n_blocks * blocks_y;
-    const dim3 grid((unsigned)n_blocks, (unsigned)blocks_y);
+  if (!(channels > 0 && (channels % 16 == 0 || channels < 16))) {
+    f.kind = ParamGradBf16Form::generic, f.items = rows;
+    f.wgs = n_partials < 512 ? n_partials : 512;  // generic fallback: two workgroups per CU, as the fp32 kernel
+    return f;
+  }
+  // two frames per wavefront share the gather (2 waves/SIMD: 16 KB of gT fragments per wavefront); one row per
+  // wavefront (odd F, or SE3_PG_SINGLE for any F) gathers each neighbour row once per centre frame but runs at 3
+  static const bool force_single = getenv("SE3_PG_SINGLE") != nullptr;
+  const bool two = g.f_ctr % 2 == 0 && !force_single;
+  f.items = two ? rows / 2 : rows;
+  f.blocks_y = edge_param_grad_bf16_channel_blocks(channels);
+  // pair form (two wavefronts share an item and its grad_T image, 3 wavefronts per SIMD).  32-channel rows (DFaust's
+  // first level) take it too, with half the grad_T image (CH16 = 2): 0.258 against 0.284 ms for the 512-thread form on
+  // the DFaust F = 2 batch (profiles/r03_c32_pair_forms_ab.txt).  (The same idea for the edge_t kernel -- a split-K wave
+  // pair for 32-channel rows -- measured 7-10 % SLOWER than the single-wavefront kernel and is not kept, same file.)
+  if (two && (channels >= 64 || channels == 32)) {
+    constexpr int per_cu = 6;  // 26 KB of LDS per workgroup
+    f.kind = ParamGradBf16Form::pair, f.ch16 = channels == 32 ? 2 : 4, f.nfr = 2;
+    f.wgs = (int64_t)n_cu * per_cu;
+    // extents in lane registers (pipe) where a resident workgroup walks at most 64 items; the per-item extent loads
+    // otherwise -- never more workgroups than the chip holds at once for the registers' sake: 3 450 workgroups of 64 items
+    // on dfaust_f4's level 0 ran as 2.25 rounds of 1 536 and took 1.52 instead of 1.23 ms, and the extent loads were never
+    // what the kernel waited on (profiles/r06_param_grad_pipeline_ab.txt)
+    if (f.wgs > n_partials) f.wgs = n_partials;
+    if (f.wgs > f.items) f.wgs = f.items;
+    if (f.wgs < 1) f.wgs = 1;
+    f.pipe = (f.items + f.wgs - 1) / f.wgs <= 64 && f.items < (1ll << 31) ? 1 : 0;
+    return f;
+  }
+  // (two frames of 32 and of >= 64 channels took the pair form above: those widths have one-frame forms only)
+  f.kind = ParamGradBf16Form::wave;
+  f.ch16 = channels >= 64 ? 4 : (channels + 15) / 16;
+  f.nfr = two ? 2 : 1;
+  f.wgs = n_partials < 512 ? n_partials : 512;  // the 512-thread form: one workgroup per CU and round
+  return f;
+}
+
+int launch_edge_param_grad_bf16(const char* tag, const EdgeGeom& g, const uint32_t* feat, int channels,
+                                int64_t feat_rows, const float* axes_ext, const float* rho, const uint32_t* grad_t,
+                                float* partials, int n_partials, int* n_used, hipStream_t stream) {
+  const int64_t rows = g.n_ctr * g.f_ctr;
+  if (feat_rows * (int64_t)channels * 4 >= (int64_t)kOobOffset) return SE3_ERR_UNSUPPORTED;
+  const int n_cu = device_cu_count();
+  const ParamGradBf16Form f = edge_param_grad_bf16_form(g, channels, n_partials, n_cu);
+  if (f.kind != ParamGradBf16Form::generic && f.items <= 0) {
+    *n_used = 0;
+    return SE3_OK;
+  }
+  if (f.kind == ParamGradBf16Form::pair && n_cu <= 0) return SE3_ERR_LAUNCH;
+  *n_used = (int)f.wgs * f.blocks_y;
+  if (forms_only()) {
+    if (f.kind == ParamGradBf16Form::pair)
+      return form_report(tag, "param_grad_pair<ch16=%d,p2=%d>/%s/y%d", f.ch16, f.p2, f.pipe ? "pipe" : "loop", f.blocks_y);
+    if (f.kind == ParamGradBf16Form::wave)
+      return form_report(tag, "param_grad<ch16=%d,nfr=%d,p2=%d>/y%d", f.ch16, f.nfr, f.p2, f.blocks_y);
+    return form_report(tag, "param_grad_generic");
+  }
+  ProfScope prof(tag, stream);
+  const int64_t items = f.items;
+  const int shift = f.shift, pipe = f.pipe;
+  const dim3 grid((unsigned)f.wgs, (unsigned)f.blocks_y);
+  switch (f.kind) {
+    case ParamGradBf16Form::pair:
+#define SE3_PG_PAIR(CH16, P2)                                                                                                 \
+  if (f.ch16 == CH16 && f.p2 == P2)                                                                                             \
+    hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<CH16, 2, true, P2>), grid, dim3(128), 0, stream, g, feat, channels,      \
+                       feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0, pipe)
+      SE3_PG_PAIR(2, true);
+      else SE3_PG_PAIR(2, false);
+      else SE3_PG_PAIR(4, true);
+      else SE3_PG_PAIR(4, false);
+      else return SE3_ERR_UNSUPPORTED;
+#undef SE3_PG_PAIR
+      break;
+    case ParamGradBf16Form::wave:
 #define SE3_PG_L(CH16, NFR, P2, THREADS)                                                                                  \
-  hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<CH16, NFR, false, P2>), grid, dim3(THREADS), 0, stream, g, feat, channels, \
-                     feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0)
-#define SE3_PG1(CH16)                                      \
-  do {                                                     \
-    if (shift >= 0) SE3_PG_L(CH16, 1, true, 256);          \
-    else SE3_PG_L(CH16, 1, false, 256);                    \
-  } while (0)
-#define SE3_PG(CH16)                                       \
-  do {                                                     \
-    if (two && shift >= 0) SE3_PG_L(CH16, 2, true, 512);   \
-    else if (two) SE3_PG_L(CH16, 2, false, 512);           \
-    else SE3_PG1(CH16);                                    \
-  } while (0)
-    // (two frames of 32 and of >= 64 channels took the pair form above: those widths have one-frame forms only)
-    switch (channels >= 64 ? 4 : (channels + 15) / 16) {
-      case 1: SE3_PG(1); break;
-      case 2: SE3_PG1(2); break;
-      case 3: SE3_PG(3); break;
-      default: SE3_PG1(4); break;
-    }
+  if (f.ch16 == CH16 && f.nfr == NFR && f.p2 == P2)                                                                         \
+    hipLaunchKernelGGL((edge_param_grad_bf16_v2_kernel<CH16, NFR, false, P2>), grid, dim3(THREADS), 0, stream, g, feat, channels, \
+                       feat_rows, axes_ext, rho, grad_t, partials, items, shift, 0)
+#define SE3_PG1(CH16)                   \
+  SE3_PG_L(CH16, 1, true, 256);         \
+  else SE3_PG_L(CH16, 1, false, 256)
+#define SE3_PG(CH16)                    \
+  SE3_PG_L(CH16, 2, true, 512);         \
+  else SE3_PG_L(CH16, 2, false, 512);   \
+  else SE3_PG1(CH16)
+      SE3_PG(1);
+      else SE3_PG1(2);
+      else SE3_PG(3);
+      else SE3_PG1(4);
+      else return SE3_ERR_UNSUPPORTED;
 #undef SE3_PG
 #undef SE3_PG1
 #undef SE3_PG_L
-    return check_launch();
+      break;
+    case ParamGradBf16Form::generic:
+      hipLaunchKernelGGL(edge_param_grad_bf16_kernel, dim3((unsigned)f.wgs), dim3(256), 0, stream, g, feat, channels, axes_ext,
+                         rho, grad_t, partials, rows);
+      break;
   }
-  *n_used = n_partials < 512 ? n_partials : 512;  // generic fallback: two workgroups per CU, as the fp32 kernel
-  hipLaunchKernelGGL(edge_param_grad_bf16_kernel, dim3(*n_used), dim3(256), 0, stream, g, feat, channels, axes_ext,
-                     rho, grad_t, partials, rows);
   return check_launch();
 }
 

@@ -248,28 +248,36 @@ bool edge_dx_bf16_applicable(const EdgeGeom& g, int channels) {
   return g.f_ctr % 2 == 0 && (channels == 32 || (channels % 64 == 0 && channels > 0)) && g.f_nb * channels <= 512;
 }
 
+// Which instantiation of edge_dx_bf16_kernel a shape takes: channel tiles per workgroup (CT) and whether the neighbour
+// frame count is a power of two (P2)
+struct EdgeDxForm { int ct, shift; };
+static EdgeDxForm edge_dx_form(const EdgeGeom& g, int channels) { return {channels == 32 ? 1 : 2, frame_shift(g.f_nb)}; }
+
 // grad_t: packed words [rows_out, channels, 32] (the grad_T GEMM's output, alpha folded in); d_rows: [edge rows * f_nb, channels]
 int launch_edge_dx_bf16(const char* tag, const EdgeGeom& g, const float* axes_ext, const float* rho, const uint32_t* grad_t,
                         int channels, float* d_rows, hipStream_t stream) {
   if (!edge_dx_bf16_applicable(g, channels)) return SE3_ERR_UNSUPPORTED;
   const int64_t items = g.n_ctr;  // one workgroup per sample point (all its centre-frame pairs)
   if (items == 0) return SE3_OK;
+  const EdgeDxForm form = edge_dx_form(g, channels);
+  if (forms_only()) return form_report(tag, "edge_dx<ct=%d,p2=%d>", form.ct, form.shift >= 0);
   ProfScope prof(tag, stream);
-  int shift = -1;
-  for (int sft = 0; sft < 8; ++sft)
-    if ((1 << sft) == g.f_nb) shift = sft;
-  const int ct = channels == 32 ? 1 : 2;
+  const int shift = form.shift, ct = form.ct;
   const dim3 grid((unsigned)(items < (1 << 20) ? items : (1 << 20)), (unsigned)(channels / (32 * ct)));
 #define SE3_DX(CT, P2) \
   hipLaunchKernelGGL((edge_dx_bf16_kernel<CT, P2>), grid, dim3(128), 0, stream, g, axes_ext, rho, grad_t, channels, d_rows, items, shift)
-  if (ct == 1) {
-    if (shift >= 0) SE3_DX(1, true); else SE3_DX(1, false);
-  } else {
-    if (shift >= 0) SE3_DX(2, true); else SE3_DX(2, false);
+  switch (ct * 2 + (shift >= 0 ? 1 : 0)) {
+    case 3: SE3_DX(1, true); break;
+    case 2: SE3_DX(1, false); break;
+    case 5: SE3_DX(2, true); break;
+    default: SE3_DX(2, false); break;
   }
 #undef SE3_DX
   return check_launch();
 }
+
+// lanes per source point of dx_gather_sum_kernel (its template argument): 16 bytes per lane and step
+static int dx_gather_form(int width) { return width <= 64 ? 16 : (width <= 128 ? 32 : 64); }
 
 int launch_dx_gather_sum(const char* tag, const float* d_rows, const int32_t* neighbors, const int32_t* ends,
                          const int32_t* t_samples, const int32_t* t_ends, const int32_t* t_edge_ids, int64_t n_src, int width,
@@ -277,16 +285,19 @@ int launch_dx_gather_sum(const char* tag, const float* d_rows, const int32_t* ne
   if (n_src == 0) return SE3_OK;
   if (width < 1 || width > 512) return SE3_ERR_UNSUPPORTED;
   if (width % 4 != 0) return SE3_ERR_UNSUPPORTED;
+  const int g = dx_gather_form(width);
+  if (forms_only()) return form_report(tag, "dx_gather<g=%d>", g);
   ProfScope prof(tag, stream);
-  const int g = width <= 64 ? 16 : (width <= 128 ? 32 : 64);  // lanes per source point: 16 bytes per lane and step
   int64_t blocks = (n_src + 4 * (64 / g) - 1) / (4 * (64 / g));
   if (blocks > (1 << 20)) blocks = 1 << 20;
 #define SE3_GATHER(G)                                                                                                      \
   hipLaunchKernelGGL(dx_gather_sum_kernel<G>, dim3((unsigned)blocks), dim3(256), 0, stream, d_rows, neighbors, ends, t_samples, \
                      t_ends, t_edge_ids, n_src, width, scale, grad_feat)
-  if (g == 16) SE3_GATHER(16);
-  else if (g == 32) SE3_GATHER(32);
-  else SE3_GATHER(64);
+  switch (g) {
+    case 16: SE3_GATHER(16); break;
+    case 32: SE3_GATHER(32); break;
+    default: SE3_GATHER(64); break;
+  }
 #undef SE3_GATHER
   return check_launch();
 }

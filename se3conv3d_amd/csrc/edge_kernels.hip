@@ -450,6 +450,13 @@ __global__ __launch_bounds__(256, 3) void edge_param_grad_fast_kernel(EdgeGeom g
 
 }  // namespace
 
+// Which instantiation of edge_t_kernel a shape takes: the channels a lane owns (VW); p2 = the neighbour frame count is a
+// power of two (the kernel splits a frame-edge by its run-time shift instead of a division).
+struct EdgeTForm { int vw, shift; };
+static EdgeTForm edge_t_form(const EdgeGeom& g, int channels) {
+  return {channels % 128 == 0 ? 4 : channels % 64 == 0 ? 2 : 1, frame_shift(g.f_nb)};
+}
+
 int launch_edge_t(const char* tag, const EdgeGeom& g, const float* feat, int channels, int64_t feat_rows,
                   const float* axes_ext, const float* rho, float* t_out, hipStream_t stream) {
   const int64_t rows = g.n_ctr * g.f_ctr;
@@ -457,16 +464,18 @@ int launch_edge_t(const char* tag, const EdgeGeom& g, const float* feat, int cha
   // 32-bit byte offsets into the gathered operand and the packed records
   if (feat_rows * (int64_t)channels * 4 >= (int64_t)kOobOffset || rows >= (1ll << 31) || !g.ctr_geom || !g.nb_geom)
     return SE3_ERR_UNSUPPORTED;
+  const EdgeTForm form = edge_t_form(g, channels);
+  if (forms_only()) return form_report(tag, "edge_t<vw=%d>/p2=%d", form.vw, form.shift >= 0);
   ProfScope prof(tag, stream);
-  int shift = -1;
-  for (int sft = 0; sft < 8; ++sft)
-    if ((1 << sft) == g.f_nb) shift = sft;
+  const int shift = form.shift;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
 #define SE3_LAUNCH(VW) \
   hipLaunchKernelGGL(edge_t_kernel<VW>, grid, block, 0, stream, g, feat, channels, feat_rows, axes_ext, rho, t_out, rows, shift)
-  if (channels % 128 == 0) SE3_LAUNCH(4);
-  else if (channels % 64 == 0) SE3_LAUNCH(2);
-  else SE3_LAUNCH(1);
+  switch (form.vw) {
+    case 4: SE3_LAUNCH(4); break;
+    case 2: SE3_LAUNCH(2); break;
+    default: SE3_LAUNCH(1); break;
+  }
 #undef SE3_LAUNCH
   return check_launch();
 }
@@ -478,34 +487,44 @@ int edge_param_grad_blocks(int64_t rows) {
   return (int)(want < 2048 ? (want > 0 ? want : 1) : 2048);
 }
 
-int launch_edge_param_grad(const char* tag, const EdgeGeom& g, const float* feat, int channels, int64_t feat_rows,
-                           const float* axes_ext, const float* rho, const float* grad_t, float* partials,
-                           int n_partials, int* n_used, hipStream_t stream) {
+// Which parameter-gradient kernel a shape takes: the pipelined form (hs = half the channels: rows of 32 or 64 channels
+// within the reach of its 32-bit offsets) or the generic kernel, and how many of the partial-sum slots it uses.
+struct EdgeParamGradForm { int hs, shift, blocks; };  // hs = 0: the generic kernel
+static EdgeParamGradForm edge_param_grad_form(const EdgeGeom& g, int channels, int64_t feat_rows, int n_partials) {
   const int64_t rows = g.n_ctr * g.f_ctr;
-  ProfScope prof(tag, stream);
-  // two workgroups per CU (2048 measured 3 % slower, 4096 11 %): the slot capacity is sized for the pair form of the
-  // split-bf16 kernel, this kernel uses at most 512 of the slots
-  *n_used = n_partials < 512 ? n_partials : 512;
   // 32-bit byte offsets in the pipelined form: the gathered operand, the packed records, the grad_T rows
   const bool fast = (channels == 32 || channels == 64) && g.ctr_geom && g.nb_geom && rows < (1ll << 31) &&
                     feat_rows * (int64_t)channels * 4 < (int64_t)kOobOffset &&
                     rows * (int64_t)channels * kBasis * 4 < (1ll << 31);
-  if (fast) {
-    // the pipelined form holds 168 registers: three workgroups per CU (768: 0.78 ms against 0.86 at 512 and 0.82 at 1024)
-    *n_used = n_partials < 768 ? n_partials : 768;
-    int shift = -1;
-    for (int sft = 0; sft < 8; ++sft)
-      if ((1 << sft) == g.f_nb) shift = sft;
-    if (channels == 64)
+  // the pipelined form holds 168 registers: three workgroups per CU (768: 0.78 ms against 0.86 at 512 and 0.82 at 1024).
+  // Otherwise two workgroups per CU (2048 measured 3 % slower, 4096 11 %): the slot capacity is sized for the pair form of
+  // the split-bf16 kernel, this kernel uses at most 512 of the slots
+  const int cap = fast ? 768 : 512;
+  return {fast ? channels / 2 : 0, frame_shift(g.f_nb), n_partials < cap ? n_partials : cap};
+}
+
+int launch_edge_param_grad(const char* tag, const EdgeGeom& g, const float* feat, int channels, int64_t feat_rows,
+                           const float* axes_ext, const float* rho, const float* grad_t, float* partials,
+                           int n_partials, int* n_used, hipStream_t stream) {
+  const int64_t rows = g.n_ctr * g.f_ctr;
+  const EdgeParamGradForm form = edge_param_grad_form(g, channels, feat_rows, n_partials);
+  *n_used = form.blocks;
+  if (forms_only())
+    return form.hs ? form_report(tag, "param_grad_fast<hs=%d>/p2=%d", form.hs, form.shift >= 0) : form_report(tag, "param_grad_generic");
+  ProfScope prof(tag, stream);
+  switch (form.hs) {
+    case 32:
       hipLaunchKernelGGL(edge_param_grad_fast_kernel<32>, dim3(*n_used), dim3(256), 0, stream, g, feat, feat_rows, axes_ext,
-                         rho, grad_t, partials, rows, shift);
-    else
+                         rho, grad_t, partials, rows, form.shift);
+      break;
+    case 16:
       hipLaunchKernelGGL(edge_param_grad_fast_kernel<16>, dim3(*n_used), dim3(256), 0, stream, g, feat, feat_rows, axes_ext,
-                         rho, grad_t, partials, rows, shift);
-    return check_launch();
+                         rho, grad_t, partials, rows, form.shift);
+      break;
+    default:
+      hipLaunchKernelGGL(edge_param_grad_kernel, dim3(*n_used), dim3(256), 0, stream, g, feat, channels, axes_ext,
+                         rho, grad_t, partials, rows);
   }
-  hipLaunchKernelGGL(edge_param_grad_kernel, dim3(*n_used), dim3(256), 0, stream, g, feat, channels, axes_ext,
-                     rho, grad_t, partials, rows);
   return check_launch();
 }
 

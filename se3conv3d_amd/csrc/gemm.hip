@@ -386,10 +386,16 @@ size_t gemm_nn_split_bytes(int64_t m, int n, int k) {
   return s > 1 ? (size_t)s * m * n * 4 : 0;
 }
 
-int launch_gemm_nn(const char* tag, const float* a, const float* b, float* c, int64_t m, int n, int k,
-                   const float* alpha_num, float alpha_scale, hipStream_t stream, float* split_ws) {
-  if (m == 0 || n == 0) return SE3_OK;
-  ProfScope prof(tag, stream);
+// Which fp32 NN kernel a product takes and its grid: row strips for the short-k, wide-n product (grad_T), the tiled
+// buffer-load kernel with or without a split of k, or the generic kernel.
+struct GemmNnForm {
+  enum Kind { strip, fast, generic } kind;
+  int kh;      // strip: k / 2 (the kernel's template argument)
+  int per;     // strip: column tiles per workgroup; split: k-tiles per split; 0 otherwise
+  dim3 grid;   // grid.z > 1: k is split, partials go to split_ws and are reduced
+};
+static GemmNnForm gemm_nn_form(int64_t m, int n, int k, bool have_split_ws) {
+  GemmNnForm f{};
   const int64_t row_blocks = (m + BM - 1) / BM;
   // 32-bit byte offsets of the buffer-load forms; kOobOffset must lie beyond both operands
   const bool small = (m + BM) * (int64_t)k * 4 < (int64_t)kOobOffset && (int64_t)k * n * 4 < (int64_t)kOobOffset;
@@ -398,26 +404,50 @@ int launch_gemm_nn(const char* tag, const float* a, const float* b, float* c, in
     const int n_tiles = n / BN;
     int n_split = row_blocks >= 1024 ? 1 : (int)(1024 / row_blocks);
     if (n_split > n_tiles / 4) n_split = n_tiles / 4;
-    const int per = (n_tiles + n_split - 1) / n_split;
-    const dim3 grid((unsigned)row_blocks, (unsigned)((n_tiles + per - 1) / per));
-    if (k == 64)
-      hipLaunchKernelGGL(gemm_nn_strip_kernel<32>, grid, dim3(256), 0, stream, a, b, c, m, n, per, alpha_num, alpha_scale);
-    else
-      hipLaunchKernelGGL(gemm_nn_strip_kernel<16>, grid, dim3(256), 0, stream, a, b, c, m, n, per, alpha_num, alpha_scale);
-    return check_launch();
+    f.kind = GemmNnForm::strip, f.kh = k / 2;
+    f.per = (n_tiles + n_split - 1) / n_split;
+    f.grid = dim3((unsigned)row_blocks, (unsigned)((n_tiles + f.per - 1) / f.per));
+    return f;
   }
-  const dim3 grid((unsigned)row_blocks, (unsigned)((n + BN - 1) / BN));
-  const int splits = small && split_ws ? gemm_nn_splits(m, n, k) : 1;
+  f.grid = dim3((unsigned)row_blocks, (unsigned)((n + BN - 1) / BN));
+  const int splits = small && have_split_ws ? gemm_nn_splits(m, n, k) : 1;
   if (splits > 1) {
-    const int per = (k / FK + splits - 1) / splits;
-    const dim3 sgrid(grid.x, grid.y, (unsigned)((k / FK + per - 1) / per));
-    hipLaunchKernelGGL(gemm_nn_fast_kernel, sgrid, dim3(256), 0, stream, a, b, split_ws, m, n, k, per, alpha_num, alpha_scale);
-    return launch_reduce_partials(split_ws, c, m * n, (int)sgrid.z, alpha_num, alpha_scale, stream);
+    f.kind = GemmNnForm::fast;
+    f.per = (k / FK + splits - 1) / splits;
+    f.grid.z = (unsigned)((k / FK + f.per - 1) / f.per);
+    return f;
   }
-  if (small && k % FK == 0 && n % 4 == 0)
-    hipLaunchKernelGGL(gemm_nn_fast_kernel, grid, dim3(256), 0, stream, a, b, c, m, n, k, 0, alpha_num, alpha_scale);
-  else
-    hipLaunchKernelGGL(gemm_nn_kernel, grid, dim3(256), 0, stream, a, b, c, m, n, k, alpha_num, alpha_scale);
+  f.kind = small && k % FK == 0 && n % 4 == 0 ? GemmNnForm::fast : GemmNnForm::generic;
+  return f;
+}
+
+int launch_gemm_nn(const char* tag, const float* a, const float* b, float* c, int64_t m, int n, int k,
+                   const float* alpha_num, float alpha_scale, hipStream_t stream, float* split_ws) {
+  if (m == 0 || n == 0) return SE3_OK;
+  const GemmNnForm f = gemm_nn_form(m, n, k, split_ws != nullptr);
+  const bool split = f.kind == GemmNnForm::fast && f.per > 0;
+  if (forms_only()) {
+    form_report(tag, f.kind == GemmNnForm::strip ? "gemm_nn_strip<kh=%d>" : f.kind == GemmNnForm::generic ? "gemm_nn_generic"
+                     : split ? "gemm_nn_fast/split" : "gemm_nn_fast", f.kh);
+    return split ? launch_reduce_partials(split_ws, c, m * n, (int)f.grid.z, alpha_num, alpha_scale, stream) : SE3_OK;
+  }
+  ProfScope prof(tag, stream);
+  switch (f.kind) {
+    case GemmNnForm::strip:
+      if (f.kh == 32)
+        hipLaunchKernelGGL(gemm_nn_strip_kernel<32>, f.grid, dim3(256), 0, stream, a, b, c, m, n, f.per, alpha_num, alpha_scale);
+      else
+        hipLaunchKernelGGL(gemm_nn_strip_kernel<16>, f.grid, dim3(256), 0, stream, a, b, c, m, n, f.per, alpha_num, alpha_scale);
+      break;
+    case GemmNnForm::fast:
+      hipLaunchKernelGGL(gemm_nn_fast_kernel, f.grid, dim3(256), 0, stream, a, b, split ? split_ws : c, m, n, k, f.per, alpha_num,
+                         alpha_scale);
+      if (split) return launch_reduce_partials(split_ws, c, m * n, (int)f.grid.z, alpha_num, alpha_scale, stream);
+      break;
+    case GemmNnForm::generic:
+      hipLaunchKernelGGL(gemm_nn_kernel, f.grid, dim3(256), 0, stream, a, b, c, m, n, k, alpha_num, alpha_scale);
+      break;
+  }
   return check_launch();
 }
 
@@ -445,25 +475,41 @@ int gemm_tn_splits(int64_t m, int ka, int n) {
   return (int)s;
 }
 
+// the buffer-load form of the fp32 TN kernel addresses both operands with 32-bit byte offsets (rows up to one batch past
+// the end); operands beyond their reach take the generic kernel
+static bool gemm_tn_form_fast(int64_t m, int ka, int n) {
+  return (m + 64) * (int64_t)ka * 4 < (int64_t)kOobOffset && (m + 64) * (int64_t)n * 4 < (int64_t)kOobOffset;
+}
+
 int launch_gemm_tn(const char* tag, const float* a, const float* b, float* c, float* partials, int splits, int64_t m,
                    int ka, int n, const float* alpha_num, float alpha_scale, hipStream_t stream) {
   if (ka == 0 || n == 0) return SE3_OK;
+  const bool fast = gemm_tn_form_fast(m, ka, n);
+  if (forms_only()) {
+    form_report(tag, fast ? "gemm_tn_fast" : "gemm_tn_generic");
+    return launch_reduce_partials(partials, c, (int64_t)ka * n, splits, alpha_num, alpha_scale, stream);
+  }
   ProfScope prof(tag, stream);
   int64_t chunk = (m + splits - 1) / splits;
   chunk += chunk & 1;  // keep every split's first row even so the (m, m+1) pairing never straddles splits
   if (chunk == 0) chunk = 2;
   const dim3 grid((unsigned)((ka + 127) / 128), (unsigned)((n + BN - 1) / BN), (unsigned)splits);
-  // the buffer-load form addresses both operands with 32-bit byte offsets (rows up to one batch past the end)
-  if ((m + 64) * (int64_t)ka * 4 < (int64_t)kOobOffset && (m + 64) * (int64_t)n * 4 < (int64_t)kOobOffset)
+  if (fast)
     hipLaunchKernelGGL(gemm_tn_fast_kernel, grid, dim3(256), 0, stream, a, b, partials, m, ka, n, chunk);
   else
     hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(256), 0, stream, a, b, partials, m, ka, n, chunk);
   return launch_reduce_partials(partials, c, (int64_t)ka * n, splits, alpha_num, alpha_scale, stream);
 }
 
+// many short ranges of a small output: one workgroup per 32 outputs sums its ranges in eight groups
+static bool reduce_partials_form_grouped(int64_t count, int splits) { return splits >= 64 && count <= (1 << 16); }
+
+// (runs inside its caller's stage: a forms query lists it under the tag of the report before it)
 int launch_reduce_partials(const float* partials, float* out, int64_t count, int splits, const float* alpha_num,
                            float alpha_scale, hipStream_t stream) {
-  if (splits >= 64 && count <= (1 << 16)) {
+  const bool grouped = reduce_partials_form_grouped(count, splits);
+  if (forms_only()) return form_report(nullptr, grouped ? "reduce_partials_grouped" : "reduce_partials");
+  if (grouped) {
     hipLaunchKernelGGL(reduce_partials_grouped_kernel, dim3((unsigned)((count + 31) / 32)), dim3(256), 0, stream, partials, out,
                        count, splits, alpha_num, alpha_scale);
     return check_launch();

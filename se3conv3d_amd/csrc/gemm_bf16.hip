@@ -1057,52 +1057,89 @@ bool gemm_strip_bf16_applicable(int64_t m, int n, int k) {
          (m + 128) * (int64_t)k * 4 < (1ll << 32) - 64 && (int64_t)(n + 64) * kp * 2 < (1ll << 32) - 64;
 }
 
-int launch_gemm_strip_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, uint32_t* c,
-                           int64_t m, int n, int k, hipStream_t stream) {
-  if (m == 0 || n == 0) return SE3_OK;
-  if (!gemm_strip_bf16_applicable(m, n, k)) return SE3_ERR_UNSUPPORTED;
-  ProfScope prof(tag, stream);
+// k-steps of 16 per row of the strip kernel (its template argument) and its grid
+struct GemmStripForm { int ks; dim3 grid; };
+static GemmStripForm gemm_strip_bf16_form(int64_t m, int n, int k) {
   const int64_t row_blocks = (m + 127) / 128;
   int n_split = row_blocks >= 1024 ? 1 : (int)(1024 / row_blocks);  // <= 1024 workgroups = one resident round (4 per CU)
   const int n_tiles = n / 32;
   if (n_split > n_tiles / 4) n_split = n_tiles / 4 > 0 ? n_tiles / 4 : 1;  // >= 4 column tiles per block
-  const dim3 sgrid((unsigned)row_blocks, (unsigned)n_split);
   const int kp = (k + 31) / 32 * 32;
-  if (kp == 32)
-    hipLaunchKernelGGL(gemm_strip_bf16_kernel<2>, sgrid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k);
-  else if (kp == 64)
-    hipLaunchKernelGGL(gemm_strip_bf16_kernel<4>, sgrid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k);
-  else
-    hipLaunchKernelGGL(gemm_strip_bf16_kernel<8>, sgrid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k);
+  return {kp == 32 ? 2 : kp == 64 ? 4 : 8, dim3((unsigned)row_blocks, (unsigned)n_split)};
+}
+
+int launch_gemm_strip_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, uint32_t* c,
+                           int64_t m, int n, int k, hipStream_t stream) {
+  if (m == 0 || n == 0) return SE3_OK;
+  if (!gemm_strip_bf16_applicable(m, n, k)) return SE3_ERR_UNSUPPORTED;
+  const GemmStripForm f = gemm_strip_bf16_form(m, n, k);
+  if (forms_only()) return form_report(tag, "gemm_strip_bf16<ks=%d>", f.ks);
+  ProfScope prof(tag, stream);
+  switch (f.ks) {
+    case 2: hipLaunchKernelGGL(gemm_strip_bf16_kernel<2>, f.grid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k); break;
+    case 4: hipLaunchKernelGGL(gemm_strip_bf16_kernel<4>, f.grid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k); break;
+    default: hipLaunchKernelGGL(gemm_strip_bf16_kernel<8>, f.grid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k); break;
+  }
   return check_launch();
 }
 
-static int gemm_nn_bf16_rows(const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, void* c, bool out_packed,
-                             int64_t m, int n, int k, float* split_ws, const float* alpha_num, float alpha_scale,
-                             hipStream_t stream, int afmt, ReduceBatch* defer) {
+// Which NN kernel a block of rows takes (gemm_nn_bf16_rows switches on it): the kernel by the format of the A rows, the
+// output mode (0 fp32, 1 packed words, 2 split-K partials), the buffer-load form (`fast`), 64-column blocks per workgroup.
+struct GemmNnBf16Form {
+  int status;        // SE3_OK, or why the shape cannot run in this row format
+  int afmt, mode, nb;
+  bool fast;
+  int kp, per, st_per, splits;
+  dim3 grid;
+};
+static GemmNnBf16Form gemm_nn_bf16_form(int64_t m, int n, int k, bool have_split_ws, bool out_packed, int afmt) {
+  GemmNnBf16Form f{};
   const bool a24 = afmt == 1, a16 = afmt == 2;  // A rows: 0 packed words, 1 3-byte rows, 2 T16 (common.h)
-  const int kp = (k + 31) / 32 * 32;
-  const int nkt = kp / BK;
-  int splits = split_ws ? gemm_nn_bf16_splits(m, n, k) : 1;
-  const int per = (nkt + splits - 1) / splits;
-  splits = (nkt + per - 1) / per;
-  const int nbw = gemm_nn_bf16_col_blocks(n, k);
-  const dim3 grid((unsigned)((m + BM - 1) / BM), (unsigned)((n + BN * nbw - 1) / (BN * nbw)), (unsigned)splits);
-  const bool fast = (k % 32 == 0) && (m * (int64_t)k * 4 < (1ll << 32)) && ((int64_t)n * kp * 2 < (1ll << 32)) &&
-                    ((m + BM) * (int64_t)k * 4 < (1ll << 32)) && ((int64_t)(n + 128) * kp * 2 < (1ll << 32));
-  if (a24 && (!fast || k % 64 != 0)) return SE3_ERR_UNSUPPORTED;
+  f.afmt = afmt;
+  f.kp = (k + 31) / 32 * 32;
+  const int nkt = f.kp / BK;
+  int splits = have_split_ws ? gemm_nn_bf16_splits(m, n, k) : 1;
+  f.per = (nkt + splits - 1) / splits;
+  splits = (nkt + f.per - 1) / f.per;
+  f.nb = gemm_nn_bf16_col_blocks(n, k);
+  f.grid = dim3((unsigned)((m + BM - 1) / BM), (unsigned)((n + BN * f.nb - 1) / (BN * f.nb)), (unsigned)splits);
+  f.fast = (k % 32 == 0) && (m * (int64_t)k * 4 < (1ll << 32)) && ((int64_t)n * f.kp * 2 < (1ll << 32)) &&
+           ((m + BM) * (int64_t)k * 4 < (1ll << 32)) && ((int64_t)(n + 128) * f.kp * 2 < (1ll << 32));
+  if (a24 && (!f.fast || k % 64 != 0)) f.status = SE3_ERR_UNSUPPORTED;
   // T16: mega tiles of 256 k; its rows are 2.25 bytes per element, addressed with 32-bit byte offsets like the others
-  if (a16 && (k % 256 != 0 || (m + BM) * ((int64_t)k / 32 * 72) >= (1ll << 32) || (int64_t)(n + 128) * kp * 2 >= (1ll << 32)))
-    return SE3_ERR_UNSUPPORTED;
-  int st_per = (per + 1) / 2;  // 3-byte / T16 rows: the kernels walk super tiles of 64 k
-  if (a16) st_per = (st_per + 3) / 4 * 4;  // whole mega tiles per split
-  if (a24 || a16) splits = (k / 64 + st_per - 1) / st_per;
-  const dim3 grid24((unsigned)((m + BM - 1) / BM), grid.y, (unsigned)splits);
-#define SE3_NN_LAUNCH(MODE, F, NBV, OUT)                                                                              \
-  hipLaunchKernelGGL((gemm_nn_bf16_kernel<MODE, F, NBV>), grid, dim3(256), 0, stream, a, bt_hi, bt_lo, (void*)(OUT), m, n, \
-                     k, kp, per, alpha_num, alpha_scale)
-#define SE3_NN_LAUNCH24(MODE, NBV, OUT)                                                                               \
-  do {                                                                                                                \
+  if (a16 && (k % 256 != 0 || (m + BM) * ((int64_t)k / 32 * 72) >= (1ll << 32) || (int64_t)(n + 128) * f.kp * 2 >= (1ll << 32)))
+    f.status = SE3_ERR_UNSUPPORTED;
+  if (f.status) return f;
+  f.st_per = (f.per + 1) / 2;  // 3-byte / T16 rows: the kernels walk super tiles of 64 k
+  if (a16) f.st_per = (f.st_per + 3) / 4 * 4;  // whole mega tiles per split
+  if (a24 || a16) {
+    splits = (k / 64 + f.st_per - 1) / f.st_per;
+    f.grid.z = (unsigned)splits;
+  }
+  f.splits = splits;
+  f.mode = splits > 1 ? 2 : out_packed ? 1 : 0;
+  return f;
+}
+
+static int gemm_nn_bf16_rows(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, void* c,
+                             bool out_packed, int64_t m, int n, int k, float* split_ws, const float* alpha_num, float alpha_scale,
+                             hipStream_t stream, int afmt, ReduceBatch* defer) {
+  const GemmNnBf16Form f = gemm_nn_bf16_form(m, n, k, split_ws != nullptr, out_packed, afmt);
+  if (f.status) return f.status;
+  const int kp = f.kp, per = f.per, st_per = f.st_per, splits = f.splits;
+  const dim3 grid = f.grid;
+  void* const out = f.mode == 2 ? (void*)split_ws : c;
+  if (forms_only()) {
+    if (afmt == 0) form_report(tag, "gemm_nn_bf16<mode=%d,fast=%d,nb=%d>", f.mode, f.fast, f.nb);
+    else form_report(tag, "gemm_nn_%s<mode=%d,nb=%d>", afmt == 2 ? "t16" : "t24", f.mode, f.nb);
+    if (splits > 1 && !defer) form_report(tag, "reduce_splits<packed=%d>", out_packed);
+  } else {
+#define SE3_NN_LAUNCH(MODE, F, NBV)                                                                                   \
+  if (f.afmt == 0 && f.mode == MODE && f.fast == F && f.nb == NBV)                                                      \
+    hipLaunchKernelGGL((gemm_nn_bf16_kernel<MODE, F, NBV>), grid, dim3(256), 0, stream, a, bt_hi, bt_lo, out, m, n,     \
+                       k, kp, per, alpha_num, alpha_scale)
+#define SE3_NN_LAUNCH24(MODE, NBV)                                                                                    \
+  if (f.afmt == 1 && f.mode == MODE && f.nb == NBV) {                                                                   \
     constexpr int lds_bytes = gemm_nn_t24_lds_bytes(NBV);                                                              \
     if (lds_bytes > 64 * 1024) {  /* beyond the default dynamic-LDS limit: raised once per (device, instantiation) -- a \
                                      runtime that keeps the attribute per device must see it on every device the      \
@@ -1118,62 +1155,69 @@ static int gemm_nn_bf16_rows(const uint32_t* a, const uint16_t* bt_hi, const uin
         raised.fetch_or(bit_, std::memory_order_relaxed);                                                             \
       }                                                                                                               \
     }                                                                                                                 \
-    hipLaunchKernelGGL((gemm_nn_t24_kernel<MODE, NBV>), grid24, dim3(256), lds_bytes, stream, (const uint8_t*)a,       \
-                       bt_hi, bt_lo, (void*)(OUT), m, n, k, st_per, alpha_num, alpha_scale);                          \
-  } while (0)
-#define SE3_NN_LAUNCH16(MODE, NBV, OUT)                                                                               \
-  hipLaunchKernelGGL((gemm_nn_t16_kernel<MODE, NBV>), grid24, dim3(256), 0, stream, (const uint8_t*)a, bt_hi, bt_lo,   \
-                     (void*)(OUT), m, n, k, st_per, alpha_num, alpha_scale)
-#define SE3_NN(MODE, OUT)                                    \
-  do {                                                       \
-    if (a16 && nbw == 2) SE3_NN_LAUNCH16(MODE, 2, OUT);      \
-    else if (a16) SE3_NN_LAUNCH16(MODE, 1, OUT);             \
-    else if (a24 && nbw == 2) SE3_NN_LAUNCH24(MODE, 2, OUT); \
-    else if (a24) SE3_NN_LAUNCH24(MODE, 1, OUT);             \
-    else if (fast && nbw == 2) SE3_NN_LAUNCH(MODE, true, 2, OUT); \
-    else if (fast) SE3_NN_LAUNCH(MODE, true, 1, OUT);        \
-    else if (nbw == 2) SE3_NN_LAUNCH(MODE, false, 2, OUT);   \
-    else SE3_NN_LAUNCH(MODE, false, 1, OUT);                 \
-  } while (0)
+    hipLaunchKernelGGL((gemm_nn_t24_kernel<MODE, NBV>), grid, dim3(256), lds_bytes, stream, (const uint8_t*)a,         \
+                       bt_hi, bt_lo, out, m, n, k, st_per, alpha_num, alpha_scale);                                   \
+  }
+#define SE3_NN_LAUNCH16(MODE, NBV)                                                                                    \
+  if (f.afmt == 2 && f.mode == MODE && f.nb == NBV)                                                                     \
+    hipLaunchKernelGGL((gemm_nn_t16_kernel<MODE, NBV>), grid, dim3(256), 0, stream, (const uint8_t*)a, bt_hi, bt_lo,   \
+                       out, m, n, k, st_per, alpha_num, alpha_scale)
+#define SE3_NN(MODE)                          \
+  SE3_NN_LAUNCH16(MODE, 2);                   \
+  else SE3_NN_LAUNCH16(MODE, 1);              \
+  else SE3_NN_LAUNCH24(MODE, 2)               \
+  else SE3_NN_LAUNCH24(MODE, 1)               \
+  else SE3_NN_LAUNCH(MODE, true, 2);          \
+  else SE3_NN_LAUNCH(MODE, true, 1);          \
+  else SE3_NN_LAUNCH(MODE, false, 2);         \
+  else SE3_NN_LAUNCH(MODE, false, 1)
+    SE3_NN(2);
+    else SE3_NN(1);
+    else SE3_NN(0);
+    else return SE3_ERR_UNSUPPORTED;
+#undef SE3_NN
+#undef SE3_NN_LAUNCH
+#undef SE3_NN_LAUNCH24
+#undef SE3_NN_LAUNCH16
+  }
   if (splits > 1) {
-    SE3_NN(2, split_ws);
     const int64_t count = m * n;
     const int rb = (int)((count + 255) / 256 < 2048 ? (count + 255) / 256 : 2048);
     if (defer)  // the caller folds the partials together with its other reductions (ReduceBatch)
       defer->sum(split_ws, c, count, splits, alpha_num, alpha_scale, out_packed);
+    else if (forms_only())
+      ;
     else if (out_packed)
       hipLaunchKernelGGL(reduce_splits_kernel<true>, dim3(rb), dim3(256), 0, stream, split_ws, c, count, splits,
                          alpha_num, alpha_scale);
     else
       hipLaunchKernelGGL(reduce_splits_kernel<false>, dim3(rb), dim3(256), 0, stream, split_ws, c, count, splits,
                          alpha_num, alpha_scale);
-  } else if (out_packed) {
-    SE3_NN(1, c);
-  } else {
-    SE3_NN(0, c);
   }
-#undef SE3_NN
-#undef SE3_NN_LAUNCH
-#undef SE3_NN_LAUNCH24
-#undef SE3_NN_LAUNCH16
   return check_launch();
 }
 
 // The kernels address A with 32-bit byte offsets (buffer loads): more rows than those reach -- 262 k rows of 2048 values
 // and up, i.e. clouds beyond ~130 k points at two frames -- go through the same kernels row block by row block (no split
-// of k at that size, so the blocks share nothing but the weights).
+// of k at that size, so the blocks share nothing but the weights).  0: the whole product is one block.
+static int64_t gemm_nn_bf16_row_block(int64_t m, int k) {
+  const int64_t max_rows = (((1ll << 32) - 64) / ((int64_t)k * 4) - 2 * BM) / BM * BM;
+  return m <= max_rows || max_rows < BM || k % 32 != 0 ? 0 : max_rows;
+}
+
 int launch_gemm_nn_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, void* c,
                         bool out_packed, int64_t m, int n, int k, float* split_ws, const float* alpha_num,
                         float alpha_scale, hipStream_t stream, int afmt, ReduceBatch* defer) {
   if (m == 0 || n == 0) return SE3_OK;
+  const int64_t max_rows = gemm_nn_bf16_row_block(m, k);
+  if (forms_only() && max_rows) form_report(tag, "gemm_nn_row_blocks");
   ProfScope prof(tag, stream);
-  const int64_t max_rows = (((1ll << 32) - 64) / ((int64_t)k * 4) - 2 * BM) / BM * BM;
-  if (m <= max_rows || max_rows < BM || k % 32 != 0)
-    return gemm_nn_bf16_rows(a, bt_hi, bt_lo, c, out_packed, m, n, k, split_ws, alpha_num, alpha_scale, stream, afmt, defer);
+  if (!max_rows)
+    return gemm_nn_bf16_rows(tag, a, bt_hi, bt_lo, c, out_packed, m, n, k, split_ws, alpha_num, alpha_scale, stream, afmt, defer);
   const int64_t a_row_bytes = afmt == 2 ? (int64_t)k / 32 * 72 : (int64_t)k * (afmt == 1 ? 3 : 4);
   for (int64_t m0 = 0; m0 < m; m0 += max_rows) {
     const int64_t mb = m - m0 < max_rows ? m - m0 : max_rows;
-    if (int rc = gemm_nn_bf16_rows(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a) + m0 * a_row_bytes), bt_hi,
+    if (int rc = gemm_nn_bf16_rows(tag, reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a) + m0 * a_row_bytes), bt_hi,
                                    bt_lo, static_cast<char*>(c) + m0 * (int64_t)n * 4, out_packed, mb, n, k, nullptr, alpha_num,
                                    alpha_scale, stream, afmt, nullptr))
       return rc;
@@ -1186,26 +1230,47 @@ size_t gemm_nn_bf16_split_bytes(int64_t m, int n, int k) {
   return s > 1 ? (size_t)s * m * n * 4 : 0;
 }
 
-int launch_gemm_tn_bf16(const char* tag, const uint32_t* a, const uint32_t* b, float* c, float* partials, int splits,
-                        int64_t m, int ka, int n, const float* alpha_num, float alpha_scale, hipStream_t stream, int afmt,
-                        ReduceBatch* defer, bool out_ikn) {
+// Which TN kernel a weight-gradient product takes: by the format of the A rows; packed-word rows take the buffer-load
+// form (`fast`) when n is a multiple of 4 and a launch's 32-bit offsets reach a range plus its prefetch
+struct GemmTnBf16Form { int status; bool fast; int afmt; int64_t chunk, zs; };
+static GemmTnBf16Form gemm_tn_bf16_form(int64_t m, int ka, int n, int splits, int afmt) {
+  GemmTnBf16Form f{};
   const bool a24 = afmt == 1, a16 = afmt == 2;
-  if (ka == 0 || n == 0) return SE3_OK;
-  if (out_ikn && (!defer || ka % kBasis != 0)) return SE3_ERR_INVALID_ARGUMENT;  // the permuted store lives in the batched reduction
-  ProfScope prof(tag, stream);
-  int64_t chunk = (m + splits - 1) / splits;
-  chunk = (chunk + BK - 1) / BK * BK;
-  if (chunk == 0) chunk = BK;
+  f.afmt = afmt;
+  f.chunk = (m + splits - 1) / splits;
+  f.chunk = (f.chunk + BK - 1) / BK * BK;
+  if (f.chunk == 0) f.chunk = BK;
   // Both operands are addressed with 32-bit byte offsets from the pointers the kernel gets: row ranges (grid.z) beyond
   // their reach are launched as further groups of ranges, each with its operands' pointers moved to its first row
   // (the partials of group j start at range j * zs of the same buffer).
   const int64_t widest = (int64_t)(ka > n ? ka : n) * 4;
-  int64_t zs = (((1ll << 32) - 64) / widest - chunk) / chunk;  // ranges one launch can address
-  if (zs < 1) zs = 1;
-  if (zs > splits) zs = splits;
-  const bool vec = n % 4 == 0, reach = (zs + 1) * chunk * widest < (1ll << 32) - 64;
-  if (a24 && (!vec || !reach || ka % 64 != 0)) return SE3_ERR_UNSUPPORTED;
-  if (a16 && (!vec || !reach || ka % 256 != 0)) return SE3_ERR_UNSUPPORTED;
+  f.zs = (((1ll << 32) - 64) / widest - f.chunk) / f.chunk;  // ranges one launch can address
+  if (f.zs < 1) f.zs = 1;
+  if (f.zs > splits) f.zs = splits;
+  const bool vec = n % 4 == 0, reach = (f.zs + 1) * f.chunk * widest < (1ll << 32) - 64;
+  if (a24 && (!vec || !reach || ka % 64 != 0)) f.status = SE3_ERR_UNSUPPORTED;
+  if (a16 && (!vec || !reach || ka % 256 != 0)) f.status = SE3_ERR_UNSUPPORTED;
+  f.fast = a16 || a24 || (vec && reach);
+  return f;
+}
+
+int launch_gemm_tn_bf16(const char* tag, const uint32_t* a, const uint32_t* b, float* c, float* partials, int splits,
+                        int64_t m, int ka, int n, const float* alpha_num, float alpha_scale, hipStream_t stream, int afmt,
+                        ReduceBatch* defer, bool out_ikn) {
+  if (ka == 0 || n == 0) return SE3_OK;
+  if (out_ikn && (!defer || ka % kBasis != 0)) return SE3_ERR_INVALID_ARGUMENT;  // the permuted store lives in the batched reduction
+  const GemmTnBf16Form f = gemm_tn_bf16_form(m, ka, n, splits, afmt);
+  if (f.status) return f.status;
+  if (forms_only()) {
+    form_report(tag, "gemm_tn_bf16<fast=%d,afmt=%d>", f.fast, f.afmt);
+    if (defer) {
+      defer->sum(partials, c, (int64_t)ka * n, splits, alpha_num, alpha_scale, false, out_ikn ? n : 0);
+      return SE3_OK;
+    }
+    return launch_reduce_partials(partials, c, (int64_t)ka * n, splits, alpha_num, alpha_scale, stream);
+  }
+  ProfScope prof(tag, stream);
+  const int64_t chunk = f.chunk, zs = f.zs;
   for (int64_t z0 = 0; z0 < splits; z0 += zs) {
     const int64_t zn = splits - z0 < zs ? splits - z0 : zs, r0 = z0 * chunk;
     if (r0 >= m) {  // ranges past the last row (rounding of chunk): their partials are zeros
@@ -1214,18 +1279,16 @@ int launch_gemm_tn_bf16(const char* tag, const uint32_t* a, const uint32_t* b, f
     }
     const int64_t mb = m - r0 < zn * chunk ? m - r0 : zn * chunk;
     const dim3 grid((unsigned)((ka + 127) / 128), (unsigned)((n + BN - 1) / BN), (unsigned)zn);
-    const int64_t a_row_bytes = a16 ? (int64_t)ka / 32 * 72 : (int64_t)ka * (a24 ? 3 : 4);
+    const int64_t a_row_bytes = afmt == 2 ? (int64_t)ka / 32 * 72 : (int64_t)ka * (afmt == 1 ? 3 : 4);
     const uint32_t* ab = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a) + r0 * a_row_bytes);
     const uint32_t* bb = b + r0 * n;
     float* pb = partials + z0 * ka * n;
-    if (a16)
-      hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 2>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk);
-    else if (a24)
-      hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 1>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk);
-    else if (vec && reach)
-      hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 0>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk);
-    else
-      hipLaunchKernelGGL((gemm_tn_bf16_kernel<false, 0>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk);
+    switch (f.fast ? f.afmt : -1) {
+      case 2: hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 2>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk); break;
+      case 1: hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 1>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk); break;
+      case 0: hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 0>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk); break;
+      default: hipLaunchKernelGGL((gemm_tn_bf16_kernel<false, 0>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk); break;
+    }
   }
   if (defer) {
     defer->sum(partials, c, (int64_t)ka * n, splits, alpha_num, alpha_scale, false, out_ikn ? n : 0);

@@ -3,6 +3,8 @@
 // microseconds of work; as separate launches (8 in the backward pass) they cost more in launch latency than in
 // execution on the small hierarchy levels.  A block finds its job from blockIdx.x and runs it grid-stride over the
 // job's own block count.
+#include <cstdio>
+
 #include "common.h"
 
 namespace se3 {
@@ -199,6 +201,16 @@ int ReduceBatch::launch(hipStream_t stream) {
   if (jobs.count == 0) return check_launch();  // still the caller's last word on the launches before it
   int total = 0;
   for (int i = 0; i < jobs.count; ++i) total += jobs.job[i].blocks;
+  if (forms_only()) {  // one kernel; its jobs: s = sum, p = sum stored as packed words, w = sum stored as dW[i, k, o], a = d[A; beta]
+    char kinds[2 * 4 + 1] = {0};
+    for (int i = 0; i < jobs.count; ++i) {
+      const ReduceJob& j = jobs.job[i];
+      kinds[2 * i] = i ? '+' : '/';
+      kinds[2 * i + 1] = j.type == 1 ? 'a' : j.packed ? 'p' : j.perm_n > 0 ? 'w' : 's';
+    }
+    jobs.count = 0;
+    return form_report("reductions", "reduce_batch%s", kinds);
+  }
   ProfScope prof("reductions", stream);
   hipLaunchKernelGGL(reduce_batch_kernel, dim3((unsigned)total), dim3(256), 0, stream, jobs);
   jobs.count = 0;
@@ -210,6 +222,13 @@ int PrepBatch::launch(hipStream_t stream) {
   if (jobs.count == 0) return SE3_OK;
   int total = 0;
   for (int i = 0; i < jobs.count; ++i) total += jobs.job[i].blocks;
+  if (forms_only()) {  // one kernel; its weight jobs as /w<mode>f<frag_layout | 3-byte k order << 1 | T16 k order << 2>
+    char kinds[8 * 8 + 1] = {0};
+    int n = 0;
+    for (int i = 0; i < jobs.count; ++i)
+      if (jobs.job[i].type == kJobWeights) n += snprintf(kinds + n, sizeof(kinds) - n, "/w%df%d", jobs.job[i].p[3], jobs.job[i].p[7]);
+    return form_report("prep", "prep_batch%s", kinds);
+  }
   ProfScope prof("prep", stream);
   hipLaunchKernelGGL(prep_batch_kernel, dim3((unsigned)total), dim3(256), 0, stream, jobs);
   return check_launch();
@@ -223,7 +242,7 @@ __global__ void fill_words_kernel(uint32_t* __restrict__ dst, uint32_t value, in
 }  // namespace
 
 int launch_fill_words(void* dst, uint32_t value, int64_t n_words, hipStream_t stream) {
-  if (n_words <= 0) return SE3_OK;
+  if (n_words <= 0 || forms_only()) return SE3_OK;
   int64_t blocks = (n_words + 1023) / 1024;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (uint32_t*)dst, value, n_words);

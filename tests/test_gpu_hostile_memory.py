@@ -45,6 +45,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 FUSED_TEST = "test_fused_random_shapes_on_hostile_memory"
+FUSED_K_TEST = "test_fused_random_shapes_other_basis_counts_at_the_c_abi"
 # entry point -> the tests of this module that run it inside the arena (and assert that they did)
 COVERED = {
     "se3_compute_keys": ["test_keys_boxes_and_grid_parameters"],
@@ -190,6 +191,11 @@ FUSED = [
     Fused("c320_320_small", (20, 200, None, 2, 2, 320, 320, 12, 1), "u"),   # widest level; edge-major form not implemented
     Fused("c32_32_f3", (16, 256, None, 3, 3, 32, 32, 8, 1), "u"),          # F = 3: odd F_out has no edge-major form
     Fused("c128_32_f4_f1", (13, 500, 250, 4, 1, 128, 32, 10, 2), "u"),     # F_in = 4 -> F_out = 1
+    # --- forms tests/test_form_coverage.py found unrun (their stray writes had never been looked for either)
+    Fused("c128_128_f3", (41, 300, None, 3, 3, 128, 128, 12, 1), "u"),       # wave pair dividing by F = 3 (p2=0), one frame per item
+    Fused("c64_13_head_f2", (42, 300, None, 2, 2, 64, 13, 12, 1), "edge"),   # class head: packed-word T behind the wave pair
+    Fused("c48_32_f2", (43, 300, None, 2, 2, 48, 32, 12, 1), "u"),           # C_in = 48: three 16-channel steps, two frames
+    Fused("c16_32_f1", (44, 300, None, 1, 1, 16, 32, 12, 1), "u"),           # C_in = 16: one step on full rows, one frame
     # --- clouds, 64 -> 64 channels, F = 2
     Fused("down", (31, 3000, 400, 2, 2, 64, 64, 18, 1), "edge"),
     Fused("up", (32, 100, 800, 2, 2, 64, 64, 12, 1), "u"),

@@ -9,9 +9,13 @@ import math
 import glob
 import os
 
+import ctypes as C
+import functools
+
 import pytest
 import torch
 
+import form_coverage_table as FC
 from conftest import GOLDEN, canon_edges, golden_layer_files, load_npz, rel_err
 from oracle import se3conv_oracle as O
 
@@ -27,8 +31,9 @@ TOL = 2e-5  # tests of the fp32-only ops (FeatBasisProj, rot tensors)
 
 # the opt-in third mode ("NOT the headline") runs where its own code is: the golden layer files, the random
 # shapes and the full-size headline subset (it used to carry a third of this module)
-T16_TESTS = ("test_layer_forward_backward_matches_golden", "test_random_shapes_against_oracle",
-             "test_headline_subset_against_oracle")
+GOLDEN_TEST, CASES_TEST = "test_layer_forward_backward_matches_golden", "test_random_shapes_against_oracle"
+FORM_TEST, FORM_TEST_OTHER = "test_random_shapes_of_every_form_against_oracle", "test_every_form_case_under_the_other_requests"
+T16_TESTS = (GOLDEN_TEST, CASES_TEST, "test_headline_subset_against_oracle", FORM_TEST, FORM_TEST_OTHER)
 
 
 @pytest.fixture(scope="module", params=["bf16x3", "fp32", "bf16x3_t16"])
@@ -199,17 +204,78 @@ CASES = [
 ]
 
 
-def run_case_against_oracle(c, f_in, f_out, amd):
-    """Ball query + operator forward/backward of one random case on the GPU against the oracle: returns the relative
-    errors of out / dx / dA / dbeta / dW (also used by tools/fuzz_parity.py) plus the geometry and reference edges."""
+# One row per kernel form that CASES, FUSED and the golden layers leave out: tests/test_form_coverage.py (CPU) sweeps the
+# library's own answer to "which form does this shape take" (se3conv_forms) and fails while a form the library can pick is
+# run by no table.  Chosen greedily against that test; the comment of a row names forms it is there for.  150-600 points a
+# side (the sizes the dispatch still distinguishes); every division form (p2=0: a neighbour frame count that is no power of
+# two) is met where edges per sample x F_nb exceeds 32 without being a multiple of it (chunk boundaries inside an edge's
+# frames) and in a two-cloud graph with empty samples and unseen sources.
+# "dense": most samples (or sources, for the transposed pass) have more than 32 frame-edges; "holes": two clouds, some samples
+# without a neighbour and some sources without an edge; "rows": beyond 600 points, because the form needs that many rows (the
+# dense products stop splitting k once their tiles fill the chip).  tests/test_form_coverage.py checks these properties too.
+FORM_CASES = [
+    # seed n_in n_out F_in F_out C_in C_out k batches    what only this row provides: a form (+ how many more), or the one dense / holed run of it
+    (41, 400, None, 1, 1, 64, 13, 20, 1),       # dense: edge_t_single<vw=2,fc=1,full=1,t24=0>/p2=1 (+1)
+    (57, 500, 250, 2, 2, 64, 13, 12, 2),        # holes: required head shape 64 -> 13 at F = 2, two clouds (its forms also run in FUSED c64_13_head_f2)
+    (59, 450, 450, 6, 6, 128, 13, 12, 2),       # dense + holes: edge_t_pair<ct=2,full=1,nf=2,p2=0,tr=-1>/fmt0 (+2)
+    (64, 450, 450, 6, 2, 64, 8, 12, 2),         # dense + holes: edge_t_pair<ct=1,full=1,nf=2,p2=0,tr=-1>/fmt1 (+1)
+    (70, 450, 450, 6, 3, 256, 8, 12, 2),        # dense + holes: param_grad<ch16=4,nfr=1,p2=0>/y4
+    (72, 450, 450, 6, 3, 192, 128, 12, 2),      # dense + holes: param_grad<ch16=4,nfr=1,p2=0>/y3
+    (75, 450, 450, 6, 6, 192, 32, 12, 2),       # dense + holes: edge_t_pair<ct=2,full=0,nf=2,p2=0,tr=-1>/fmt1 (+3)
+    (84, 450, 450, 6, 2, 32, 13, 12, 2),        # dense + holes: edge_dx<ct=1,p2=0> (+2)
+    (85, 300, 600, 3, 1, 16, 256, 5, 2),        # holes: edge_t_pair<ct=2,full=1,nf=1,p2=1,tr=1>/fmt1 (+1)
+    (93, 450, 450, 6, 1, 64, 8, 12, 2),         # dense + holes: edge_t_single<vw=2,fc=1,full=1,t24=1>/p2=0
+    (106, 450, 450, 6, 1, 80, 13, 12, 2),       # dense + holes: edge_t_pair<ct=2,full=0,nf=1,p2=0,tr=-1>/fmt0
+    (107, 350, 500, 2, 3, 192, 128, 18, 1),     # dense: edge_t_pair<ct=2,full=0,nf=1,p2=1,tr=0>/fmt1 (+2)
+    (118, 450, 450, 6, 2, 320, 13, 12, 2),      # dense + holes: edge_t_pair<ct=2,full=0,nf=2,p2=0,tr=-1>/fmt0 (+1)
+    (119, 600, 150, 3, 1, 48, 192, 5, 2),       # holes: edge_t_pair<ct=2,full=0,nf=1,p2=1,tr=1>/fmt1 (+1)
+    (122, 450, 450, 6, 1, 32, 13, 12, 2),       # dense + holes: edge_t_single<vw=1,fc=1,full=1,t24=0>/p2=0
+    (126, 450, 450, 6, 2, 16, 8, 12, 2),         # dense + holes: param_grad<ch16=1,nfr=2,p2=0>/y1
+    (127, 350, 500, 1, 3, 256, 13, 18, 1),      # dense: edge_t_pair<ct=2,full=1,nf=1,p2=1,tr=0>/fmt0 (+1)
+    (128, 450, 450, 3, 6, 48, 32, 12, 2),       # dense + holes: the only dense run of edge_t_single<vw=1,fc=1,full=1,t24=1>/p2=0; the only run with holes of edge_t_single<vw=1,fc=1,full=1,t24=1>/p2=0 (+1)
+    (129, 600, 150, 3, 2, 64, 13, 5, 2),        # holes: the only run with holes of edge_t_pair<ct=1,full=1,nf=2,p2=0,tr=-1>/fmt0
+    (131, 450, 450, 6, 1, 64, 13, 12, 2),       # dense + holes: edge_t_single<vw=2,fc=1,full=1,t24=0>/p2=0
+    (133, 450, 450, 6, 1, 128, 13, 12, 2),      # dense + holes: edge_t_pair<ct=2,full=1,nf=1,p2=0,tr=-1>/fmt0
+    (139, 450, 450, 6, 2, 256, 8, 12, 2),       # dense + holes: param_grad_pair<ch16=4,p2=0>/pipe/y4
+    (140, 300, None, 1, 6, 256, 2, 18, 1),      # dense: edge_t_pair<ct=2,full=1,nf=2,p2=1,tr=0>/fmt0 (+1)
+    (145, 600, 150, 1, 1, 320, 13, 12, 2),      # holes: edge_t_pair<ct=2,full=0,nf=1,p2=1,tr=0>/fmt0 (+1)
+    (146, 300, None, 6, 6, 48, 8, 18, 1),       # dense: the only dense run of param_grad<ch16=3,nfr=2,p2=0>/y1
+    (153, 600, 150, 1, 1, 32, 13, 12, 2),       # holes: edge_t_single<vw=1,fc=1,full=1,t24=0>/p2=1
+    (158, 600, 150, 1, 1, 48, 8, 12, 2),        # holes: param_grad<ch16=3,nfr=1,p2=1>/y1
+    (164, 600, 150, 1, 2, 32, 13, 12, 2),       # holes: edge_t_single<vw=1,fc=2,full=1,t24=0>/p2=1
+    (182, 600, 150, 1, 2, 80, 13, 12, 2),       # holes: edge_t_pair<ct=2,full=0,nf=2,p2=1,tr=0>/fmt0
+    (183, 300, None, 6, 1, 8, 8, 18, 1),        # dense: the only dense run of param_grad<ch16=1,nfr=1,p2=0>/y1
+    (184, 300, None, 6, 1, 48, 8, 18, 1),       # dense: the only dense run of param_grad<ch16=3,nfr=1,p2=0>/y1
+    (185, 300, None, 6, 2, 64, 13, 18, 1),      # dense: the only dense run of edge_t_pair<ct=1,full=1,nf=2,p2=0,tr=-1>/fmt0
+    (188, 300, None, 2, 1, 24, 128, 14, 1),       # for the SE3_DX_PATH=1 child, where every 128-channel row with even F_out goes edge-major: edge_t_pair<ct=2,full=1,nf=2,p2=1,tr=1>/fmt1
+    (186, 1400, 600, 6, 1, 320, 40, 10, 2),     # rows: gemm_nn_bf16<mode=0,fast=1,nb=2>
+    (187, 1900, 600, 6, 1, 320, 64, 10, 2),     # rows: edge_t_stream_pair<tr=1> (+1)
+]
+
+
+@functools.lru_cache(maxsize=None)
+def form_case_oracle(case):
+    """The CPU side of a FORM_CASES row, computed once for both tests and every arithmetic mode: the generator's output, the
+    oracle's edges and the oracle's forward + backward.  Nobody writes to it."""
+    c = random_case(*case)
     nb_ref, ends_ref = O.ball_query(c["pts_in"], c["pts_out"], c["bid_in"], c["bid_out"], c["r"])
+    rho, nu = torch.tensor(1.0 / c["r"]), torch.tensor(ends_ref.shape[0] / max(nb_ref.shape[0], 1))
+    ref = O.conv_forward_backward(c["pts_in"], c["pts_out"], c["fi"], c["fo"], nb_ref, c["x"], c["a"], c["b"], c["w"], rho, nu, c["go"])
+    return c, nb_ref, ends_ref, rho, nu, ref
+
+
+def run_case_against_oracle(c, f_in, f_out, amd, oracle=None):
+    """Ball query + operator forward/backward of one random case on the GPU against the oracle: returns the relative
+    errors of out / dx / dA / dbeta / dW (also used by tools/fuzz_parity.py) plus the geometry and reference edges.
+    oracle: (edges, ends, (out, dx, dA, dbeta, dW)) of the case where the caller has them already."""
+    nb_ref, ends_ref = oracle[:2] if oracle else O.ball_query(c["pts_in"], c["pts_out"], c["bid_in"], c["bid_out"], c["r"])
     nb, ends = amd.ops.ball_query(c["pts_in"].to(DEV), c["pts_out"].to(DEV), c["bid_in"].to(DEV), c["bid_out"].to(DEV), c["r"])
     assert torch.equal(ends.cpu(), ends_ref)
     assert torch.equal(canon_edges(nb), canon_edges(nb_ref))
 
     rho, nu = torch.tensor(1.0 / c["r"]), torch.tensor(ends_ref.shape[0] / max(nb_ref.shape[0], 1))
-    out_r, dx_r, da_r, db_r, dw_r = O.conv_forward_backward(c["pts_in"], c["pts_out"], c["fi"], c["fo"], nb_ref, c["x"],
-                                                           c["a"], c["b"], c["w"], rho, nu, c["go"])
+    out_r, dx_r, da_r, db_r, dw_r = oracle[2] if oracle else O.conv_forward_backward(
+        c["pts_in"], c["pts_out"], c["fi"], c["fo"], nb_ref, c["x"], c["a"], c["b"], c["w"], rho, nu, c["go"])
     geom = amd.ops.ConvGeometry.build(c["pts_in"].to(DEV), c["pts_out"].to(DEV), c["fi"].to(DEV), c["fo"].to(DEV), nb, ends)
     x = c["x"].to(DEV).requires_grad_(True)
     a, b, w = (c[k].to(DEV).requires_grad_(True) for k in ("a", "b", "w"))
@@ -235,6 +301,66 @@ def test_random_shapes_against_oracle(case, amd):
     assert torch.equal(te, torch.cumsum(deg_in, 0))
     srcs = torch.repeat_interleave(torch.arange(c["pts_in"].shape[0]), deg_in)
     assert torch.equal(canon_edges(torch.stack((ts, srcs), 1)), canon_edges(nb_ref))
+
+
+@pytest.mark.parametrize("case", FORM_CASES, ids=[f"seed{c[0]}" for c in FORM_CASES])
+def test_random_shapes_of_every_form_against_oracle(case, amd):
+    """FORM_CASES through the autograd node, as CASES above: every kernel form the library can pick runs against the fp64
+    oracle somewhere in the suite (tests/test_form_coverage.py holds the tables to that)."""
+    c, nb_ref, ends_ref, rho, nu, ref = form_case_oracle(case)
+    errs, _, _ = run_case_against_oracle(c, case[3], case[4], amd, oracle=(nb_ref, ends_ref, ref))
+    print(f"form case seed{case[0]} {amd.get_precision()}: " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
+    for key, err in errs.items():
+        assert err < tol(amd), (key, err)
+
+
+# The autograd node makes one request: every gradient, T kept where backward reads it.  The other requests -- a feature
+# gradient alone, parameter gradients alone from a saved T, both with and both without a saved T -- on every row where the
+# library's answer for that pair of calls differs in any line from its answer for the autograd node's (asked at collection
+# time, in any arithmetic mode): the weight gradient from U, from a saved T and from a recomputed T, and the plans without
+# a parameter branch, all behind the forms of this table.
+FORM_OTHER_REQUESTS = [(case, r) for case in FORM_CASES for r in FC.BACKWARD
+                       if any(r in FC.other_requests(case, p) for p in FC.PRECISIONS)]
+
+
+@pytest.mark.parametrize("case,req", FORM_OTHER_REQUESTS,
+                         ids=[f"seed{c[0]}-feat{r[1]}-params{r[2]}-t{r[3]}" for c, r in FORM_OTHER_REQUESTS])
+def test_every_form_case_under_the_other_requests(case, req, amd):
+    """Raw se3conv_forward / se3conv_backward with the request stated, against the same oracle results; and the one place
+    where se3conv_forms is held against the hardware: the stages that launched in the two calls (profile hooks) are the
+    stages it listed for them.  Every row of the table is here with at least two requests.  (The name keeps this test out
+    of the slice of tests/test_gpu_variants.py: what a switch changes for these rows it changes under the autograd node's
+    request too, which the children do run; tests/test_form_coverage.py checks that per environment.)"""
+    from se3conv3d_amd import _lib
+    ops, lib, prec = amd.ops, _lib.load(), amd.get_precision()
+    _, want_feat, want_params, have_t = req
+    c, nb_ref, ends_ref, rho, nu, ref = form_case_oracle(case)
+    ref = dict(zip(("out", "dx", "dA", "dbeta", "dW"), ref))
+    same = c["pts_out"] is c["pts_in"]
+    pts_in, fi = c["pts_in"].to(DEV), c["fi"].to(DEV)
+    pts_out, fo = (pts_in if same else c["pts_out"].to(DEV)), (fi if c["fo"] is c["fi"] else c["fo"].to(DEV))
+    geom = ops.ConvGeometry.build(pts_in, pts_out, fi, fo, nb_ref.to(torch.int32).to(DEV), ends_ref.to(torch.int32).to(DEV))
+    x, a, b, w, go = (c[k].to(DEV) for k in ("x", "a", "b", "w", "go"))
+    shp = geom.shape(case[5], case[6], 32, prec)
+    lib.se3_profile_reset(), lib.se3_profile_enable(1)
+    out, t_save = ops.se3conv_forward(geom, x, a, b, w, rho, nu, save_t=bool(have_t), precision=prec)
+    assert (t_save is not None) == bool(have_t)
+    dx, da, db, dw = ops.se3conv_backward(geom, x, a, b, w, rho, nu, t_save, go, bool(want_feat), bool(want_params), precision=prec)
+    torch.cuda.synchronize()
+    lib.se3_profile_enable(0)
+    buf = C.create_string_buffer(4096)
+    assert lib.se3_profile_tags(buf, len(buf)) == 0
+    launched = set(filter(None, buf.value.decode().split(",")))
+    lib.se3_profile_reset()
+    shape = (prec, shp.n_in, shp.n_out, shp.n_edges, shp.f_in, shp.f_out, shp.c_in, shp.c_out)
+    listed = {line.split(":", 1)[0] for call in FC.raw_calls(req) for line in FC.lines(shape, call)}
+    assert launched == listed, (sorted(launched), sorted(listed))
+    got = {"out": out, "dx": dx, "dA": da, "dbeta": db, "dW": dw}
+    assert {k for k, v in got.items() if v is not None} == {"out"} | ({"dx"} if want_feat else set()) | ({"dA", "dbeta", "dW"} if want_params else set())
+    errs = {k: rel_err(v, ref[k]) for k, v in got.items() if v is not None}
+    print(f"form case seed{case[0]} {prec} request {req[1:]}: " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
+    for key, err in errs.items():
+        assert err < tol(amd), (key, err)
 
 
 @pytest.mark.parametrize("scale", [8.0, 60.0, 3000.0])

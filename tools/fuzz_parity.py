@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Random-shape parity sweep (GPU operator vs the fp64 oracle): frames, channel counts, degrees, batch counts and
-input/output cloud sizes drawn at random.  usage: tools/fuzz_parity.py [n_cases] [seed]"""
+input/output cloud sizes drawn at random.  Prints the kernel forms every case takes (se3conv_forms) and ends with the forms
+the run reached that no table of the suite runs (tests/test_form_coverage.py keeps that list empty for the shapes it sweeps).
+usage: tools/fuzz_parity.py [n_cases] [seed]"""
 import os, sys, random
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,12 +10,26 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import se3conv3d_amd as amd
 from oracle import se3conv_oracle as O
 import test_gpu_parity as T
+import form_coverage_table as FC
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 24
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 worst = 0.0
+reached = {}
+
+
+def note_forms(label, geom, c_in, c_out, prec):
+    """the forms of the calls run_case_against_oracle makes (the autograd node's request) for this case"""
+    shp = geom.shape(c_in, c_out, 32, prec)
+    shape = (prec, shp.n_in, shp.n_out, shp.n_edges, shp.f_in, shp.f_out, shp.c_in, shp.c_out)
+    names = sorted(set().union(*(FC.forms(shape, r) for r in FC.module_requests(shape))))
+    for name in names:
+        reached.setdefault(name, label)
+    print("        forms: " + " ".join(names))
+
+
 for i in range(n_cases):
-    f_in, f_out = rng.choice([1, 2, 3, 4]), rng.choice([1, 2, 3, 4])
+    f_in, f_out = rng.choice([1, 2, 3, 4, 6]), rng.choice([1, 2, 3, 4, 6])
     c_in = rng.choice([1, 3, 8, 16, 24, 32, 48, 64, 80, 96, 128, 160, 192, 256, 320])
     c_out = rng.choice([5, 13, 32, 64, 96, 128, 192, 256])
     n_in = rng.choice([97, 200, 333, 500])
@@ -25,12 +41,13 @@ for i in range(n_cases):
     c = T.random_case(100 + i, n_in, n_out, f_in, f_out, c_in, c_out, k_deg, batches)
     for prec in ("bf16x3", "fp32", "bf16x3_t16"):
         amd.set_precision(prec)
-        errs, _, _ = T.run_case_against_oracle(c, f_in, f_out, amd)
+        errs, geom, _ = T.run_case_against_oracle(c, f_in, f_out, amd)
         m = max(errs.values())
         worst = max(worst, m / T.TOLS[prec])
         flag = "" if m < T.TOLS[prec] else "   <-- FAIL"
         print(f"case {i:2d} {prec:6s} F {f_in}->{f_out} C {c_in:3d}->{c_out:3d} n {n_in}->{n_out} k~{k_deg:2d} b{batches}: "
               f"max rel err {m:.2e}{flag}")
+        note_forms(f"case {i} {prec}", geom, c_in, c_out, prec)
 # larger clouds with narrow rows: >= 2048 output rows (strip GEMM), the grid search of the ball query, the two-stream
 # range of backward; sizes the CPU oracle still finishes in seconds
 for i in range(max(2, n_cases // 8)):
@@ -42,10 +59,14 @@ for i in range(max(2, n_cases // 8)):
     c = T.random_case(500 + i, n_in, rng.choice([None, None, 1200]), f, f, c_in, c_out, rng.choice([6, 9]), rng.choice([1, 2]))
     for prec in ("bf16x3", "fp32", "bf16x3_t16"):
         amd.set_precision(prec)
-        errs, _, _ = T.run_case_against_oracle(c, f, f, amd)
+        errs, geom, _ = T.run_case_against_oracle(c, f, f, amd)
         m = max(errs.values())
         worst = max(worst, m / T.TOLS[prec])
         flag = "" if m < T.TOLS[prec] else "   <-- FAIL"
         print(f"large {i} {prec:6s} F {f} C {c_in:3d}->{c_out:3d} n {n_in}: max rel err {m:.2e}{flag}")
+        note_forms(f"large {i} {prec}", geom, c_in, c_out, prec)
+in_tables = FC.covered()
+print("forms this run reached that no table of the suite runs: "
+      + (", ".join(f"{n} ({w})" for n, w in sorted(reached.items()) if n not in in_tables) or "none"))
 print(f"worst error / tolerance = {worst:.3f}")
 sys.exit(0 if worst < 1.0 else 1)

@@ -23,8 +23,8 @@
  *     nothing allocated) except the two-phase se3_ball_query_count / _store pair.  The library issues NO hipMemsetAsync
  *     (buffers are zeroed by kernels) and its sorts stay on rocPRIM's merge sort at every size: on the HIP runtime
  *     PyTorch 2.10 ships (7.0.51831, RCCL 2.26.6) a captured graph with memset nodes -- rocPRIM's one-sweep radix sort
- *     issues three per pass -- faults on replay once an RCCL collective has run between two replays (round 4,
- *     tools/debug_up_graph.py).
+ *     issues three per pass -- faults on replay once an RCCL collective has run between two replays (found in round 4
+ *     by replaying one captured piece of a step per process; the scripts are in the history).
  *   - return value: SE3_OK (0) or a negative SE3_ERR_* code; no exceptions cross the boundary.
  *
  * Layouts: points [N,3]; frames [N,F,9] = row-major 3x3 per (point,frame)

@@ -16,8 +16,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-# SE3_LIB_SUFFIX=_x builds (and _lib.py loads) lib/libse3conv_hip_x.so with its objects under lib/obj_x/: variant and
-# ablation builds (SE3_CXXFLAGS) of tools/*.sh never overwrite the library the tests and the bench ship with
+# SE3_LIB_SUFFIX=_x builds (and _lib.py loads) lib/libse3conv_hip_x.so with its objects under lib/obj_x/: another commit's
+# build or a variant build (SE3_CXXFLAGS) for tools/*.sh never overwrites the library the tests and the bench ship with
 SUFFIX = os.environ.get("SE3_LIB_SUFFIX", "")
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj" + SUFFIX) if SUFFIX else LIBDIR
@@ -49,8 +49,8 @@ def _stale(target: str, deps) -> bool:
 
 
 def _fingerprint() -> str:
-    """What the objects were compiled with: a change of flags (SE3_CXXFLAGS carries the ablation / variant defines of
-    tools/*.sh, some of which give deliberately wrong results) must rebuild everything, whatever the mtimes say."""
+    """What the objects were compiled with: a change of flags (SE3_CXXFLAGS carries the defines of a variant build, the
+    timeline build for one) must rebuild everything, whatever the mtimes say."""
     return hashlib.sha256(" ".join([ARCH, *FLAGS]).encode()).hexdigest()
 
 

@@ -22,6 +22,21 @@ thread_local FormSink* t_forms = nullptr;
 }  // namespace
 bool forms_only() { return t_forms != nullptr; }
 int forms_cu_count() { return t_forms ? t_forms->n_cu : 0; }
+const Switches& switches() {
+  static const Switches sw = [] {
+    Switches v{};
+    v.no_t24 = getenv("SE3_NO_T24") != nullptr;
+    v.no_pair = getenv("SE3_NO_PAIR") != nullptr;
+    v.pg_single = getenv("SE3_PG_SINGLE") != nullptr;
+    v.tr_merge_sort = getenv("SE3_TR_MERGE_SORT") != nullptr;
+    const char* dx = getenv("SE3_DX_PATH");
+    v.dx_path = dx ? atoi(dx) : -1;
+    const char* es = getenv("SE3_EDGE_STREAM");  // n > 0: n items; anything else: never
+    v.edge_stream_min_items = es ? (atoi(es) > 0 ? atoi(es) : INT32_MAX) : 4096;
+    return v;
+  }();
+  return sw;
+}
 int form_report(const char* tag, const char* fmt, ...) {  // tag == nullptr: a launch inside the stage reported last
   if (!t_forms) return SE3_OK;
   if (tag) t_forms->tag = tag;
@@ -308,7 +323,7 @@ void prepare_geometry(PrepBatch& pb, const se3conv_prepared* prep, const se3conv
 // tn_cols = the column count of the TN product that also reads the rows (0: none).  Any row count: the GEMMs that read the
 // rows walk them in blocks their 32-bit offsets reach (gemm_bf16.hip).
 int row_format(const se3conv_shape* s, const EdgeGeom& g, int channels, int tn_cols) {
-  static const bool on = getenv("SE3_NO_T24") == nullptr;
+  const bool on = !switches().no_t24;
   if (s->precision == SE3_PRECISION_BF16X3_T16 && kBasis == 32 && edge_t_bf16_t16_rows(g, channels) && tn_cols % 4 == 0)
     return 2;
   return on && kBasis == 32 && channels % 2 == 0 && edge_t_bf16_t24_rows(g, channels) && tn_cols % 4 == 0 ? 1 : 0;
@@ -379,10 +394,7 @@ struct BwdPlan {
 // and gathered, plus grad_T when the parameter gradients do not need it anyway -- with a factor of two in favour of the
 // default.  SE3_DX_PATH=0 never, =1 whenever implemented (tests force both on the same shapes).
 bool plan_edge_major(const se3conv_shape* s, bool want_params) {
-  static const int mode = [] {
-    const char* e = getenv("SE3_DX_PATH");
-    return e ? atoi(e) : -1;
-  }();
+  const int mode = switches().dx_path;
   if (mode == 0 || s->precision == SE3_PRECISION_FP32) return false;
   if (s->n_in == 0 || s->n_out == 0) return false;
   if (!edge_dx_bf16_applicable(forward_geom(s), s->c_in)) return false;

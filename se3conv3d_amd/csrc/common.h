@@ -362,18 +362,13 @@ __device__ __forceinline__ void load_geom_record(const __amdgpu_buffer_rsrc_t rs
 // span although they hold the same work to 5 % (profiles/r06_edge_timeline.txt) -- a fifth of the slot time is idle and the
 // last wavefront runs alone, where nothing covers its latencies.  Every wavefront therefore takes priority
 // (step + its slot) mod 4 and moves on by one every chunk: each is the preferred one a quarter of the time.
-#ifndef SE3_ROTATE_PRIO
-#define SE3_ROTATE_PRIO 1
-#endif
 __device__ __forceinline__ void rotate_priority(int step_plus_slot) {
-#if SE3_ROTATE_PRIO
   switch (step_plus_slot & 3) {
     case 0: __builtin_amdgcn_s_setprio(0); break;
     case 1: __builtin_amdgcn_s_setprio(1); break;
     case 2: __builtin_amdgcn_s_setprio(2); break;
     default: __builtin_amdgcn_s_setprio(3); break;
   }
-#endif
 }
 __device__ __forceinline__ int wave_slot_id() { return (int)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (3 << 11)) ; }  // HW_ID[3:0]
 
@@ -385,6 +380,15 @@ __device__ __forceinline__ int wave_slot_id() { return (int)__builtin_amdgcn_s_g
 bool forms_only();                                         // a query is running on this thread: no device call of any kind
 int forms_cu_count();                                      // the CU count the query was given (resident grids are sized by it)
 int form_report(const char* tag, const char* fmt, ...) __attribute__((format(printf, 2, 3)));  // one line; returns SE3_OK
+
+// The runtime switches of the library (appendix of include/se3conv.h: what each one means and which tool or test sets it).
+// Every decision function reads them here and nowhere else.
+struct Switches {
+  bool no_t24, no_pair, pg_single, tr_merge_sort;  // SE3_NO_T24, SE3_NO_PAIR, SE3_PG_SINGLE, SE3_TR_MERGE_SORT: set at all
+  int dx_path;                // SE3_DX_PATH.  -1: cost model, 0: never, 1: wherever implemented
+  int edge_stream_min_items;  // SE3_EDGE_STREAM.  4096 by default
+};
+const Switches& switches();   // the process's switches, read from the environment once, at first use (api.hip)
 
 inline int check_launch() {
   if (forms_only()) return SE3_OK;
@@ -402,7 +406,8 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Fill `n_words` 32-bit words with `value` by a kernel (prep.hip).  Used wherever hipMemsetAsync would do: a memset NODE of
 // a captured graph faults on replay once an RCCL collective has run between two replays on the HIP runtime PyTorch 2.10
-// ships (7.0.51831) -- round 4, tools/debug_up_graph.py; kernel nodes and device-to-device copy nodes are fine.
+// ships (7.0.51831) -- found in round 4 by replaying an up-convolution's capture mode by mode (the scripts are in the
+// history); kernel nodes and device-to-device copy nodes are fine.
 int launch_fill_words(void* dst, uint32_t value, int64_t n_words, hipStream_t stream);
 
 // Optional per-kernel timing (se3_profile_* in se3conv.h): when enabled every launcher brackets its

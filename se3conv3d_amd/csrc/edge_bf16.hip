@@ -14,10 +14,11 @@
 //
 // Kernels in this file:
 //   edge_t_pair_bf16_kernel<CT, FULL, NF>   default for C >= 64: a wave pair per item (two frames, or one row for odd F)
+//   edge_t_stream_bf16_kernel<TR>           chunk-stream form of the wave pair: resident workgroups, 64-channel rows
 //   edge_t_bf16_kernel<VW, FC, FULL>        single wavefront per item (edge_bf16_body.h), used for C < 64
+//   edge_t_stream1_bf16_kernel<VW, FC, TR>  chunk-stream form of the single wavefront: resident workgroups, 32-channel rows
 //   edge_param_grad_bf16_v2_kernel<CH16, NFR>  parameter gradients, 64-channel blocks over blockIdx.y
 //   edge_param_grad_bf16_kernel             generic fallback (channel counts that are not multiples of 16)
-#include <cstdlib>
 
 // T / U rows leave the wave-pair kernel through non-temporal stores: the kernel is VALU-bound and does not care, and
 // the kernel that follows it (the GEMM reading those rows) no longer runs against the write-back of ~300 MB of dirty
@@ -185,21 +186,17 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : (FC == 1 ? 3 : 2)) void edge_t_b
 // 4 waves/SIMD); CT = 2: 128 channels per pass.  Wider rows take several passes, each recomputing phi (the MFMA
 // work per pass grows with CT, the GELU work does not).  FULL: C is a multiple of 64*CT.
 // ------------------------------------------------------------------------------------------------
-#ifndef SE3_PAIR_WAVES
-#define SE3_PAIR_WAVES 4
-#endif
-#ifndef SE3_PAIR2_WAVES
-#define SE3_PAIR2_WAVES 2  // wavefronts per SIMD of the two-tile form (rows of 128 channels and up).  At 3 (168 VGPRs) it spilled
-                           // 48 - 64 bytes per lane to scratch and was 1 % slower (dfaust_f2 stack 2.02 vs 2.00 ms, a 128-channel
-                           // layer 4.67 vs 4.63 ms, profiles/r04_pair2_waves_ab.txt); no kernel the shipped configurations launch uses scratch now
-#endif
+constexpr int kPairWaves = 4;
+constexpr int kPair2Waves = 2;  // wavefronts per SIMD of the two-tile form (rows of 128 channels and up).  At 3 (168 VGPRs) it spilled
+                                // 48 - 64 bytes per lane to scratch and was 1 % slower (dfaust_f2 stack 2.02 vs 2.00 ms, a 128-channel
+                                // layer 4.67 vs 4.63 ms, profiles/r04_pair2_waves_ab.txt); no kernel the shipped configurations launch uses scratch now
 // (The ablation builds of rounds 2 - 5 -- SE3_PAIR_ABLATE, SE3_PG_ABLATE, SE3_ABLATE: kernels with one ingredient taken out,
 // wrong results, for the "what bounds them" tables of profiles/README.md -- were removed in round 6 with the questions they
 // answered; the commits that produced a table hold the code that produced it.)
 // POW2: fnb_shift >= 0 is known (no division path, no branch on it).  TR: 0 forward, 1 transposed pass, -1 decided by
 // g.transposed at run time (both descriptor paths in the loop)
 template <int CT, bool FULL, int NF, bool POW2 = false, int TR = -1>
-__global__ __launch_bounds__(128, CT == 1 ? (POW2 ? SE3_PAIR_WAVES : 3) : (FULL ? SE3_PAIR2_WAVES : 2)) void edge_t_pair_bf16_kernel(
+__global__ __launch_bounds__(128, CT == 1 ? (POW2 ? kPairWaves : 3) : (FULL ? kPair2Waves : 2)) void edge_t_pair_bf16_kernel(
     EdgeGeom g, const uint32_t* __restrict__ feat, int C, int64_t feat_rows, const float* __restrict__ axes_ext,
     const float* __restrict__ rho_p, uint32_t* __restrict__ t_out, int64_t item_lo, int64_t n_items, int fnb_shift,
     int t24) {
@@ -441,7 +438,7 @@ struct ChunkCursor {
 };
 
 template <int TR>
-__global__ __launch_bounds__(128, SE3_PAIR_WAVES) void edge_t_stream_bf16_kernel(
+__global__ __launch_bounds__(128, kPairWaves) void edge_t_stream_bf16_kernel(
     EdgeGeom g, const uint32_t* __restrict__ feat, int64_t feat_rows, const float* __restrict__ axes_ext,
     const float* __restrict__ rho_p, char* __restrict__ t_out, uint32_t item_lo, uint32_t item_hi, int fnb_shift) {
   constexpr int C = 64, row_bytes = C * 4;
@@ -1009,19 +1006,17 @@ __global__ __launch_bounds__(256) void edge_param_grad_bf16_kernel(EdgeGeom g, c
 // a wave-private LDS image (CH16 * 4 KB per wavefront; in registers they cost CH16 * 16 VGPRs and spilled),
 // hence 512-thread blocks: 8 wavefronts share the CU's LDS at the same 2 waves/SIMD as before.
 // ------------------------------------------------------------------------------------------------
-#ifndef SE3_PG_PAIR_WAVES
-#define SE3_PG_PAIR_WAVES 3  // wavefronts per SIMD the pair form's register budget is set for.  (A lean form at 4 -- 19 KB of LDS,
-#endif                       // MLP weights in registers, one descriptor image per wavefront -- was 2 % slower: r02_param_grad_lean_ab.)
-#ifndef SE3_PG_SINGLE_WAVES
-#define SE3_PG_SINGLE_WAVES 3  // one frame per wavefront (odd F).  4 (40 KB of LDS per 4-wave workgroup = 4 per CU) was measured:
-#endif                         // at 128 VGPRs the 64-channel form spills 11 registers and runs 0.65 instead of 0.47 ms (ScanNet-like)
+constexpr int kPgPairWaves = 3;    // wavefronts per SIMD the pair form's register budget is set for.  (A lean form at 4 -- 19 KB of LDS,
+                                   // MLP weights in registers, one descriptor image per wavefront -- was 2 % slower: r02_param_grad_lean_ab.)
+constexpr int kPgSingleWaves = 3;  // one frame per wavefront (odd F).  4 (40 KB of LDS per 4-wave workgroup = 4 per CU) was measured:
+                                   // at 128 VGPRs the 64-channel form spills 11 registers and runs 0.65 instead of 0.47 ms (ScanNet-like)
 // PAIR (round 2, two frames only): a 128-thread workgroup = two wavefronts share ONE item -- one grad_T image (16 KB
 // instead of 16 KB per wavefront: 26 KB of LDS per workgroup, 6 workgroups = 3 wavefronts per SIMD instead of 2),
 // wavefront v builds the image of frame v (32 of the 64 row loads) and takes the chunks v, v + 2, ... of the item for
 // both frames; two workgroup barriers per item (image built / image free), partial sums folded per workgroup.
 // POW2: the neighbour cloud's frame count is a power of two (fnb_shift >= 0) -- no division path, no branch on it
 template <int CH16, int NFR, bool PAIR = false, bool POW2 = false>  // NFR = frames per wavefront: 2 (even F) or 1 (odd F: both lane halves hold the frame)
-__global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_PAIR_WAVES : (NFR == 2 ? 2 : (CH16 == 3 ? 3 : SE3_PG_SINGLE_WAVES))) void edge_param_grad_bf16_v2_kernel(EdgeGeom g, const uint32_t* __restrict__ feat,
+__global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? kPgPairWaves : (NFR == 2 ? 2 : (CH16 == 3 ? 3 : kPgSingleWaves))) void edge_param_grad_bf16_v2_kernel(EdgeGeom g, const uint32_t* __restrict__ feat,
                                                                          int row_ch, int64_t feat_rows,
                                                                          const float* __restrict__ axes_ext,
                                                                          const float* __restrict__ rho_p,
@@ -1064,9 +1059,6 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
   // Items are taken last-to-first: grad_T was written front-to-back by the GEMM just before this kernel, so its tail
   // (what fits the memory-side cache) is still on chip -- reading it first turns those rows into cache hits instead of
   // letting the front-to-back walk evict them unread (0.492 -> 0.477 ms).
-#ifndef SE3_PG_REVERSE
-#define SE3_PG_REVERSE 1
-#endif
   // Software pipeline over the items (round 6): the centre's record and the ids of an item's first two chunks are issued
   // when this wavefront has finished its last chunk of the PREVIOUS item, i.e. in front of the barrier that frees the
   // image, into registers that item no longer uses: the barrier wait (the partner wavefront still on its chunk: 12 % of a
@@ -1078,7 +1070,7 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
   int v_lo = 0, v_hi = 0;  // pipe: extents of local item `lane`
   if (pipe) {
     const int64_t item_f = min((int64_t)blockIdx.x + (int64_t)lane * item_stride, n_items - 1);
-    const uint32_t ctr = (uint32_t)(item_lo + (SE3_PG_REVERSE ? n_items - 1 - item_f : item_f)) / (uint32_t)groups;
+    const uint32_t ctr = (uint32_t)(item_lo + (n_items - 1 - item_f)) / (uint32_t)groups;
     v_hi = g.ends[ctr];
     v_lo = g.ends[max((int)ctr - 1, 0)];
     if (ctr == 0) v_lo = 0;
@@ -1105,7 +1097,7 @@ __global__ __launch_bounds__(PAIR ? 128 : (NFR == 2 ? 512 : 256), PAIR ? SE3_PG_
   // pair form, both wavefronts skip their barriers); false: none left
   auto find_item = [&]() {
     for (; item_f < n_items; item_f += item_stride, ++local_j) {
-      item = item_lo + (SE3_PG_REVERSE ? n_items - 1 - item_f : item_f);  // items item_lo .. item_lo + n_items - 1
+      item = item_lo + (n_items - 1 - item_f);  // items item_lo .. item_lo + n_items - 1
       // rows < 2^31 (checked on the host), so 32-bit unsigned division is exact -- the 64-bit one is ~150 scalar instructions
       const int64_t ctr = (uint32_t)item / (uint32_t)groups;
       const int a0 = (int)((uint32_t)item - (uint32_t)ctr * (uint32_t)groups) * NFR;
@@ -1379,7 +1371,7 @@ int launch_split_pack(const float* src, uint32_t* dst, int64_t n, hipStream_t st
 // the single-wavefront kernel at two channels per lane is 5 % faster there since it is pipelined like the pair
 // (profiles/r03_f1_forms_ab.txt).  SE3_NO_PAIR=1: the single-wavefront kernel everywhere.
 static bool edge_t_bf16_uses_pair(const EdgeGeom& g, int channels) {
-  return channels >= 64 && getenv("SE3_NO_PAIR") == nullptr && !(channels == 64 && g.f_ctr % 2 == 1);
+  return channels >= 64 && !switches().no_pair && !(channels == 64 && g.f_ctr % 2 == 1);
 }
 
 // Which launches can write their rows in the 3-byte format: the wave-pair kernel, and the single-wavefront kernel at one
@@ -1394,15 +1386,6 @@ bool edge_t_bf16_t24_rows(const EdgeGeom& g, int channels) {
 // 2.25-byte rows (T16): the wave-pair kernel on full 64-channel passes (a lane's four consecutive registers are a block)
 bool edge_t_bf16_t16_rows(const EdgeGeom& g, int channels) {
   return channels % 64 == 0 && edge_t_bf16_uses_pair(g, channels);
-}
-
-// items below which the chunk-stream kernels are not used (SE3_EDGE_STREAM=n: n items; 0: never)
-static int edge_stream_min_items() {
-  static const int v = [] {
-    const char* e = getenv("SE3_EDGE_STREAM");
-    return e ? (atoi(e) > 0 ? atoi(e) : INT32_MAX) : 4096;
-  }();
-  return v;
 }
 
 static int device_cu_count() {  // of the current device (the resident grids are sized by it); <= 0: the query failed
@@ -1441,8 +1424,8 @@ static EdgeTBf16Form edge_t_bf16_form(const EdgeGeom& g, int channels, int rowfm
     f.nf = two ? 2 : 1, f.items = two ? rows / 2 : rows;
     // chunk-stream form (resident workgroups, the chunk pipeline running across item boundaries): 64-channel rows, two
     // frames per item, power-of-two neighbour frame count, 3-byte rows; SE3_EDGE_STREAM=0 keeps the one-item workgroups
-    if (channels == 64 && two && f.shift >= 0 && rowfmt == 1 && f.items >= edge_stream_min_items() && reach && f.items < (1ll << 31)) {
-      constexpr int per_cu = 2 * SE3_PAIR_WAVES;  // 18 KB of LDS and <= 128 VGPRs: eight two-wavefront workgroups per CU
+    if (channels == 64 && two && f.shift >= 0 && rowfmt == 1 && f.items >= switches().edge_stream_min_items && reach && f.items < (1ll << 31)) {
+      constexpr int per_cu = 2 * kPairWaves;  // 18 KB of LDS and <= 128 VGPRs: eight two-wavefront workgroups per CU
       f.kind = EdgeTBf16Form::stream_pair;
       f.wgs = (int64_t)n_cu * per_cu;  // resident workgroups only, whatever the level's size (windows of 64 items inside)
       if (f.wgs > f.items) f.wgs = f.items;
@@ -1460,7 +1443,7 @@ static EdgeTBf16Form edge_t_bf16_form(const EdgeGeom& g, int channels, int rowfm
   // four; <2, 1> (64-channel rows at one frame, the ScanNet scene: items of ONE chunk, so every chunk ends in its stores
   // and there is no pipeline to carry across) +1 %, and +6 % when squeezed to four wavefronts per SIMD (7 spilled
   // registers) -- those rows keep the one-item form.
-  if (t24 && f.shift >= 0 && channels == 32 && f.fc == 2 && f.items >= edge_stream_min_items() && reach && f.items < (1ll << 31)) {
+  if (t24 && f.shift >= 0 && channels == 32 && f.fc == 2 && f.items >= switches().edge_stream_min_items && reach && f.items < (1ll << 31)) {
     constexpr int per_cu = 3;  // = the kernel's launch bounds: resident workgroups only
     f.kind = EdgeTBf16Form::stream1, f.vw = 1;
     f.wgs = (int64_t)n_cu * per_cu;
@@ -1596,8 +1579,7 @@ static ParamGradBf16Form edge_param_grad_bf16_form(const EdgeGeom& g, int channe
   }
   // two frames per wavefront share the gather (2 waves/SIMD: 16 KB of gT fragments per wavefront); one row per
   // wavefront (odd F, or SE3_PG_SINGLE for any F) gathers each neighbour row once per centre frame but runs at 3
-  static const bool force_single = getenv("SE3_PG_SINGLE") != nullptr;
-  const bool two = g.f_ctr % 2 == 0 && !force_single;
+  const bool two = g.f_ctr % 2 == 0 && !switches().pg_single;
   f.items = two ? rows / 2 : rows;
   f.blocks_y = edge_param_grad_bf16_channel_blocks(channels);
   // pair form (two wavefronts share an item and its grad_T image, 3 wavefronts per SIMD).  32-channel rows (DFaust's

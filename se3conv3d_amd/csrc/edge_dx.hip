@@ -27,22 +27,18 @@
 //     function acc_row(8 s + j, h)), no lane moves data;
 //   * D[n, i] accumulates over both centre frames and both k-steps (24 MFMAs per chunk at 64 channels) and is stored as
 //     fp32 rows, 128 contiguous bytes per half-wavefront and register.
-#include <cstdlib>
-
 #include "common.h"
 #include "edge_bf16_body.h"
-
-#ifndef SE3_DX_WAVES
-#define SE3_DX_WAVES 3
-#endif
 
 namespace se3 {
 
 namespace {
 
+constexpr int kDxWaves = 3;  // wavefronts per SIMD the kernel's register budget is set for
+
 // CT = 32-channel tiles per workgroup: 1 (rows of 32 channels) or 2 (64-channel blocks over blockIdx.y)
 template <int CT, bool POW2>
-__global__ __launch_bounds__(128, SE3_DX_WAVES) void edge_dx_bf16_kernel(EdgeGeom g, const float* __restrict__ axes_ext,
+__global__ __launch_bounds__(128, kDxWaves) void edge_dx_bf16_kernel(EdgeGeom g, const float* __restrict__ axes_ext,
                                                               const float* __restrict__ rho_p,
                                                               const uint32_t* __restrict__ grad_t, int row_ch,
                                                               float* __restrict__ d_out, int64_t n_items, int fnb_shift) {

@@ -9,8 +9,6 @@
 //
 // These are streaming kernels: A (1 GB at the headline shape) is read once, so they are HBM-bound
 // as long as the MFMA side reaches ~1/3 of its peak.
-#include <cstdlib>
-
 #include <atomic>
 
 #include "common.h"
@@ -19,15 +17,7 @@ namespace se3 {
 
 namespace {
 
-#ifndef SE3_GEMM_ABLATE
-#define SE3_GEMM_ABLATE 0  // diagnostic builds: 1 no MFMA stage, 2 no LDS staging, 4 no barriers
-#endif
-#ifndef SE3_T16_ABLATE
-#define SE3_T16_ABLATE 0  // diagnostic builds of gemm_nn_t16_kernel (wrong results): 1 no decode, 2 no weight loads, 4 no MFMA stage
-#endif
-#ifndef SE3_GEMM_DEPTH
-#define SE3_GEMM_DEPTH 4
-#endif
+constexpr int kGemmDepth = 4;  // k-tiles of A in flight in gemm_nn_bf16_kernel (3, 4, 6 and 8 measured the same, see there)
 constexpr int BM = 128, BN = 64, BK = 32;
 constexpr int A_LD = BK + 4;   // words; 144-byte pitch keeps 16-byte alignment and spreads ds_read_b128 over all banks
 constexpr int B_LD = BK + 8;   // bf16;  80-byte pitch, same properties
@@ -93,11 +83,6 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
       t.a1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, aoff + rstep, 0, 0));
       t.a2 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, aoff + 2 * rstep, 0, 0));
       t.a3 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, aoff + 3 * rstep, 0, 0));
-#if SE3_GEMM_ABLATE & 8
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) t.bh[nb] = t.bl[nb] = zero4;
-      return;
-#endif
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const uint32_t boff = (uint32_t)((((int64_t)(n0 + 64 * nb + (tid >> 2))) * kp + k0 + (tid & 3) * 8) * 2);
@@ -127,10 +112,6 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
 #pragma unroll
   for (int c = 0; c < 2 * NB; ++c) acc[c] = zero16();
   auto store_tile = [&](const Tile& t, int buf) {
-#if SE3_GEMM_ABLATE & 2
-    acc[0][0] += __uint_as_float(t.a0[0] ^ t.a1[1] ^ t.a2[2] ^ t.a3[3] ^ t.bh[0][0] ^ t.bl[0][1]);
-    return;
-#endif
     const int row = tid >> 3, kq = (tid & 7) * 4;
     *reinterpret_cast<u32x4*>(&as[buf][row][kq]) = t.a0;
     *reinterpret_cast<u32x4*>(&as[buf][row + 32][kq]) = t.a1;
@@ -145,9 +126,6 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
   };
 
   auto compute = [&](int buf) {
-#if SE3_GEMM_ABLATE & 1
-    return;
-#endif
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int kk = 16 * s + 8 * h;
@@ -166,10 +144,10 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
   // k-tile kt lives in register set (kt mod DEPTH) until it is written to LDS buffer (kt & 1).  The kernel's
   // occupancy is set by its LDS tiles (2 blocks per CU), which leaves 256 VGPRs per wavefront: they hold DEPTH
   // tiles in flight.  Measured on MI355X: 3, 4, 6 and 8 tiles give the same time, and so does the kernel with
-  // everything but the A loads removed (SE3_GEMM_ABLATE=15): 0.245 ms for 1.07 GB = 4.4 TB/s, while the same walk
+  // everything but the A loads removed (a diagnostic build of round 1): 0.245 ms for 1.07 GB = 4.4 TB/s, while the same walk
   // over a buffer that was not just written by the previous kernel reads at 5.8-6.3 TB/s (tools/probes/): the
   // producer's dirty lines are still draining from L2 / the memory-side cache into HBM while this kernel reads.
-  constexpr int DEPTH = SE3_GEMM_DEPTH;
+  constexpr int DEPTH = kGemmDepth;
   static_assert(DEPTH % 2 == 0, "the LDS buffer parity of a step must be a compile-time constant");
   Tile t[DEPTH];
 #pragma unroll
@@ -186,9 +164,7 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
       load_tile(t[u], kt0 + u + DEPTH);
       compute(u & 1);
       store_tile(t[(u + 1) % DEPTH], (u & 1) ^ 1);
-#if !(SE3_GEMM_ABLATE & 4)
       __syncthreads();
-#endif
     }
   }
   for (; kt0 < nk; kt0 += DEPTH) {
@@ -442,10 +418,6 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
     }
 #pragma unroll
     for (int j = 0; j < NBP; ++j) {
-#if SE3_T16_ABLATE & 2
-      t.bh[j] = t.bl[j] = u32x4{k0, k0, k0, k0};
-      continue;
-#endif
       const uint32_t off = ((uint32_t)(n0 + CP * j + (tid >> 3)) * (uint32_t)k + k0 + (uint32_t)((tid & 7) ^ ((j & 1) << 2)) * 8u) * 2u;
       t.bh[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(bh_rs, off, 0, 0));
       t.bl[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(bl_rs, off, 0, 0));
@@ -471,11 +443,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
       const u32x2 ev = q ? e[2 * g + 1] : e[2 * g];
       const uint32_t e2 = (s < 2 ? ev[0] : ev[1]) >> (16 * (s & 1));  // bytes 2 s, 2 s + 1 of the 8
       u32x4 vh, vl;
-#if SE3_T16_ABLATE & 1
-      vh = mw, vl = mw ^ u32x4{e2, e2, e2, e2};
-#else
       t16_unpack8(mw, e2, vh, vl);
-#endif
       const int row = (2 * g + (q ? 1 : 0)) * RP + r8;
       *reinterpret_cast<u32x4*>(&ash[buf][row][c4]) = vh;
       *reinterpret_cast<u32x4*>(&asl[buf][row][c4]) = vl;
@@ -490,9 +458,6 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
 #pragma unroll
   for (int ct = 0; ct < 2 * NB; ++ct) acc[ct] = zero16();
   auto compute = [&](int buf) {
-#if SE3_T16_ABLATE & 4
-    return;
-#endif
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int kk = 16 * s + 8 * h;
@@ -587,9 +552,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
 // as the MFMAs have issued and land during the epilogue.  Everything fits 128 VGPRs, so 4 wavefronts share a
 // SIMD and the 4096 strips of the headline shape are resident at once (the previous 64-column version needed
 // ~150 VGPRs: 3 per SIMD, i.e. a second, mostly empty round).  alpha is folded into the prepared weights.
-#ifndef SE3_STRIP_ROT
-#define SE3_STRIP_ROT 17
-#endif
+constexpr int kStripRot = 17;  // column tiles a strip's walk starts further on than its predecessor's ("Column order rotated" below)
 template <int KS>  // kp / 16: 2, 4 (k <= 64, 120 VGPRs) or 8 (k <= 128: twice the fragments, 3 waves per SIMD)
 __global__ __launch_bounds__(256, KS <= 4 ? 4 : 2) void gemm_strip_bf16_kernel(const uint32_t* __restrict__ a,
                                                                  const uint16_t* __restrict__ bt_hi,
@@ -685,7 +648,7 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : 2) void gemm_strip_bf16_kernel(c
   const int n_tiles = min(per, n_tiles_all - tile_lo);
   if (n_tiles <= 0) return;
   const int n_lo = tile_lo * 32, n_hi = min(n, (tile_lo + n_tiles) * 32);
-  int n0 = n_lo + (int)(((blockIdx.x * 4 + wave) * (unsigned)SE3_STRIP_ROT) % (unsigned)n_tiles) * 32;
+  int n0 = n_lo + (int)(((blockIdx.x * 4 + wave) * (unsigned)kStripRot) % (unsigned)n_tiles) * 32;
   load_b(n0);
   SE3_WAIT_B(0);
   // (rotating wave priority, common.h rotate_priority, was measured here too -- every strip is resident for the whole
@@ -701,9 +664,6 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : 2) void gemm_strip_bf16_kernel(c
     for (int r = 0; r < 16; r += 2) {
       uint32_t w0, w1;
       split_pack2(acc[r], acc[r + 1], w0, w1);
-#ifdef SE3_STRIP_NOSTORE
-      if ((w0 ^ w1) != 0x12345678u) continue;
-#endif
       __builtin_amdgcn_raw_buffer_store_b32(w0, c_rs, lane_off, (acc_row(r, 0) * n + n0) * 4, 0);
       __builtin_amdgcn_raw_buffer_store_b32(w1, c_rs, lane_off, (acc_row(r + 1, 0) * n + n0) * 4, 0);
     }
@@ -873,9 +833,6 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const uint32_t* __res
 
   f32x16 acc0 = zero16(), acc1 = zero16();
   auto compute = [&](int buf) {
-#if SE3_GEMM_ABLATE & 1
-    return;
-#endif
     if constexpr (A24) {
       const int grp = lane >> 4, q = (lane >> 2) & 3, p4 = (lane & 3) * 4;
       const int col = 16 * (grp & 1) + p4;  // this lane's address: row q of the block, 4 columns from here

@@ -10,7 +10,6 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include <cstdlib>
 #include <limits>
 
 #include "common.h"
@@ -632,10 +631,8 @@ struct KeyLess {
 // block-sorted runs of 4 096 pairs (512 threads x 8) instead of the 1 024 its radix-sort front end uses below 1 M items -- two
 // merge launches fewer per sort (58 k pairs: 1 + 4 launches instead of 1 + 6), and the grid builds of a step are bound by
 // launches (27 sorts per DFaust step).  Stable either way, so equal keys keep their input order: same result, bit for bit.
-#ifndef SE3_SORT_RUN
-#define SE3_SORT_RUN 4096  // 0: hipcub::DeviceRadixSort's own choice (A/B)
-#endif
-using GridSortConfig = rocprim::merge_sort_config<512, 512, (SE3_SORT_RUN ? SE3_SORT_RUN : 4096) / 512>;
+constexpr int kSortRun = 4096;  // (against hipcub::DeviceRadixSort's own choice: profiles/r06_grid_sort_ab.txt)
+using GridSortConfig = rocprim::merge_sort_config<512, 512, kSortRun / 512>;
 template <class Key>
 hipError_t sort_pairs_no_scratch(void* temp, size_t& temp_bytes, const Key* kin, Key* kout, const int32_t* vin, int32_t* vout,
                                  int n, int begin_bit = 0, int end_bit = (int)sizeof(Key) * 8, hipStream_t stream = nullptr) {
@@ -651,7 +648,7 @@ hipError_t sort_pairs_no_scratch(void* temp, size_t& temp_bytes, const Key* kin,
     if (c > temp_bytes) temp_bytes = c;
     return e;
   }
-  if (SE3_SORT_RUN && n <= kRadixIsMergeLimit)
+  if (n <= kRadixIsMergeLimit)
     return rocprim::merge_sort<GridSortConfig>(temp, temp_bytes, kin, kout, vin, vout, (size_t)n, KeyLess(), stream);
   if (n <= kRadixIsMergeLimit) return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, stream);
   hipError_t e = hipMemcpyAsync(kout, kin, (size_t)n * sizeof(Key), hipMemcpyDeviceToDevice, stream);
@@ -1193,7 +1190,7 @@ extern "C" int se3_ball_query_capped(const float* pts_src, const float* pts_dst,
 // transposition used until then -- the captured level 1 -> 0 convolution next to a live communicator faulted in 7 of 7
 // runs, at the first replay behind the first barrier; the same graph with a merge sort (no memset) was clean, a counting
 // form with two hipMemsetAsync faulted again, the same form zeroing its arrays by a kernel is clean
-// (tools/debug_up_graph.py, tools/fault_bisect_memset.sh).  The one-sweep kernels also use scratch
+// (one captured piece of the step per process, mode by mode: the scripts are in the history).  The one-sweep kernels also use scratch
 // memory (80 bytes per lane), the only kernels of this file that do; sorts stay on scratch-free forms too.
 // The list arrives grouped by sample in ascending sample order and a sample lists a source at most once, so "stable sort
 // by source" = per source the ascending list of its samples: count per source (atomics), inclusive scan, scatter into
@@ -1379,7 +1376,7 @@ extern "C" int se3_csr_transpose_bounded(const int32_t* neighbors, int64_t n_row
     hipLaunchKernelGGL(tr_zero_kernel, dim3(blocks_for(n_src)), dim3(256), 0, stream, t_ends, (int32_t*)nullptr, n_src);
     return check_launch();
   }
-  static const bool force_merge = getenv("SE3_TR_MERGE_SORT") != nullptr;  // A/B and test switch: the fallback form everywhere
+  const bool force_merge = switches().tr_merge_sort;  // A/B and test switch: the fallback form everywhere
   // The counting form ranks every source's segment by itself: up to kTrSegLds entries per segment in registers / LDS, longer
   // ones from memory at L^2 / 64 steps of ONE wavefront -- fine for the odd long segment, seconds for a list whose segments
   // are all that long (a coarsest-level up-convolution handed over as a plain list: 1e5 .. 1e6 edges per source).  Lists

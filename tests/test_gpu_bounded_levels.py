@@ -15,7 +15,7 @@ from test_gpu_graph_nodes import HIP_GRAPH_NODE_TYPE_MEMSET, node_types
 pytestmark = pytest.mark.gpu
 
 # Sizes at which the work changes method (se3conv3d_amd/csrc/geometry.hip):
-#   4096   = SE3_SORT_RUN: up to there the sort is one block sort, beyond it block-sorted runs are merged;
+#   4096   = kSortRun (geometry.hip): up to there the sort is one block sort, beyond it block-sorted runs are merged;
 #   65536  = 16 runs: one merge pass more (the fifth), and the first size whose key kernels loop over more than 256 blocks.
 # Two further switches lie beyond what a seconds-long test holds: rocPRIM's merge-path form from 200 000 items on and
 # kRadixIsMergeLimit = 2^20 of sort_pairs_no_scratch (tests/test_gpu_large_clouds.py runs the unbounded call there).

@@ -4,8 +4,8 @@
 #
 #   tools/ab.sh <name> [--reps N] [--levels] [--bench-args "<args>"] <variant> [<variant> ...]
 #
-# A variant is "-" (the shipped library, default environment), "lib:<suffix>" (a variant build
-# lib/libse3conv_hip<suffix>.so made beforehand with SE3_LIB_SUFFIX=<suffix> SE3_CXXFLAGS="-D..." python -m
+# A variant is "-" (the shipped library, default environment), "lib:<suffix>" (another commit's build or a timeline build,
+# lib/libse3conv_hip<suffix>.so made beforehand with SE3_LIB_SUFFIX=<suffix> [SE3_CXXFLAGS=...] python -m
 # se3conv3d_amd.build -- cross-compiled in the build container, it travels with the snapshot), "env:VAR=val,VAR2=val"
 # (environment switches), or "lib:<suffix>+env:VAR=val".  Variants alternate inside every repetition, so box-to-box
 # and drift effects cancel.  One line per run: ms per step, single-layer ms, every stage time of the full-resolution

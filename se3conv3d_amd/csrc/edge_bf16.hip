@@ -12,10 +12,14 @@
 // words too.  The bf16 kernels evaluate GELU in its scaled form (common.h: gelu_scaled): T and U hold kGeluOut times
 // the reference's values, the consuming GEMM divides it out.
 //
-// Kernels in this file:
-//   edge_t_pair_bf16_kernel<CT, FULL, NF>   default for C >= 64: a wave pair per item (two frames, or one row for odd F)
+// Kernels in this file.  The pieces of a chunk are written once in edge_bf16_body.h (feature-word gather, GELU + split,
+// wave-pair chunk, single-wavefront chunk, 3-byte row store, the cursor of the chunk streams).  The two chunk-stream kernels
+// are assembled from them: what they hold is the cursor instantiation and their loop with its pins, waits and barrier.  The
+// two one-item kernels take gelu_frags, pair_mlp and t24_store2 and keep their own text of the other pieces: every helper
+// shape tried for them moved their waits or registers (profiles/edge_chunk_body.txt).
+//   edge_t_pair_bf16_kernel<CT, FULL, NF, POW2, TR>  default for C >= 64: a wave pair per item (two frames, or one row for odd F)
 //   edge_t_stream_bf16_kernel<TR>           chunk-stream form of the wave pair: resident workgroups, 64-channel rows
-//   edge_t_bf16_kernel<VW, FC, FULL>        single wavefront per item (edge_bf16_body.h), used for C < 64
+//   edge_t_bf16_kernel<VW, FC, FULL, T24>   single wavefront per item (edge_item_bf16), used for C < 64
 //   edge_t_stream1_bf16_kernel<VW, FC, TR>  chunk-stream form of the single wavefront: resident workgroups, 32-channel rows
 //   edge_param_grad_bf16_v2_kernel<CH16, NFR>  parameter gradients, 64-channel blocks over blockIdx.y
 //   edge_param_grad_bf16_kernel             generic fallback (channel counts that are not multiples of 16)
@@ -157,12 +161,7 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : (FC == 1 ? 3 : 2)) void edge_t_b
     edge_item_bf16<VW, FC, FULL>(g, feat_rs, channels, lds_w, *rho_p, item, fnb_shift,
                                  [&](int a, int ch0, int, float x0, float x1, bool ok0, bool ok1) {
                                    if (!ok0) return;  // channels is even and ch0 is: ok1 == ok0
-                                   uint32_t hp, lp;
-                                   t24_pack2(x0, ok1 ? x1 : 0.f, hp, lp);
-                                   char* row = rows + a * t24_row_bytes(channels);
-                                   const int idx = (ch0 >> 1) * kBasis + kcol;
-                                   __builtin_nontemporal_store(hp, reinterpret_cast<uint32_t*>(row) + idx);
-                                   __builtin_nontemporal_store((uint16_t)lp, reinterpret_cast<uint16_t*>(row + (int64_t)row_words * 2) + idx);
+                                   t24_store2(rows + a * t24_row_bytes(channels), channels, ch0, kcol, x0, ok1 ? x1 : 0.f);
                                  });
   } else {
     uint32_t* t_rows = t_out + item * FC * (int64_t)channels * kBasis;  // rows FC*item .. FC*item + FC-1
@@ -288,8 +287,10 @@ __global__ __launch_bounds__(128, CT == 1 ? (POW2 ? kPairWaves : 3) : (FULL ? kP
       nb_b = nbr_of(c0 + 64);
 
       // gathered feature words for this wavefront's channels (shared by both frames): all loads go out now and are
-      // only turned into MFMA fragments after the barrier below
-      uint32_t fw[CT][2][8];
+      // only turned into MFMA fragments after the barrier below.  (Written out here, like the publish and aggregate
+      // loops and the row-store loop below, and not taken from edge_bf16_body.h as the stream kernel does: with any of
+      // those helpers this kernel's waits and address arithmetic come out otherwise, profiles/edge_chunk_body.txt.)
+      uint32_t fw[2][CT][8];
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(128, CT == 1 ? (POW2 ? kPairWaves : 3) : (FULL ? kP
           const int src_off = __builtin_amdgcn_ds_bpermute(hb + 4 * acc_row(8 * s + j, 0), qoff);
 #pragma unroll
           for (int t = 0; t < CT; ++t)
-            fw[t][s][j] = __builtin_amdgcn_raw_buffer_load_b32(feat_rs, ch_ok[t] ? src_off + cb4[t] : kOobOffset, 0, 0);
+            fw[s][t][j] = __builtin_amdgcn_raw_buffer_load_b32(feat_rs, ch_ok[t] ? src_off + cb4[t] : kOobOffset, 0, 0);
         }
       load_geom_record(nbg_rs, q_b, xn_nx, rn_nx);
       q_a = q_b;
@@ -310,35 +311,22 @@ __global__ __launch_bounds__(128, CT == 1 ? (POW2 ? kPairWaves : 3) : (FULL ? kP
         edge_descriptor(xn, rn, yc, rc, rho, d);
       else
         edge_descriptor(yc, rc, xn, rn, rho, d);
-
-      // kernel MLP + GELU for this wavefront's frame; both lane halves hold the same descriptor: half 0 feeds
-      // dims 0..7, half 1 dims 8, 9
-      {
-        float v[8];
+      const f32x16 phi = pair_mlp(d, lane, lds_w);  // kernel MLP for this wavefront's frame
+      TL(tl_pin(phi[0]); tl_mark(tl_rec, tl_ch + 3);)
+      // GELU + split, published as pair_publish<NF> does
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = h ? (j == 0 ? d[8] : (j == 1 ? 1.0f : 0.f)) : d[j];
-        u32x4 a_hi, a_lo;
-        frags_from_floats(v, a_hi, a_lo);
-        const u32x4 wb_hi = *reinterpret_cast<const u32x4*>(&lds_w[0][0][lane][0]);
-        const u32x4 wb_lo = *reinterpret_cast<const u32x4*>(&lds_w[0][1][lane][0]);
-        const f32x16 phi = mfma_bf16x3(a_hi, a_lo, wb_hi, wb_lo, zero16());
-        TL(tl_pin(phi[0]); tl_mark(tl_rec, tl_ch + 3);)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          if (s * 16 < cnt && (NF == 2 || s == wv)) {
-            float pv[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pv[j] = gelu_scaled(phi[8 * s + j]);
-            u32x4 b_hi, b_lo;
-            frags_from_floats(pv, b_hi, b_lo);
-            *reinterpret_cast<u32x4*>(&lds_phi[buf][NF == 2 ? wv : 0][s][0][lane][0]) = b_hi;
-            *reinterpret_cast<u32x4*>(&lds_phi[buf][NF == 2 ? wv : 0][s][1][lane][0]) = b_lo;
-          }
+      for (int s = 0; s < 2; ++s) {
+        if (s * 16 < cnt && (NF == 2 || s == wv)) {
+          u32x4 b_hi, b_lo;
+          gelu_frags(phi, s, b_hi, b_lo);
+          *reinterpret_cast<u32x4*>(&lds_phi[buf][NF == 2 ? wv : 0][s][0][lane][0]) = b_hi;
+          *reinterpret_cast<u32x4*>(&lds_phi[buf][NF == 2 ? wv : 0][s][1][lane][0]) = b_lo;
         }
       }
       TL(tl_mark(tl_rec, tl_ch + 4);)
       __syncthreads();  // both frames' fragments of this chunk are published (other buffer is used next chunk)
       TL(tl_mark(tl_rec, tl_ch + 5); tl_pin(fw[0][0][7]); tl_mark(tl_rec, tl_ch + 6);)
+      // aggregation, as pair_aggregate<CT, NF> does
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if (s * 16 < cnt) {
@@ -351,7 +339,7 @@ __global__ __launch_bounds__(128, CT == 1 ? (POW2 ? kPairWaves : 3) : (FULL ? kP
 #pragma unroll
           for (int t = 0; t < CT; ++t) {
             u32x4 fa_hi, fa_lo;
-            frags_from_words(fw[t][s], fa_hi, fa_lo);
+            frags_from_words(fw[s][t], fa_hi, fa_lo);
 #pragma unroll
             for (int a = 0; a < NF; ++a) acc[a][t] = mfma_bf16x3(fa_hi, fa_lo, b_hi[a], b_lo[a], acc[a][t]);
           }
@@ -382,17 +370,13 @@ __global__ __launch_bounds__(128, CT == 1 ? (POW2 ? kPairWaves : 3) : (FULL ? kP
           }
           continue;
         }
-        if (t24) {  // 3-byte rows (common.h): channels c, c+1 of this lane = one hi word + one lo half-word
+        if (t24) {  // 3-byte rows (common.h)
           char* row = reinterpret_cast<char*>(t_out) + (item * NF + a) * t24_row_bytes(C);
 #pragma unroll
           for (int r = 0; r < 16; r += 2) {
             const int ch = ch0 + acc_row(r, h);  // even
             if (!FULL && ch >= C) continue;
-            uint32_t hp, lp;
-            t24_pack2(acc[a][t][r], (FULL || ch + 1 < C) ? acc[a][t][r + 1] : 0.f, hp, lp);
-            const int idx = (ch >> 1) * kBasis + kcol;
-            __builtin_nontemporal_store(hp, reinterpret_cast<uint32_t*>(row) + idx);
-            __builtin_nontemporal_store((uint16_t)lp, reinterpret_cast<uint16_t*>(row + (int64_t)C * kBasis * 2) + idx);
+            t24_store2(row, C, ch, kcol, acc[a][t][r], (FULL || ch + 1 < C) ? acc[a][t][r + 1] : 0.f);
           }
           continue;
         }
@@ -428,15 +412,6 @@ __global__ __launch_bounds__(128, CT == 1 ? (POW2 ? kPairWaves : 3) : (FULL ? kP
 // neighbouring extents and write neighbouring rows, and a cloud's dense regions are spread over all of them.
 // Rows without neighbours are one chunk of zero frame-edges (every lane reads out of bounds: zero rows are stored).
 // ------------------------------------------------------------------------------------------------
-struct ChunkCursor {
-  int j;        // local item index; n_mine = past the end
-  int c0;       // first frame-edge of the chunk
-  int start;    // first edge of the item's centre point
-  int n_total;  // frame-edges of the item
-  int crow;     // this wavefront's centre row (record index)
-  uint32_t item;
-};
-
 template <int TR>
 __global__ __launch_bounds__(128, kPairWaves) void edge_t_stream_bf16_kernel(
     EdgeGeom g, const uint32_t* __restrict__ feat, int64_t feat_rows, const float* __restrict__ axes_ext,
@@ -454,82 +429,28 @@ __global__ __launch_bounds__(128, kPairWaves) void edge_t_stream_bf16_kernel(
   const __amdgpu_buffer_rsrc_t feat_rs = buffer_of(feat, feat_rows * row_bytes);
   const __amdgpu_buffer_rsrc_t nbg_rs = buffer_of(g.nb_geom, g.n_nb * g.f_nb * 64);
   const __amdgpu_buffer_rsrc_t nbr_rs = buffer_of(g.nbr, g.n_edges * g.nbr_stride * 4);  // ids past the list read 0
-  const uint32_t groups = (uint32_t)g.f_ctr / 2u;
   const uint32_t item0_wg = item_lo + blockIdx.x;
-  const int n_mine = (int)((item_hi - item0_wg + gridDim.x - 1) / gridDim.x);  // >= 1: the grid has at most one workgroup per item
-  const int fmask = (1 << fnb_shift) - 1;
+  const int n_all = (int)((item_hi - item0_wg + gridDim.x - 1) / gridDim.x);  // >= 1: the grid has at most one workgroup per item
   const int hb = 16 * h;
+  const int cb4[1] = {(32 * wv + kcol) * 4};
+  const bool ch_ok[1] = {true};
 
-  f32x16 acc[2] = {zero16(), zero16()};
+  f32x16 acc[2][1] = {{zero16()}, {zero16()}};  // [frame][tile]
   int buf = 0;
   int prio_step = wave_slot_id();
   // The workgroup's items in windows of 64: the row extents of a window sit in two registers (lane l = the window's l-th
   // item), the chunk pipeline is drained and restarted between two windows (one exposed round trip per 64 items).  A
   // level of up to 64 items per resident workgroup -- 131 072 items, the headline's 65 536 among them -- is one window.
-  const int n_all = n_mine;
+  // Wavefront wv's centre row is frame wv of the item.
+  ChunkStream<2> cs{g, nbr_rs, item0_wg, gridDim.x, n_all, wv, fnb_shift, kcol};
   for (int win0 = 0; win0 < n_all; win0 += 64) {
-  const int n_mine = min(64, n_all - win0);  // (the loop body below sees one window as "its" items)
-  const uint32_t item0 = item0_wg + (uint32_t)win0 * gridDim.x;
-  int v_lo, v_hi;
-  {
-    const uint32_t item = item0 + (uint32_t)min(lane, n_mine - 1) * gridDim.x;
-    const uint32_t ctr = item / groups;
-    v_hi = g.ends[ctr];
-    v_lo = g.ends[max((int)ctr - 1, 0)];
-    if (ctr == 0) v_lo = 0;
-  }
-  // (every cursor field is wave-uniform; readfirstlane says so to the compiler: scalar registers, scalar branches)
-  auto uni = [](int x) { return __builtin_amdgcn_readfirstlane(x); };
-  auto enter = [&](int j, int crow_keep, uint32_t item_keep) {  // first chunk of local item j, or the end mark
-    ChunkCursor c;
-    c.j = j, c.c0 = 0, c.start = 0, c.n_total = 0;
-    c.crow = crow_keep, c.item = item_keep;  // end mark: the last item's record stays the (valid) prefetch target
-    if (j < n_mine) {
-      const int lo = __builtin_amdgcn_readlane(v_lo, j), hi = __builtin_amdgcn_readlane(v_hi, j);
-      c.start = lo, c.n_total = (hi - lo) << fnb_shift;
-      c.item = item0 + (uint32_t)j * gridDim.x;
-      const uint32_t ctr = c.item / groups;
-      c.crow = uni((int)(ctr * (uint32_t)g.f_ctr + (c.item - ctr * groups) * 2u) + wv);
-    }
-    return c;
-  };
-  auto advance = [&](const ChunkCursor& c) {
-    ChunkCursor r = c;
-    if (c.c0 + 32 < c.n_total) r.c0 = c.c0 + 32;
-    else if (c.j < n_mine) r = enter(c.j + 1, c.crow, c.item);
-    r.j = uni(r.j), r.c0 = uni(r.c0), r.start = uni(r.start), r.n_total = uni(r.n_total), r.item = (uint32_t)uni((int)r.item);
-    return r;
-  };
-  auto fe_of = [&](const ChunkCursor& c) { return max(min(c.c0 + kcol, c.n_total - 1), 0); };
-  auto nbr_of = [&](const ChunkCursor& c) {
-    const int e = c.start + (fe_of(c) >> fnb_shift);
-    return (int)__builtin_amdgcn_raw_buffer_load_b32(nbr_rs, (e * g.nbr_stride + g.nbr_offset) * 4, 0, 0);
-  };
-  auto row_of = [&](int nb, const ChunkCursor& c) { return (nb << fnb_shift) + (fe_of(c) & fmask); };
-  // the centre's record is wave-uniform: read through the scalar cache (constant address space + a uniform index = s_load)
-  typedef const f32x4 __attribute__((address_space(4))) * crec_t;
-  const crec_t ctr_rec = (crec_t)(uintptr_t)g.ctr_geom;
-  auto centre = [&](const ChunkCursor& c, float yc[3], float rc[9]) {
-    const int row = c.crow;
-    const f32x4 v0 = ctr_rec[row * 4], v1 = ctr_rec[row * 4 + 1], v2 = ctr_rec[row * 4 + 2];
-    yc[0] = v0[0], yc[1] = v0[1], yc[2] = v0[2], rc[8] = v0[3];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rc[i] = v1[i], rc[4 + i] = v2[i];
-  };
-
-  ChunkCursor cur, n1, n2;
-  cur = enter(0, 0, 0u);
-  n1 = advance(cur);
-  n2 = advance(n1);
+  cs.window(win0, lane);
   // carried from chunk to chunk: the source rows of this chunk and of the next (ids consumed), this chunk's record
+  ChunkCursor cur, n1, n2;
   int q_cur, q_n1;
   float xn_nx[3], rn_nx[9];
+  cs.prime(nbg_rs, cur, n1, n2, q_cur, q_n1, xn_nx, rn_nx);
   {
-    const int nb_cur = nbr_of(cur);
-    const int nb_n1 = nbr_of(n1);
-    q_cur = row_of(nb_cur, cur);
-    load_geom_record(nbg_rs, q_cur, xn_nx, rn_nx);
-    q_n1 = row_of(nb_n1, n1);
     // (consumed in front of the loop like every chunk's loads are at its end, see below: the loop is entered with no load in flight)
 #pragma unroll
     for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(xn_nx[i]));
@@ -537,9 +458,9 @@ __global__ __launch_bounds__(128, kPairWaves) void edge_t_stream_bf16_kernel(
     for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(rn_nx[i]));
   }
   float yc[3], rc[9];
-  centre(cur, yc, rc);
+  cs.template centre<false>(cur, h, yc, rc);
 
-  while (cur.j < n_mine) {
+  while (cur.j < cs.n_mine) {
     rotate_priority(prio_step++);
     const int cnt = min(32, cur.n_total - cur.c0);  // <= 0: a row without neighbours
     // rows past the end of the neighbour list read out of bounds (buffer loads return 0): their phi needs no mask
@@ -549,99 +470,48 @@ __global__ __launch_bounds__(128, kPairWaves) void edge_t_stream_bf16_kernel(
     for (int i = 0; i < 3; ++i) xn[i] = xn_nx[i];
 #pragma unroll
     for (int i = 0; i < 9; ++i) rn[i] = rn_nx[i];
-    const int nb_n2 = nbr_of(n2);  // ids two chunks ahead
+    const int nb_n2 = cs.nbr_of(n2);  // ids two chunks ahead
 
     // gathered feature words for this wavefront's channels (shared by both frames): all loads go out now and are only
     // turned into MFMA fragments after the barrier below
-    uint32_t fw[2][8];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int src_off = __builtin_amdgcn_ds_bpermute(hb + 4 * acc_row(8 * s + j, 0), qoff);
-        fw[s][j] = __builtin_amdgcn_raw_buffer_load_b32(feat_rs, src_off + (32 * wv + kcol) * 4, 0, 0);
-      }
+    uint32_t fw[2][1][8];
+    gather_feature_words<1, 1>(feat_rs, hb, qoff, cb4, ch_ok, fw);
     load_geom_record(nbg_rs, q_n1, xn_nx, rn_nx);  // record one chunk ahead
     float yn[3], rnc[9];
-    centre(n1, yn, rnc);  // the next chunk's centre (the same record until the item changes)
+    cs.template centre<false>(n1, h, yn, rnc);  // the next chunk's centre (the same record until the item changes)
 
     if (TR == 0)
       edge_descriptor(xn, rn, yc, rc, rho, d);
     else
       edge_descriptor(yc, rc, xn, rn, rho, d);
-
-    // kernel MLP + GELU for this wavefront's frame; both lane halves hold the same descriptor: half 0 feeds dims 0..7,
-    // half 1 dims 8, 9
-    {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = h ? (j == 0 ? d[8] : (j == 1 ? 1.0f : 0.f)) : d[j];
-      u32x4 a_hi, a_lo;
-      frags_from_floats(v, a_hi, a_lo);
-      const u32x4 wb_hi = *reinterpret_cast<const u32x4*>(&lds_w[0][0][lane][0]);
-      const u32x4 wb_lo = *reinterpret_cast<const u32x4*>(&lds_w[0][1][lane][0]);
-      const f32x16 phi = mfma_bf16x3(a_hi, a_lo, wb_hi, wb_lo, zero16());
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        if (s * 16 < cnt) {
-          float pv[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) pv[j] = gelu_scaled(phi[8 * s + j]);
-          u32x4 b_hi, b_lo;
-          frags_from_floats(pv, b_hi, b_lo);
-          *reinterpret_cast<u32x4*>(&lds_phi[buf][wv][s][0][lane][0]) = b_hi;
-          *reinterpret_cast<u32x4*>(&lds_phi[buf][wv][s][1][lane][0]) = b_lo;
-        }
-      }
-    }
+    const f32x16 phi = pair_mlp(d, lane, lds_w);
+    pair_publish<2>(phi, cnt, wv, lane, lds_phi[buf]);
     __syncthreads();  // both frames' fragments of this chunk are published (the other buffer is used by the next chunk)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      if (s * 16 < cnt) {
-        u32x4 b_hi[2], b_lo[2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          b_hi[a] = *reinterpret_cast<const u32x4*>(&lds_phi[buf][a][s][0][lane][0]);
-          b_lo[a] = *reinterpret_cast<const u32x4*>(&lds_phi[buf][a][s][1][lane][0]);
-        }
-        u32x4 fa_hi, fa_lo;
-        frags_from_words(fw[s], fa_hi, fa_lo);
-#pragma unroll
-        for (int a = 0; a < 2; ++a) acc[a] = mfma_bf16x3(fa_hi, fa_lo, b_hi[a], b_lo[a], acc[a]);
-      }
-    }
+    pair_aggregate<1, 2>(lds_phi[buf], cnt, lane, fw, acc);
     // Every load this chunk issued is consumed HERE, in front of the stores: gfx9 counts loads and stores in one in-order
     // counter, so a wait behind the stores for a load issued before them would be a wait for the stores (and the
     // compiler's counts at the loop top must hold for the path without stores: they would drain them).  The next wait
     // behind the stores is for the next chunk's feature words, a few thousand cycles away.
     q_cur = q_n1;
-    q_n1 = row_of(nb_n2, n2);
+    q_n1 = cs.row_of(nb_n2, n2);
 #pragma unroll
     for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(xn_nx[i]));
 #pragma unroll
     for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(rn_nx[i]));
     if (n1.j != cur.j) {
-      // the item's last chunk: acc[a] register r, lane (kcol, h) = T[row 2 item + a][32 wv + acc_row(r, h)][kcol] leaves
-      // as 3-byte rows (channels c, c + 1 of this lane = one hi word + one lo half-word), non-temporal
+      // the item's last chunk: acc[a][0] register r, lane (kcol, h) = T[row 2 item + a][32 wv + acc_row(r, h)][kcol] leaves
+      // as 3-byte rows
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
-        char* row = t_out + ((int64_t)cur.item * 2 + a) * t24_row_bytes(C);
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          uint32_t hp, lp;
-          t24_pack2(acc[a][r], acc[a][r + 1], hp, lp);
-          const int idx = ((32 * wv + acc_row(r, h)) >> 1) * kBasis + kcol;
-          __builtin_nontemporal_store(hp, reinterpret_cast<uint32_t*>(row) + idx);
-          __builtin_nontemporal_store((uint16_t)lp, reinterpret_cast<uint16_t*>(row + (int64_t)C * kBasis * 2) + idx);
-        }
-        acc[a] = zero16();
+        t24_store_tile<true>(t_out + ((int64_t)cur.item * 2 + a) * t24_row_bytes(C), C, 32 * wv, h, kcol, acc[a][0]);
+        acc[a][0] = zero16();
       }
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) yc[i] = yn[i];
 #pragma unroll
     for (int i = 0; i < 9; ++i) rc[i] = rnc[i];
-    cur = n1, n1 = n2, n2 = advance(n2);
+    cur = n1, n1 = n2, n2 = cs.advance(n2);
     buf ^= 1;
     TL(++tl_chunks;)
   }
@@ -674,14 +544,13 @@ __global__ __launch_bounds__(256, (VW == 1 && FC == 1) ? 4 : 3) void edge_t_stre
   const __amdgpu_buffer_rsrc_t feat_rs = buffer_of(feat, feat_rows * row_bytes);
   const __amdgpu_buffer_rsrc_t nbg_rs = buffer_of(g.nb_geom, g.n_nb * g.f_nb * 64);
   const __amdgpu_buffer_rsrc_t nbr_rs = buffer_of(g.nbr, g.n_edges * g.nbr_stride * 4);  // ids past the list read 0
-  const uint32_t groups = (uint32_t)g.f_ctr / (uint32_t)FC;
   const uint32_t n_waves = gridDim.x * 4u;
   const uint32_t item0_wave = item_lo + (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
   // (a wavefront past the end of the range -- the last workgroup's -- has no items and falls through both loops)
   const int n_all = item0_wave < item_hi ? (int)((item_hi - item0_wave + n_waves - 1) / n_waves) : 0;
-  const int fmask = (1 << fnb_shift) - 1;
   const int hb = 16 * h;
-  const int cb4 = VW * kcol * 4;
+  const int cb4[1] = {VW * kcol * 4};
+  const bool ch_ok[1] = {true};
 
   f32x16 acc[FC][VW];
 #pragma unroll
@@ -689,83 +558,24 @@ __global__ __launch_bounds__(256, (VW == 1 && FC == 1) ? 4 : 3) void edge_t_stre
 #pragma unroll
     for (int t = 0; t < VW; ++t) acc[a][t] = zero16();
   int prio_step = wave_slot_id();
+  // this wavefront's items: item_lo + wavefront index + j * wavefronts of the grid; centre row = the item's first
+  ChunkStream<FC> cs{g, nbr_rs, item0_wave, n_waves, n_all, 0, fnb_shift, kcol};
   for (int win0 = 0; win0 < n_all; win0 += 64) {  // windows of 64 items, as above
-  const int n_mine = min(64, n_all - win0);
-  const uint32_t item0 = item0_wave + (uint32_t)win0 * n_waves;
-  int v_lo, v_hi;
-  {
-    const uint32_t item = item0 + (uint32_t)min(lane, n_mine - 1) * n_waves;
-    const uint32_t ctr = item / groups;
-    v_hi = g.ends[ctr];
-    v_lo = g.ends[max((int)ctr - 1, 0)];
-    if (ctr == 0) v_lo = 0;
-  }
-  auto uni = [](int x) { return __builtin_amdgcn_readfirstlane(x); };
-  auto enter = [&](int j, int crow_keep, uint32_t item_keep) {  // first chunk of local item j, or the end mark
-    ChunkCursor c;
-    c.j = j, c.c0 = 0, c.start = 0, c.n_total = 0;
-    c.crow = crow_keep, c.item = item_keep;
-    if (j < n_mine) {
-      const int lo = __builtin_amdgcn_readlane(v_lo, j), hi = __builtin_amdgcn_readlane(v_hi, j);
-      c.start = lo, c.n_total = (hi - lo) << fnb_shift;
-      c.item = item0 + (uint32_t)j * n_waves;
-      const uint32_t ctr = c.item / groups;
-      c.crow = uni((int)(ctr * (uint32_t)g.f_ctr + (c.item - ctr * groups) * (uint32_t)FC));  // the item's first centre row
-    }
-    return c;
-  };
-  auto advance = [&](const ChunkCursor& c) {
-    ChunkCursor r = c;
-    if (c.c0 + 32 < c.n_total) r.c0 = c.c0 + 32;
-    else if (c.j < n_mine) r = enter(c.j + 1, c.crow, c.item);
-    r.j = uni(r.j), r.c0 = uni(r.c0), r.start = uni(r.start), r.n_total = uni(r.n_total), r.item = (uint32_t)uni((int)r.item);
-    return r;
-  };
-  auto fe_of = [&](const ChunkCursor& c) { return max(min(c.c0 + kcol, c.n_total - 1), 0); };
-  auto nbr_of = [&](const ChunkCursor& c) {
-    const int e = c.start + (fe_of(c) >> fnb_shift);
-    return (int)__builtin_amdgcn_raw_buffer_load_b32(nbr_rs, (e * g.nbr_stride + g.nbr_offset) * 4, 0, 0);
-  };
-  auto row_of = [&](int nb, const ChunkCursor& c) { return (nb << fnb_shift) + (fe_of(c) & fmask); };
-  typedef const f32x4 __attribute__((address_space(4))) * crec_t;
-  const crec_t ctr_rec = (crec_t)(uintptr_t)g.ctr_geom;
-  // the centre record(s) of chunk c: through the scalar cache; FC = 2: the record of frame a0 + h per lane half
-  auto centre = [&](const ChunkCursor& c, float yc[3], float rc[9]) {
-    const int row = c.crow;
-    const f32x4 v0 = ctr_rec[row * 4], v1 = ctr_rec[row * 4 + 1], v2 = ctr_rec[row * 4 + 2];
-    if constexpr (FC == 2) {
-      const f32x4 w0 = ctr_rec[row * 4 + 4], w1 = ctr_rec[row * 4 + 5], w2 = ctr_rec[row * 4 + 6];
-      yc[0] = h ? w0[0] : v0[0], yc[1] = h ? w0[1] : v0[1], yc[2] = h ? w0[2] : v0[2], rc[8] = h ? w0[3] : v0[3];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rc[i] = h ? w1[i] : v1[i], rc[4 + i] = h ? w2[i] : v2[i];
-    } else {
-      yc[0] = v0[0], yc[1] = v0[1], yc[2] = v0[2], rc[8] = v0[3];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rc[i] = v1[i], rc[4 + i] = v2[i];
-    }
-  };
-
+  cs.window(win0, lane);
   ChunkCursor cur, n1, n2;
-  cur = enter(0, 0, 0u);
-  n1 = advance(cur);
-  n2 = advance(n1);
   int q_cur, q_n1;
   float xn_nx[3], rn_nx[9];
+  cs.prime(nbg_rs, cur, n1, n2, q_cur, q_n1, xn_nx, rn_nx);
   {
-    const int nb_cur = nbr_of(cur);
-    const int nb_n1 = nbr_of(n1);
-    q_cur = row_of(nb_cur, cur);
-    load_geom_record(nbg_rs, q_cur, xn_nx, rn_nx);
-    q_n1 = row_of(nb_n1, n1);
 #pragma unroll
     for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(xn_nx[i]));
 #pragma unroll
     for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(rn_nx[i]));
   }
   float yc[3], rc[9];
-  centre(cur, yc, rc);
+  cs.template centre<FC == 2>(cur, h, yc, rc);
 
-  while (cur.j < n_mine) {
+  while (cur.j < cs.n_mine) {
     rotate_priority(prio_step++);
     const int cnt = min(32, cur.n_total - cur.c0);  // <= 0: a row without neighbours
     const int qoff = cur.c0 + kcol < cur.n_total ? q_cur * row_bytes : kOobOffset;
@@ -774,104 +584,41 @@ __global__ __launch_bounds__(256, (VW == 1 && FC == 1) ? 4 : 3) void edge_t_stre
     for (int i = 0; i < 3; ++i) xn[i] = xn_nx[i];
 #pragma unroll
     for (int i = 0; i < 9; ++i) rn[i] = rn_nx[i];
-    const int nb_n2 = nbr_of(n2);  // ids two chunks ahead
+    const int nb_n2 = cs.nbr_of(n2);  // ids two chunks ahead
 
     uint32_t fw[2][VW][8];  // gathered feature words of the chunk's two k-steps (shared by the FC rows)
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int src_off = __builtin_amdgcn_ds_bpermute(hb + 4 * acc_row(8 * s + j, 0), qoff);
-        if constexpr (VW == 2) {
-          const auto v = __builtin_amdgcn_raw_buffer_load_b64(feat_rs, src_off + cb4, 0, 0);
-          fw[s][0][j] = v[0], fw[s][1][j] = v[1];
-        } else {
-          fw[s][0][j] = __builtin_amdgcn_raw_buffer_load_b32(feat_rs, src_off + cb4, 0, 0);
-        }
-      }
+    gather_feature_words<VW, 1>(feat_rs, hb, qoff, cb4, ch_ok, fw);
     load_geom_record(nbg_rs, q_n1, xn_nx, rn_nx);  // record one chunk ahead
     float yn[3], rnc[9];
-    centre(n1, yn, rnc);  // the next chunk's centre (the same record until the item changes)
+    cs.template centre<FC == 2>(n1, h, yn, rnc);  // the next chunk's centre (the same record until the item changes)
 
     if (TR == 0)
       edge_descriptor(xn, rn, yc, rc, rho, d);
     else
       edge_descriptor(yc, rc, xn, rn, rho, d);
 
-    // MLP A operand pieces of this lane (edge_bf16_body.h): its own dims 0..7, and {dim 8 of the row it serves as "other" half, 1}
-    u32x4 own_hi, own_lo, oth_hi, oth_lo;
-    frags_from_floats(d, own_hi, own_lo);
-    {
-      float d8 = d[8];
-      if constexpr (FC == 2) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(d8), __float_as_uint(d8), false, false);
-        d8 = __uint_as_float(h ? sw[0] : sw[1]);
-      }
-      uint32_t p_hi, p_lo;
-      split2(d8, 1.0f, p_hi, p_lo);
-      oth_hi = u32x4{p_hi, 0u, 0u, 0u};
-      oth_lo = u32x4{p_lo, 0u, 0u, 0u};
-    }
+    const MlpOperand<FC> op(d, h);
     u32x4 fa_hi[2][VW], fa_lo[2][VW];
 #pragma unroll
-    for (int a = 0; a < FC; ++a) {
-      const bool dims07 = FC == 1 ? h == 0 : h == a;
-      u32x4 a_hi, a_lo;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        a_hi[i] = dims07 ? own_hi[i] : oth_hi[i];
-        a_lo[i] = dims07 ? own_lo[i] : oth_lo[i];
-      }
-      const u32x4 wb_hi = *reinterpret_cast<const u32x4*>(&lds_w[a][0][lane][0]);
-      const u32x4 wb_lo = *reinterpret_cast<const u32x4*>(&lds_w[a][1][lane][0]);
-      const f32x16 phi = mfma_bf16x3(a_hi, a_lo, wb_hi, wb_lo, zero16());
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        if (s * 16 < cnt) {
-          float pv[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) pv[j] = gelu_scaled(phi[8 * s + j]);
-          u32x4 b_hi, b_lo;
-          frags_from_floats(pv, b_hi, b_lo);
-#pragma unroll
-          for (int t = 0; t < VW; ++t) {
-            if (a == 0) frags_from_words(fw[s][t], fa_hi[s][t], fa_lo[s][t]);
-            acc[a][t] = mfma_bf16x3(fa_hi[s][t], fa_lo[s][t], b_hi, b_lo, acc[a][t]);
-          }
-        }
-      }
-    }
+    for (int a = 0; a < FC; ++a) single_frame<VW, FC>(a, op, cnt, lane, lds_w, fw, fa_hi, fa_lo, acc[a]);
     // every load of this chunk is consumed here, in front of the stores (see the wave-pair stream)
     q_cur = q_n1;
-    q_n1 = row_of(nb_n2, n2);
+    q_n1 = cs.row_of(nb_n2, n2);
 #pragma unroll
     for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(xn_nx[i]));
 #pragma unroll
     for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(rn_nx[i]));
     if (n1.j != cur.j) {
       // the item's last chunk: acc[a][t] register r, lane (kcol, h) = T[row FC item + a][VW acc_row(r, h) + t][kcol] leaves
-      // as 3-byte rows (two adjacent channels of this lane = one hi word + one lo half-word), non-temporal
+      // as 3-byte rows (two adjacent channels of this lane: registers r, r + 1 of the tile, or tiles 0 and 1 of a register)
 #pragma unroll
       for (int a = 0; a < FC; ++a) {
         char* row = t_out + ((int64_t)cur.item * FC + a) * t24_row_bytes(C);
         if constexpr (VW == 2) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            uint32_t hp, lp;
-            t24_pack2(acc[a][0][r], acc[a][1][r], hp, lp);
-            const int idx = acc_row(r, h) * kBasis + kcol;
-            __builtin_nontemporal_store(hp, reinterpret_cast<uint32_t*>(row) + idx);
-            __builtin_nontemporal_store((uint16_t)lp, reinterpret_cast<uint16_t*>(row + (int64_t)C * kBasis * 2) + idx);
-          }
+          for (int r = 0; r < 16; ++r) t24_store2(row, C, 2 * acc_row(r, h), kcol, acc[a][0][r], acc[a][1][r]);
         } else {
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            uint32_t hp, lp;
-            t24_pack2(acc[a][0][r], acc[a][0][r + 1], hp, lp);
-            const int idx = (acc_row(r, h) >> 1) * kBasis + kcol;
-            __builtin_nontemporal_store(hp, reinterpret_cast<uint32_t*>(row) + idx);
-            __builtin_nontemporal_store((uint16_t)lp, reinterpret_cast<uint16_t*>(row + (int64_t)C * kBasis * 2) + idx);
-          }
+          t24_store_tile<true>(row, C, 0, h, kcol, acc[a][0]);
         }
 #pragma unroll
         for (int t = 0; t < VW; ++t) acc[a][t] = zero16();
@@ -881,7 +628,7 @@ __global__ __launch_bounds__(256, (VW == 1 && FC == 1) ? 4 : 3) void edge_t_stre
     for (int i = 0; i < 3; ++i) yc[i] = yn[i];
 #pragma unroll
     for (int i = 0; i < 9; ++i) rc[i] = rnc[i];
-    cur = n1, n1 = n2, n2 = advance(n2);
+    cur = n1, n1 = n2, n2 = cs.advance(n2);
   }
   }  // windows
 }

@@ -113,17 +113,7 @@ __global__ __launch_bounds__(128, kDxWaves) void edge_dx_bf16_kernel(EdgeGeom g,
       if (c0 + 64 < n_total) load_geom_record(nbg_rs, row_of_fe(min(c0 + 64 + kcol, n_total - 1)), xn_nx, rn_nx);  // next chunk of this wavefront
       edge_descriptor(xn, rn, yc, rc, rho, d);
 
-      // descriptor pieces as in edge_item_bf16<.., FC = 2>: own dims 0..7, and {dim 8 of the other half's frame, 1}
-      u32x4 own_hi, own_lo, oth_hi, oth_lo;
-      frags_from_floats(d, own_hi, own_lo);
-      {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(d[8]), __float_as_uint(d[8]), false, false);
-        const float d8 = __uint_as_float(h ? sw[0] : sw[1]);
-        uint32_t p_hi, p_lo;
-        split2(d8, 1.0f, p_hi, p_lo);
-        oth_hi = u32x4{p_hi, 0u, 0u, 0u};
-        oth_lo = u32x4{p_lo, 0u, 0u, 0u};
-      }
+      const MlpOperand<2> op(d, h);  // own dims 0..7, and {dim 8 of the other half's frame, 1} (edge_bf16_body.h)
       f32x16 dacc[CT];
 #pragma unroll
       for (int t = 0; t < CT; ++t) dacc[t] = zero16();
@@ -133,19 +123,16 @@ __global__ __launch_bounds__(128, kDxWaves) void edge_dx_bf16_kernel(EdgeGeom g,
         u32x4 b_hi, b_lo;  // desc^T as the B operand: K = descriptor dim, N = frame-edge
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          b_hi[i] = dims07 ? own_hi[i] : oth_hi[i];
-          b_lo[i] = dims07 ? own_lo[i] : oth_lo[i];
+          b_hi[i] = dims07 ? op.own_hi[i] : op.oth_hi[i];
+          b_lo[i] = dims07 ? op.own_lo[i] : op.oth_lo[i];
         }
         const u32x4 wa_hi = *reinterpret_cast<const u32x4*>(&lds_w[a][0][lane][0]);  // [A; beta]^T as the A operand: M = basis function
         const u32x4 wa_lo = *reinterpret_cast<const u32x4*>(&lds_w[a][1][lane][0]);
         const f32x16 pre_t = mfma_bf16x3(wa_hi, wa_lo, b_hi, b_lo, zero16());  // register r, lane (n, h): k = acc_row(r, h)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          float pv[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) pv[j] = gelu_scaled(pre_t[8 * s + j]);
           u32x4 a_hi, a_lo;
-          frags_from_floats(pv, a_hi, a_lo);
+          gelu_frags(pre_t, s, a_hi, a_lo);
 #pragma unroll
           for (int t = 0; t < CT; ++t) {
             const u32x4 g_hi = *reinterpret_cast<const u32x4*>(&lds_gt[a][t][s][0][lane][0]);

@@ -2,6 +2,10 @@
 
 Tolerances (||d||_2 / ||ref||_2 per tensor): the north star allows 1e-4; the fp32-MFMA path is exact
 fp32 arithmetic with a different summation order, so the tests hold it to 2e-5.
+Held per tensor (`rel_err`): every comparison of this module.  Held per row as well (tests/rowwise_error.py: every output
+row, source row, c_in slice / c_out column / 4-lane of dW, basis column of dA and element of dbeta against its own
+random-sign scale and the fp64 oracle, bounds from the CPU emulation of each arithmetic mode): the two random-shape tables,
+for every row of at most ROWWISE_MAX_POINTS input points, and tests/test_gpu_rowwise_parity.py on data of uneven magnitude.
 Integer results (edges, ends, keys, transposed lists) are compared bit-exactly (as sets per sample
 where the reference leaves the order undefined).
 """
@@ -16,6 +20,7 @@ import pytest
 import torch
 
 import form_coverage_table as FC
+import rowwise_error as RW
 from conftest import GOLDEN, canon_edges, golden_layer_files, load_npz, rel_err
 from oracle import se3conv_oracle as O
 
@@ -255,8 +260,8 @@ FORM_CASES = [
 
 @functools.lru_cache(maxsize=None)
 def form_case_oracle(case):
-    """The CPU side of a FORM_CASES row, computed once for both tests and every arithmetic mode: the generator's output, the
-    oracle's edges and the oracle's forward + backward.  Nobody writes to it."""
+    """The CPU side of a CASES / FORM_CASES row, computed once for both tests and every arithmetic mode: the generator's output,
+    the oracle's edges and the oracle's forward + backward.  Nobody writes to it."""
     c = random_case(*case)
     nb_ref, ends_ref = O.ball_query(c["pts_in"], c["pts_out"], c["bid_in"], c["bid_out"], c["r"])
     rho, nu = torch.tensor(1.0 / c["r"]), torch.tensor(ends_ref.shape[0] / max(nb_ref.shape[0], 1))
@@ -264,35 +269,84 @@ def form_case_oracle(case):
     return c, nb_ref, ends_ref, rho, nu, ref
 
 
-def run_case_against_oracle(c, f_in, f_out, amd, oracle=None):
-    """Ball query + operator forward/backward of one random case on the GPU against the oracle: returns the relative
-    errors of out / dx / dA / dbeta / dW (also used by tools/fuzz_parity.py) plus the geometry and reference edges.
-    oracle: (edges, ends, (out, dx, dA, dbeta, dW)) of the case where the caller has them already."""
+# Rows of the two tables beyond this many input points keep the whole-tensor check only: the fp64 scale pass of the row-wise
+# metric costs too much host time there (seeds 17, 22, 23, 24, 186, 187; tests/test_rowwise_error.py counts them).
+ROWWISE_MAX_POINTS = 700
+
+
+def rowwise_checked(case):
+    return case[1] <= ROWWISE_MAX_POINTS
+
+
+@functools.lru_cache(maxsize=None)
+def form_case_rowwise(case):
+    """(fp64 reference, squared scales) of a table row for the row-wise metric: once per case for all three arithmetic modes."""
+    c, nb_ref, _, rho, nu, _ = form_case_oracle(case)
+    return RW.reference_and_scales(c, nb_ref, rho, nu)
+
+
+def _run_case(c, amd, oracle):
     nb_ref, ends_ref = oracle[:2] if oracle else O.ball_query(c["pts_in"], c["pts_out"], c["bid_in"], c["bid_out"], c["r"])
     nb, ends = amd.ops.ball_query(c["pts_in"].to(DEV), c["pts_out"].to(DEV), c["bid_in"].to(DEV), c["bid_out"].to(DEV), c["r"])
     assert torch.equal(ends.cpu(), ends_ref)
     assert torch.equal(canon_edges(nb), canon_edges(nb_ref))
 
     rho, nu = torch.tensor(1.0 / c["r"]), torch.tensor(ends_ref.shape[0] / max(nb_ref.shape[0], 1))
-    out_r, dx_r, da_r, db_r, dw_r = oracle[2] if oracle else O.conv_forward_backward(
+    refs = oracle[2] if oracle else O.conv_forward_backward(
         c["pts_in"], c["pts_out"], c["fi"], c["fo"], nb_ref, c["x"], c["a"], c["b"], c["w"], rho, nu, c["go"])
     geom = amd.ops.ConvGeometry.build(c["pts_in"].to(DEV), c["pts_out"].to(DEV), c["fi"].to(DEV), c["fo"].to(DEV), nb, ends)
     x = c["x"].to(DEV).requires_grad_(True)
     a, b, w = (c[k].to(DEV).requires_grad_(True) for k in ("a", "b", "w"))
     out = amd.SE3ConvFunction.apply(x, a, b, w, geom, rho, nu)
     out.backward(c["go"].to(DEV))
-    errs = {"out": rel_err(out, out_r), "dx": rel_err(x.grad, dx_r), "dA": rel_err(a.grad, da_r),
-            "dbeta": rel_err(b.grad, db_r), "dW": rel_err(w.grad, dw_r)}
+    got = {"out": out.detach(), "dx": x.grad, "dA": a.grad, "dbeta": b.grad, "dW": w.grad}
+    errs = {k: rel_err(got[k], r) for k, r in zip(RW.KEYS, refs)}
+    return errs, got, geom, nb_ref, rho, nu
+
+
+def run_case_against_oracle(c, f_in, f_out, amd, oracle=None):
+    """Ball query + operator forward/backward of one random case on the GPU against the oracle: returns the relative
+    errors of out / dx / dA / dbeta / dW plus the geometry and reference edges.
+    oracle: (edges, ends, (out, dx, dA, dbeta, dW)) of the case where the caller has them already."""
+    errs, _, geom, nb_ref, _, _ = _run_case(c, amd, oracle)
     return errs, geom, nb_ref
+
+
+def run_case_rowwise_against_oracle(c, f_in, f_out, amd, oracle=None, rowwise=None):
+    """run_case_against_oracle plus the row-wise ratios of the same outputs (tests/rowwise_error.py; also used by
+    tools/fuzz_parity.py): (errs, ratios, geom, edges).  rowwise: (fp64 reference, squared scales) where the caller has them."""
+    errs, got, geom, nb_ref, rho, nu = _run_case(c, amd, oracle)
+    ref64, s2 = rowwise or RW.reference_and_scales(c, nb_ref, rho, nu)
+    return errs, RW.ratios(got, ref64, s2), geom, nb_ref
+
+
+def assert_rowwise(ratios, precision, what, skip=()):
+    """Every entry under the bound of its arithmetic mode; slices without an edge exactly zero.  The failure names the slice."""
+    assert ratios["zeros_exact"], (what, "a row without an edge is not exactly zero")
+    for entry in RW.ENTRIES:
+        if entry not in skip:
+            assert ratios[entry] < RW.TOLERANCES[precision][entry], (what, entry, ratios[entry], "slice", ratios["argmax"][entry])
+
+
+def check_table_row(case, amd):
+    c, nb_ref, ends_ref, rho, nu, ref = form_case_oracle(case)
+    prec = amd.get_precision()
+    if rowwise_checked(case):
+        errs, ratios, geom, _ = run_case_rowwise_against_oracle(c, case[3], case[4], amd, (nb_ref, ends_ref, ref), form_case_rowwise(case))
+    else:
+        (errs, geom, _), ratios = run_case_against_oracle(c, case[3], case[4], amd, oracle=(nb_ref, ends_ref, ref)), None
+    print(f"case seed{case[0]} {prec}: " + " ".join(f"{k}={v:.2e}" for k, v in errs.items())
+          + (f" | rowwise {RW.fmt(ratios)}" if ratios else " | rowwise not computed (more than 700 points)"))
+    for key, err in errs.items():
+        assert err < tol(amd), (key, err)
+    if ratios:
+        assert_rowwise(ratios, prec, f"seed{case[0]}")
+    return c, geom, nb_ref
 
 
 @pytest.mark.parametrize("case", CASES, ids=[f"seed{c[0]}" for c in CASES])
 def test_random_shapes_against_oracle(case, amd):
-    seed, n_in, n_out, f_in, f_out, c_in, c_out, k_deg, batches = case
-    c = random_case(seed, n_in, n_out, f_in, f_out, c_in, c_out, k_deg, batches)
-    errs, geom, nb_ref = run_case_against_oracle(c, f_in, f_out, amd)
-    for key, err in errs.items():
-        assert err < tol(amd), (key, err)
+    c, geom, nb_ref = check_table_row(case, amd)
 
     # the source-major edge list is a permutation of the edges, grouped by source, samples ascending
     ts, te = geom.transpose()
@@ -307,11 +361,7 @@ def test_random_shapes_against_oracle(case, amd):
 def test_random_shapes_of_every_form_against_oracle(case, amd):
     """FORM_CASES through the autograd node, as CASES above: every kernel form the library can pick runs against the fp64
     oracle somewhere in the suite (tests/test_form_coverage.py holds the tables to that)."""
-    c, nb_ref, ends_ref, rho, nu, ref = form_case_oracle(case)
-    errs, _, _ = run_case_against_oracle(c, case[3], case[4], amd, oracle=(nb_ref, ends_ref, ref))
-    print(f"form case seed{case[0]} {amd.get_precision()}: " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
-    for key, err in errs.items():
-        assert err < tol(amd), (key, err)
+    check_table_row(case, amd)
 
 
 # The autograd node makes one request: every gradient, T kept where backward reads it.  The other requests -- a feature

@@ -9,6 +9,20 @@
 //
 // These are streaming kernels: A (1 GB at the headline shape) is read once, so they are HBM-bound
 // as long as the MFMA side reaches ~1/3 of its peak.
+//
+// The three NN kernels (gemm_nn_bf16 over packed words, gemm_nn_t24 over 3-byte rows, gemm_nn_t16 over 2.25-byte block rows)
+// are one skeleton; what they share is written once (profiles/gemm_nn_pieces.txt has the device code it was checked against):
+//   piece                                   gemm_nn_bf16          gemm_nn_t24        gemm_nn_t16
+//   weight_plane_rsrc                       yes                   yes                yes
+//   weight passes: the loads                own (32-k tiles,      own text           own text    (every shared shape moved
+//                                           other thread map)                                    the waits of a k loop)
+//   nn_store_weights_half                   own store_tile        yes                yes
+//   A fragments out of LDS                  pair_hi / pair_lo     t24_lo_word        straight reads
+//   nn_mfma_tiles                           yes                   yes                yes
+//   nn_store_acc                            yes                   yes                yes
+// gemm_tn_bf16: the row-plane forms (AFMT 1, 2) share store_b_planes; their B loads are written in both branches, in front of
+// the A loads (behind them the address selects compile differently and the stage loop's waits move).  gemm_a_row_bytes is
+// the size of an A row for the kernels and the host.
 #include <atomic>
 
 #include "common.h"
@@ -22,6 +36,13 @@ constexpr int BM = 128, BN = 64, BK = 32;
 constexpr int A_LD = BK + 4;   // words; 144-byte pitch keeps 16-byte alignment and spreads ds_read_b128 over all banks
 constexpr int B_LD = BK + 8;   // bf16;  80-byte pitch, same properties
 
+// bytes of one A row of k values by its format: 0 packed words, 1 the 3-byte rows (T24: k * 3 = t24_row_bytes(k / kBasis)
+// for the k the format exists for, and exact for any other k a caller asks about before its form is checked), 2 the
+// 2.25-byte block rows (T16, whole blocks of 32: the forms reject other k)
+__host__ __device__ inline int64_t gemm_a_row_bytes(int afmt, int k) {
+  return afmt == 2 ? t16_row_bytes(k / kBasis) : (int64_t)k * (afmt == 1 ? 3 : 4);
+}
+
 // up to 4 consecutive words starting at p, `avail` of them readable (<= 0: none).  Native vector
 // type on purpose: HIP's uint4 struct made the register tiles of the pipeline land in scratch.
 __device__ __forceinline__ u32x4 ld4_words(const uint32_t* p, int64_t avail, bool vec) {
@@ -31,7 +52,70 @@ __device__ __forceinline__ u32x4 ld4_words(const uint32_t* p, int64_t avail, boo
   return u32x4{x, y, z, w};
 }
 
-// OUT_MODE 0: fp32 C * alpha, 1: packed words of C * alpha, 2: raw fp32 partial of split z (no alpha).
+// ---- Pieces the NN kernels share (who takes which: the table in the header comment) -------------------------------------
+
+// one plane of the prepared weights, Bt[n][kp] bf16, as a buffer resource; !bounded: the guarded-load form, which takes no buffer load
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t weight_plane_rsrc(const uint16_t* bt, int n, int kp, bool bounded = true) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(bt), (short)0,
+                                           bounded ? (int)(uint32_t)((int64_t)n * kp * 2) : 0, 0x00020000);
+}
+
+// The weights of a 64-k super tile (the kernels over row planes) are loaded in 2 * NB passes of kWeightPassCols columns per
+// plane, into bh[] / bl[]; passes alternate which 32-k half a thread holds (each kernel's load_super).  This writes one
+// half to LDS buffer `buf`.  The passes come in pairs (2 g, 2 g + 1): the even pass holds this thread's piece of the half
+// iff !q (q = half ^ bit 2 of tid); row r8 = tid >> 3 of the pass, column c4 = (tid & 3) * 8.  LDS: the kernel's tile
+// image as it declares it, [2][64 NB][B_LD] (an array or a pointer to its first buffer: no decay, the addressing stays the
+// kernel's own).
+constexpr int kWeightPassCols = 32;
+template <int NB, class LDS>
+__device__ __forceinline__ void nn_store_weights_half(const u32x4 (&bh)[2 * NB], const u32x4 (&bl)[2 * NB], LDS& bsh, LDS& bsl,
+                                                      int buf, bool q, int r8, int c4) {
+  constexpr int CP = kWeightPassCols;
+#pragma unroll
+  for (int g = 0; g < NB; ++g) {
+    *reinterpret_cast<u32x4*>(&bsh[buf][CP * (2 * g) + (q ? CP : 0) + r8][c4]) = q ? bh[2 * g + 1] : bh[2 * g];
+    *reinterpret_cast<u32x4*>(&bsl[buf][CP * (2 * g) + (q ? CP : 0) + r8][c4]) = q ? bl[2 * g + 1] : bl[2 * g];
+  }
+}
+
+// The A fragments of k-step kk against the wavefront's 2 * NB column tiles of LDS buffer `buf`.
+template <int NB, class LDS>
+__device__ __forceinline__ void nn_mfma_tiles(u32x4 a_hi, u32x4 a_lo, const LDS& bsh, const LDS& bsl, int buf, int kk, int rl,
+                                              f32x16 (&acc)[2 * NB]) {
+#pragma unroll
+  for (int ct = 0; ct < 2 * NB; ++ct) {
+    const u32x4 bh = *reinterpret_cast<const u32x4*>(&bsh[buf][32 * ct + rl][kk]);
+    const u32x4 bl = *reinterpret_cast<const u32x4*>(&bsl[buf][32 * ct + rl][kk]);
+    acc[ct] = mfma_bf16x3(a_hi, a_lo, bh, bl, acc[ct]);
+  }
+}
+
+// The accumulators of a wavefront (rows m0 + 32 wave .., columns n0 ..) -> C.
+// OUT_MODE 0: fp32 C * alpha, 1: packed words of C * alpha, 2: raw fp32 partial of split blockIdx.z (no alpha).
+template <int OUT_MODE, int NB>
+__device__ __forceinline__ void nn_store_acc(const f32x16 (&acc)[2 * NB], void* c, int64_t m, int n, int64_t m0, int n0,
+                                             int wave, int rl, int h, const float* alpha_num, float alpha_scale) {
+  const float alpha = OUT_MODE == 2 ? 1.0f : (alpha_num ? *alpha_num : 1.0f) * alpha_scale;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t gr = m0 + wave * 32 + acc_row(r, h);
+    if (gr < m) {
+#pragma unroll
+      for (int ct = 0; ct < 2 * NB; ++ct) {
+        const int gc = n0 + 32 * ct + rl;
+        if (gc >= n) continue;
+        if constexpr (OUT_MODE == 1) {
+          static_cast<uint32_t*>(c)[gr * n + gc] = split_pack(alpha * acc[ct][r]);
+        } else {
+          float* out = static_cast<float*>(c) + (OUT_MODE == 2 ? (int64_t)blockIdx.z * m * n : 0);
+          out[gr * n + gc] = alpha * acc[ct][r];
+        }
+      }
+    }
+  }
+}
+
+// OUT_MODE: see nn_store_acc.
 // The A stream is prefetched DEPTH k-tiles ahead in registers: one k-tile of compute (~400 cycles) is
 // far shorter than an HBM round trip, so a single tile in flight leaves the kernel latency-bound.
 // FAST (k % 32 == 0, operands < 4 GB): every load is an unconditional raw buffer load whose out-of-range
@@ -63,10 +147,7 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
   const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint32_t*>(a), (short)0, FAST ? (int)(uint32_t)(m * k * 4) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t bh_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(bt_hi), (short)0, FAST ? (int)(uint32_t)((int64_t)n * kp * 2) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t bl_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(bt_lo), (short)0, FAST ? (int)(uint32_t)((int64_t)n * kp * 2) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t bh_rs = weight_plane_rsrc(bt_hi, n, kp, FAST), bl_rs = weight_plane_rsrc(bt_lo, n, kp, FAST);
   // Every block walks its k-tiles from a different starting phase (the sum is order-independent up to
   // rounding): with a common phase all resident blocks read the same 128-byte column strip of their
   // 8 KB rows at the same time, which concentrates the traffic on a few HBM channels.
@@ -133,12 +214,7 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
       const u32x4 w1 = *reinterpret_cast<const u32x4*>(&as[buf][wave * 32 + rl][kk + 4]);
       const u32x4 a_hi = {pair_hi(w0[0], w0[1]), pair_hi(w0[2], w0[3]), pair_hi(w1[0], w1[1]), pair_hi(w1[2], w1[3])};
       const u32x4 a_lo = {pair_lo(w0[0], w0[1]), pair_lo(w0[2], w0[3]), pair_lo(w1[0], w1[1]), pair_lo(w1[2], w1[3])};
-#pragma unroll
-      for (int c = 0; c < 2 * NB; ++c) {
-        const u32x4 bh = *reinterpret_cast<const u32x4*>(&bsh[buf][32 * c + rl][kk]);
-        const u32x4 bl = *reinterpret_cast<const u32x4*>(&bsl[buf][32 * c + rl][kk]);
-        acc[c] = mfma_bf16x3(a_hi, a_lo, bh, bl, acc[c]);
-      }
+      nn_mfma_tiles<NB>(a_hi, a_lo, bsh, bsl, buf, kk, rl, acc);
     }
   };
   // k-tile kt lives in register set (kt mod DEPTH) until it is written to LDS buffer (kt & 1).  The kernel's
@@ -180,24 +256,7 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
     }
   }
 
-  const float alpha = OUT_MODE == 2 ? 1.0f : (alpha_num ? *alpha_num : 1.0f) * alpha_scale;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t gr = m0 + wave * 32 + acc_row(r, h);
-    if (gr < m) {
-#pragma unroll
-      for (int ct = 0; ct < 2 * NB; ++ct) {
-        const int gc = n0 + 32 * ct + rl;
-        if (gc >= n) continue;
-        if constexpr (OUT_MODE == 1) {
-          static_cast<uint32_t*>(c)[gr * n + gc] = split_pack(alpha * acc[ct][r]);
-        } else {
-          float* out = static_cast<float*>(c) + (OUT_MODE == 2 ? (int64_t)blockIdx.z * m * n : 0);
-          out[gr * n + gc] = alpha * acc[ct][r];
-        }
-      }
-    }
-  }
+  nn_store_acc<OUT_MODE, NB>(acc, c, m, n, m0, n0, wave, rl, h, alpha_num, alpha_scale);
 }
 
 // NN GEMM over A rows in the 3-byte format (common.h, T24; k a multiple of 64).  What bounds the A stream of these
@@ -222,8 +281,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t24_kernel(const uint8_t* __restr
   constexpr int RB = BM;           // rows per workgroup
   constexpr int RP = 32;           // rows one load pass of the hi plane covers (8 threads per row): 4 passes = RB rows
   constexpr int RPL = 64;          // rows one load pass of the lo plane covers (4 threads per row): 2 passes = RB rows
-  constexpr int CP = 32;           // weight columns one load pass covers: 2 * NB passes per plane
-  constexpr int NBP = 2 * NB;
+  constexpr int CP = kWeightPassCols, NBP = 2 * NB;
   // one block of LDS, carved into the four tile images
   constexpr int kAsh = 2 * RB * (BK + 8) * 2, kAsl = 2 * RB * (BK + 16), kBs = 2 * BNW * B_LD * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // gemm_nn_t24_lds_bytes: 52 / 72 KB
@@ -243,10 +301,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t24_kernel(const uint8_t* __restr
   struct Super { u32x4 ah[4], al[2], bh[NBP], bl[NBP]; };
   const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint8_t*>(a), (short)0, (int)(uint32_t)(m * k * 3), 0x00020000);
-  const __amdgpu_buffer_rsrc_t bh_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(bt_hi), (short)0, (int)(uint32_t)((int64_t)n * k * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t bl_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(bt_lo), (short)0, (int)(uint32_t)((int64_t)n * k * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t bh_rs = weight_plane_rsrc(bt_hi, n, k), bl_rs = weight_plane_rsrc(bt_lo, n, k);
   const int phase = (int)((blockIdx.x * 5u) % (unsigned)ns);  // see gemm_nn_bf16_kernel
   const uint32_t rb = (uint32_t)k * 3u;
   const int hsel = (tid >> 2) & 1, lsel = (tid >> 1) & 1;
@@ -264,6 +319,8 @@ __global__ __launch_bounds__(256) void gemm_nn_t24_kernel(const uint8_t* __restr
       const uint32_t off = (uint32_t)(m0 + p * RPL + (tid >> 2)) * rb + (uint32_t)k * 2u + k0 + (uint32_t)((tid & 3) ^ (p << 1)) * 16u;
       t.al[p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, off, 0, 0));
     }
+    // (the weight loads stay written out here and in gemm_nn_t16_kernel: as a shared function the offset is associated
+    // otherwise -- k0 joins the thread's piece, not the row -- and waits move inside the k loop, profiles/gemm_nn_pieces.txt)
 #pragma unroll
     for (int j = 0; j < NBP; ++j) {  // pass j: columns CP * j + (tid >> 3); passes alternate which 32-k half a thread holds
       const uint32_t off = ((uint32_t)(n0 + CP * j + (tid >> 3)) * (uint32_t)k + k0 + (uint32_t)((tid & 7) ^ ((j & 1) << 2)) * 8u) * 2u;
@@ -278,12 +335,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t24_kernel(const uint8_t* __restr
     *reinterpret_cast<u32x4*>(&ash[buf][(q ? RP : 0) + r8][c4]) = q ? t.ah[1] : t.ah[0];
     *reinterpret_cast<u32x4*>(&ash[buf][(q ? 3 * RP : 2 * RP) + r8][c4]) = q ? t.ah[3] : t.ah[2];
     *reinterpret_cast<u32x4*>(&asl[buf][(ql ? RPL : 0) + (tid >> 2)][(tid & 1) * 16]) = ql ? t.al[1] : t.al[0];
-    // weight passes come in pairs (2 g, 2 g + 1): the even pass holds this thread's half-0 piece iff q == 0
-#pragma unroll
-    for (int g = 0; g < NBP / 2; ++g) {
-      *reinterpret_cast<u32x4*>(&bsh[buf][CP * (2 * g) + (q ? CP : 0) + r8][c4]) = q ? t.bh[2 * g + 1] : t.bh[2 * g];
-      *reinterpret_cast<u32x4*>(&bsl[buf][CP * (2 * g) + (q ? CP : 0) + r8][c4]) = q ? t.bl[2 * g + 1] : t.bl[2 * g];
-    }
+    nn_store_weights_half<NB>(t.bh, t.bl, bsh, bsl, buf, q, r8, c4);
   };
   f32x16 acc[2 * NB];
 #pragma unroll
@@ -298,12 +350,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t24_kernel(const uint8_t* __restr
       const uint32_t l0 = lp[0], l1 = lp[1];
       const u32x4 a_lo = {t24_lo_word<0>(a_hi[0], l0), t24_lo_word<2>(a_hi[1], l0), t24_lo_word<0>(a_hi[2], l1),
                           t24_lo_word<2>(a_hi[3], l1)};
-#pragma unroll
-      for (int ct = 0; ct < 2 * NB; ++ct) {
-        const u32x4 bh = *reinterpret_cast<const u32x4*>(&bsh[buf][32 * ct + rl][kk]);
-        const u32x4 bl = *reinterpret_cast<const u32x4*>(&bsl[buf][32 * ct + rl][kk]);
-        acc[ct] = mfma_bf16x3(a_hi, a_lo, bh, bl, acc[ct]);
-      }
+      nn_mfma_tiles<NB>(a_hi, a_lo, bsh, bsl, buf, kk, rl, acc);
     }
   };
   // Two super tiles in registers (= the 4 k-tiles in flight of the kernel above).  Step A computes the first half
@@ -346,24 +393,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t24_kernel(const uint8_t* __restr
 #undef SE3_T24_STEP
 #undef SE3_T24_STEP_FULL
 
-  const float alpha = OUT_MODE == 2 ? 1.0f : (alpha_num ? *alpha_num : 1.0f) * alpha_scale;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t gr = m0 + wave * 32 + acc_row(r, h);
-    if (gr < m) {
-#pragma unroll
-      for (int ct = 0; ct < 2 * NB; ++ct) {
-        const int gc = n0 + 32 * ct + rl;
-        if (gc >= n) continue;
-        if constexpr (OUT_MODE == 1) {
-          static_cast<uint32_t*>(c)[gr * n + gc] = split_pack(alpha * acc[ct][r]);
-        } else {
-          float* out = static_cast<float*>(c) + (OUT_MODE == 2 ? (int64_t)blockIdx.z * m * n : 0);
-          out[gr * n + gc] = alpha * acc[ct][r];
-        }
-      }
-    }
-  }
+  nn_store_acc<OUT_MODE, NB>(acc, c, m, n, m0, n0, wave, rl, h, alpha_num, alpha_scale);
 }
 
 constexpr int gemm_nn_t24_lds_bytes(int nb) {
@@ -386,8 +416,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
   constexpr int BNW = BN * NB;
   constexpr int RB = BM;           // rows per workgroup
   constexpr int RP = 32;           // rows one load pass covers (8 threads per row): 4 passes = RB rows
-  constexpr int CP = 32;           // weight columns one load pass covers: 2 * NB passes per plane
-  constexpr int NBP = 2 * NB;
+  constexpr int CP = kWeightPassCols, NBP = 2 * NB;
   __shared__ __attribute__((aligned(16))) uint16_t ash[2][RB][BK + 8];   // 80-byte pitch
   __shared__ __attribute__((aligned(16))) uint16_t asl[2][RB][BK + 8];
   __shared__ __attribute__((aligned(16))) uint16_t bsh[2][BNW][B_LD];
@@ -403,10 +432,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
   const uint32_t rb = (uint32_t)k / 32u * 72u;             // row bytes: 2 k of mantissas + k / 4 exponent bytes
   const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint8_t*>(a), (short)0, (int)(uint32_t)(m * rb), 0x00020000);
-  const __amdgpu_buffer_rsrc_t bh_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(bt_hi), (short)0, (int)(uint32_t)((int64_t)n * k * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t bl_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(bt_lo), (short)0, (int)(uint32_t)((int64_t)n * k * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t bh_rs = weight_plane_rsrc(bt_hi, n, k), bl_rs = weight_plane_rsrc(bt_lo, n, k);
   const int hsel = (tid >> 2) & 1;
   // lane l of load pass p reads 16-byte column (l & 7) ^ (4 * (p & 1)) of its row (see gemm_nn_t24_kernel)
   auto load_super = [&](Super& t, int st) {
@@ -417,7 +443,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
       t.am[p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, off, 0, 0));
     }
 #pragma unroll
-    for (int j = 0; j < NBP; ++j) {
+    for (int j = 0; j < NBP; ++j) {  // pass j: columns CP * j + (tid >> 3); passes alternate which 32-k half a thread holds
       const uint32_t off = ((uint32_t)(n0 + CP * j + (tid >> 3)) * (uint32_t)k + k0 + (uint32_t)((tid & 7) ^ ((j & 1) << 2)) * 8u) * 2u;
       t.bh[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(bh_rs, off, 0, 0));
       t.bl[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(bl_rs, off, 0, 0));
@@ -448,11 +474,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
       *reinterpret_cast<u32x4*>(&ash[buf][row][c4]) = vh;
       *reinterpret_cast<u32x4*>(&asl[buf][row][c4]) = vl;
     }
-#pragma unroll
-    for (int g = 0; g < NBP / 2; ++g) {
-      *reinterpret_cast<u32x4*>(&bsh[buf][CP * (2 * g) + (q ? CP : 0) + r8][c4]) = q ? t.bh[2 * g + 1] : t.bh[2 * g];
-      *reinterpret_cast<u32x4*>(&bsl[buf][CP * (2 * g) + (q ? CP : 0) + r8][c4]) = q ? t.bl[2 * g + 1] : t.bl[2 * g];
-    }
+    nn_store_weights_half<NB>(t.bh, t.bl, bsh, bsl, buf, q, r8, c4);
   };
   f32x16 acc[2 * NB];
 #pragma unroll
@@ -463,12 +485,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
       const int kk = 16 * s + 8 * h;
       const u32x4 a_hi = *reinterpret_cast<const u32x4*>(&ash[buf][wave * 32 + rl][kk]);
       const u32x4 a_lo = *reinterpret_cast<const u32x4*>(&asl[buf][wave * 32 + rl][kk]);
-#pragma unroll
-      for (int ct = 0; ct < 2 * NB; ++ct) {
-        const u32x4 bh = *reinterpret_cast<const u32x4*>(&bsh[buf][32 * ct + rl][kk]);
-        const u32x4 bl = *reinterpret_cast<const u32x4*>(&bsl[buf][32 * ct + rl][kk]);
-        acc[ct] = mfma_bf16x3(a_hi, a_lo, bh, bl, acc[ct]);
-      }
+      nn_mfma_tiles<NB>(a_hi, a_lo, bsh, bsl, buf, kk, rl, acc);
     }
   };
   // Mega tile = 4 super tiles, fully unrolled (the exponent bytes of super tile s sit at a compile-time position of the
@@ -524,24 +541,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
     __syncthreads();
   }
 
-  const float alpha = OUT_MODE == 2 ? 1.0f : (alpha_num ? *alpha_num : 1.0f) * alpha_scale;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t gr = m0 + wave * 32 + acc_row(r, h);
-    if (gr < m) {
-#pragma unroll
-      for (int ct = 0; ct < 2 * NB; ++ct) {
-        const int gc = n0 + 32 * ct + rl;
-        if (gc >= n) continue;
-        if constexpr (OUT_MODE == 1) {
-          static_cast<uint32_t*>(c)[gr * n + gc] = split_pack(alpha * acc[ct][r]);
-        } else {
-          float* out = static_cast<float*>(c) + (OUT_MODE == 2 ? (int64_t)blockIdx.z * m * n : 0);
-          out[gr * n + gc] = alpha * acc[ct][r];
-        }
-      }
-    }
-  }
+  nn_store_acc<OUT_MODE, NB>(acc, c, m, n, m0, n0, wave, rl, h, alpha_num, alpha_scale);
 }
 
 // Row-strip GEMM for the wide, write-dominated products with a short k (grad_T = g W^T, H = f W''):
@@ -724,7 +724,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const uint32_t* __res
 
   struct Stage { u32x4 a0, a1, a2, a3, b0, b1; };
   const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint32_t*>(a), (short)0, FAST ? (int)(uint32_t)(A16 ? me * (ka / 32 * 72) : me * ka * (A24 ? 3 : 4)) : 0, 0x00020000);
+      const_cast<uint32_t*>(a), (short)0, FAST ? (int)(uint32_t)(me * gemm_a_row_bytes(AFMT, ka)) : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t b_rs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint32_t*>(b), (short)0, FAST ? (int)(uint32_t)(me * n * 4) : 0, 0x00020000);
   const int arow = tid >> 5, acq = (tid & 31) * 4, brow = tid >> 4, bcq = (tid & 15) * 4;
@@ -733,7 +733,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const uint32_t* __res
     const int64_t mm = mb + st * BK;
     if constexpr (A16) {
       const uint32_t oob = 0xfffffff0u;
-      const uint32_t rb = (uint32_t)ka / 32u * 72u;
+      const uint32_t rb = (uint32_t)gemm_a_row_bytes(AFMT, ka);
       constexpr int kNtLoad = 2;
       // mantissas: 32 rows x 256 B = 2 pieces of 16 B per thread (rows tid >> 4 and + 16, piece tid & 15 = 8 mantissas =
       // blocks 2 pc, 2 pc + 1 of the 128 columns); their exponent bytes are adjacent in the plane (t16_exp_pos: bit 0)
@@ -791,6 +791,13 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const uint32_t* __res
       }
     }
   };
+  // the hi / lo halves of a stage's B words (rows brow and brow + 16) into the 16-bit images of the row-plane forms (A16, A24)
+  auto store_b_planes = [&](const Stage& t, int buf) {
+    *reinterpret_cast<u32x2*>(&bth[buf][brow][bcq]) = u32x2{pair_hi(t.b0[0], t.b0[1]), pair_hi(t.b0[2], t.b0[3])};
+    *reinterpret_cast<u32x2*>(&btl[buf][brow][bcq]) = u32x2{pair_lo(t.b0[0], t.b0[1]), pair_lo(t.b0[2], t.b0[3])};
+    *reinterpret_cast<u32x2*>(&bth[buf][brow + 16][bcq]) = u32x2{pair_hi(t.b1[0], t.b1[1]), pair_hi(t.b1[2], t.b1[3])};
+    *reinterpret_cast<u32x2*>(&btl[buf][brow + 16][bcq]) = u32x2{pair_lo(t.b1[0], t.b1[1]), pair_lo(t.b1[2], t.b1[3])};
+  };
   auto store_stage = [&](const Stage& t, int buf) {
     if constexpr (A16) {
 #pragma unroll
@@ -802,10 +809,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const uint32_t* __res
         *reinterpret_cast<u32x4*>(&ath[buf][16 * p + (tid >> 4)][(tid & 15) * 8]) = vh;
         *reinterpret_cast<u32x4*>(&atl[buf][16 * p + (tid >> 4)][(tid & 15) * 8]) = vl;
       }
-      *reinterpret_cast<u32x2*>(&bth[buf][brow][bcq]) = u32x2{pair_hi(t.b0[0], t.b0[1]), pair_hi(t.b0[2], t.b0[3])};
-      *reinterpret_cast<u32x2*>(&btl[buf][brow][bcq]) = u32x2{pair_lo(t.b0[0], t.b0[1]), pair_lo(t.b0[2], t.b0[3])};
-      *reinterpret_cast<u32x2*>(&bth[buf][brow + 16][bcq]) = u32x2{pair_hi(t.b1[0], t.b1[1]), pair_hi(t.b1[2], t.b1[3])};
-      *reinterpret_cast<u32x2*>(&btl[buf][brow + 16][bcq]) = u32x2{pair_lo(t.b1[0], t.b1[1]), pair_lo(t.b1[2], t.b1[3])};
+      store_b_planes(t, buf);
     } else if constexpr (A24) {
       *reinterpret_cast<u32x4*>(&ath[buf][tid >> 4][(tid & 15) * 8]) = t.a0;
       *reinterpret_cast<u32x4*>(&ath[buf][16 + (tid >> 4)][(tid & 15) * 8]) = t.a1;
@@ -817,10 +821,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const uint32_t* __res
       }
       *reinterpret_cast<u32x4*>(&atl[buf][tid >> 3][(tid & 7) * 16]) = e0;
       *reinterpret_cast<u32x4*>(&atl[buf][tid >> 3][(tid & 7) * 16 + 8]) = e1;
-      *reinterpret_cast<u32x2*>(&bth[buf][brow][bcq]) = u32x2{pair_hi(t.b0[0], t.b0[1]), pair_hi(t.b0[2], t.b0[3])};
-      *reinterpret_cast<u32x2*>(&btl[buf][brow][bcq]) = u32x2{pair_lo(t.b0[0], t.b0[1]), pair_lo(t.b0[2], t.b0[3])};
-      *reinterpret_cast<u32x2*>(&bth[buf][brow + 16][bcq]) = u32x2{pair_hi(t.b1[0], t.b1[1]), pair_hi(t.b1[2], t.b1[3])};
-      *reinterpret_cast<u32x2*>(&btl[buf][brow + 16][bcq]) = u32x2{pair_lo(t.b1[0], t.b1[1]), pair_lo(t.b1[2], t.b1[3])};
+      store_b_planes(t, buf);
     } else {
       *reinterpret_cast<u32x4*>(&at[buf][arow][acq]) = t.a0;
       *reinterpret_cast<u32x4*>(&at[buf][arow + 8][acq]) = t.a1;
@@ -1032,11 +1033,8 @@ int launch_gemm_strip_bf16(const char* tag, const uint32_t* a, const uint16_t* b
   const GemmStripForm f = gemm_strip_bf16_form(m, n, k);
   if (forms_only()) return form_report(tag, "gemm_strip_bf16<ks=%d>", f.ks);
   ProfScope prof(tag, stream);
-  switch (f.ks) {
-    case 2: hipLaunchKernelGGL(gemm_strip_bf16_kernel<2>, f.grid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k); break;
-    case 4: hipLaunchKernelGGL(gemm_strip_bf16_kernel<4>, f.grid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k); break;
-    default: hipLaunchKernelGGL(gemm_strip_bf16_kernel<8>, f.grid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k); break;
-  }
+  const auto kernel = f.ks == 2 ? gemm_strip_bf16_kernel<2> : f.ks == 4 ? gemm_strip_bf16_kernel<4> : gemm_strip_bf16_kernel<8>;
+  hipLaunchKernelGGL(kernel, f.grid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k);
   return check_launch();
 }
 
@@ -1064,7 +1062,7 @@ static GemmNnBf16Form gemm_nn_bf16_form(int64_t m, int n, int k, bool have_split
            ((m + BM) * (int64_t)k * 4 < (1ll << 32)) && ((int64_t)(n + 128) * f.kp * 2 < (1ll << 32));
   if (a24 && (!f.fast || k % 64 != 0)) f.status = SE3_ERR_UNSUPPORTED;
   // T16: mega tiles of 256 k; its rows are 2.25 bytes per element, addressed with 32-bit byte offsets like the others
-  if (a16 && (k % 256 != 0 || (m + BM) * ((int64_t)k / 32 * 72) >= (1ll << 32) || (int64_t)(n + 128) * f.kp * 2 >= (1ll << 32)))
+  if (a16 && (k % 256 != 0 || (m + BM) * gemm_a_row_bytes(afmt, k) >= (1ll << 32) || (int64_t)(n + 128) * f.kp * 2 >= (1ll << 32)))
     f.status = SE3_ERR_UNSUPPORTED;
   if (f.status) return f;
   f.st_per = (f.per + 1) / 2;  // 3-byte / T16 rows: the kernels walk super tiles of 64 k
@@ -1076,6 +1074,32 @@ static GemmNnBf16Form gemm_nn_bf16_form(int64_t m, int n, int k, bool have_split
   f.splits = splits;
   f.mode = splits > 1 ? 2 : out_packed ? 1 : 0;
   return f;
+}
+
+// The NN kernel of a form, by (output mode; row format; `fast`, 64-column blocks per workgroup - 1)
+using NnWordsKernel = void (*)(const uint32_t*, const uint16_t*, const uint16_t*, void*, int64_t, int, int, int, int, const float*, float);
+using NnPlanesKernel = void (*)(const uint8_t*, const uint16_t*, const uint16_t*, void*, int64_t, int, int, int, const float*, float);
+struct NnKernels { NnWordsKernel words[2][2]; NnPlanesKernel t24[2], t16[2]; };
+template <int MODE>
+static constexpr NnKernels nn_kernels() {
+  return {{{gemm_nn_bf16_kernel<MODE, false, 1>, gemm_nn_bf16_kernel<MODE, false, 2>},
+           {gemm_nn_bf16_kernel<MODE, true, 1>, gemm_nn_bf16_kernel<MODE, true, 2>}},
+          {gemm_nn_t24_kernel<MODE, 1>, gemm_nn_t24_kernel<MODE, 2>},
+          {gemm_nn_t16_kernel<MODE, 1>, gemm_nn_t16_kernel<MODE, 2>}};
+}
+static const NnKernels kNnKernels[3] = {nn_kernels<0>(), nn_kernels<1>(), nn_kernels<2>()};
+
+// A kernel whose dynamic LDS exceeds the default limit of 64 KB: the limit is raised once per (device, instantiation) -- a
+// runtime that keeps the attribute per device must see it on every device the process uses; `raised` is the instantiation's
+// set of devices done.  A failure is not cached.
+static int raise_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_t>& raised) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return SE3_ERR_LAUNCH;
+  const uint64_t bit = 1ull << (dev & 63);
+  if (raised.load(std::memory_order_relaxed) & bit) return SE3_OK;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return SE3_ERR_LAUNCH;
+  raised.fetch_or(bit, std::memory_order_relaxed);
+  return SE3_OK;
 }
 
 static int gemm_nn_bf16_rows(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, void* c,
@@ -1091,51 +1115,22 @@ static int gemm_nn_bf16_rows(const char* tag, const uint32_t* a, const uint16_t*
     else form_report(tag, "gemm_nn_%s<mode=%d,nb=%d>", afmt == 2 ? "t16" : "t24", f.mode, f.nb);
     if (splits > 1 && !defer) form_report(tag, "reduce_splits<packed=%d>", out_packed);
   } else {
-#define SE3_NN_LAUNCH(MODE, F, NBV)                                                                                   \
-  if (f.afmt == 0 && f.mode == MODE && f.fast == F && f.nb == NBV)                                                      \
-    hipLaunchKernelGGL((gemm_nn_bf16_kernel<MODE, F, NBV>), grid, dim3(256), 0, stream, a, bt_hi, bt_lo, out, m, n,     \
-                       k, kp, per, alpha_num, alpha_scale)
-#define SE3_NN_LAUNCH24(MODE, NBV)                                                                                    \
-  if (f.afmt == 1 && f.mode == MODE && f.nb == NBV) {                                                                   \
-    constexpr int lds_bytes = gemm_nn_t24_lds_bytes(NBV);                                                              \
-    if (lds_bytes > 64 * 1024) {  /* beyond the default dynamic-LDS limit: raised once per (device, instantiation) -- a \
-                                     runtime that keeps the attribute per device must see it on every device the      \
-                                     process uses; a failure is not cached */                                          \
-      static std::atomic<uint64_t> raised{0};                                                                          \
-      int dev_ = 0;                                                                                                   \
-      if (hipGetDevice(&dev_) != hipSuccess) return SE3_ERR_LAUNCH;                                                   \
-      const uint64_t bit_ = 1ull << (dev_ & 63);                                                                      \
-      if (!(raised.load(std::memory_order_relaxed) & bit_)) {                                                         \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nn_t24_kernel<MODE, NBV>),                        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)                 \
-          return SE3_ERR_LAUNCH;                                                                                      \
-        raised.fetch_or(bit_, std::memory_order_relaxed);                                                             \
-      }                                                                                                               \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((gemm_nn_t24_kernel<MODE, NBV>), grid, dim3(256), lds_bytes, stream, (const uint8_t*)a,         \
-                       bt_hi, bt_lo, out, m, n, k, st_per, alpha_num, alpha_scale);                                   \
-  }
-#define SE3_NN_LAUNCH16(MODE, NBV)                                                                                    \
-  if (f.afmt == 2 && f.mode == MODE && f.nb == NBV)                                                                     \
-    hipLaunchKernelGGL((gemm_nn_t16_kernel<MODE, NBV>), grid, dim3(256), 0, stream, (const uint8_t*)a, bt_hi, bt_lo,   \
-                       out, m, n, k, st_per, alpha_num, alpha_scale)
-#define SE3_NN(MODE)                          \
-  SE3_NN_LAUNCH16(MODE, 2);                   \
-  else SE3_NN_LAUNCH16(MODE, 1);              \
-  else SE3_NN_LAUNCH24(MODE, 2)               \
-  else SE3_NN_LAUNCH24(MODE, 1)               \
-  else SE3_NN_LAUNCH(MODE, true, 2);          \
-  else SE3_NN_LAUNCH(MODE, true, 1);          \
-  else SE3_NN_LAUNCH(MODE, false, 2);         \
-  else SE3_NN_LAUNCH(MODE, false, 1)
-    SE3_NN(2);
-    else SE3_NN(1);
-    else SE3_NN(0);
-    else return SE3_ERR_UNSUPPORTED;
-#undef SE3_NN
-#undef SE3_NN_LAUNCH
-#undef SE3_NN_LAUNCH24
-#undef SE3_NN_LAUNCH16
+    const bool planes = f.afmt == 1 || f.afmt == 2;
+    if (f.mode < 0 || f.mode > 2 || f.nb < 1 || f.nb > 2 || (f.afmt != 0 && !planes)) return SE3_ERR_UNSUPPORTED;
+    const NnKernels& ks = kNnKernels[f.mode];
+    if (planes) {
+      const NnPlanesKernel kernel = f.afmt == 1 ? ks.t24[f.nb - 1] : ks.t16[f.nb - 1];
+      const int lds_bytes = f.afmt == 1 ? gemm_nn_t24_lds_bytes(f.nb) : 0;  // t16: static LDS
+      // per t24 instantiation [mode][nb - 1]: the devices whose limit has been raised (only nb = 2, 72 KB, is beyond the default)
+      static std::atomic<uint64_t> raised[3][2];
+      if (lds_bytes > 64 * 1024)
+        if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, raised[f.mode][f.nb - 1])) return rc;
+      hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, stream, (const uint8_t*)a, bt_hi, bt_lo, out, m, n, k, st_per,
+                         alpha_num, alpha_scale);
+    } else {
+      hipLaunchKernelGGL(ks.words[f.fast][f.nb - 1], grid, dim3(256), 0, stream, a, bt_hi, bt_lo, out, m, n, k, kp, per,
+                         alpha_num, alpha_scale);
+    }
   }
   if (splits > 1) {
     const int64_t count = m * n;
@@ -1171,7 +1166,7 @@ int launch_gemm_nn_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_h
   ProfScope prof(tag, stream);
   if (!max_rows)
     return gemm_nn_bf16_rows(tag, a, bt_hi, bt_lo, c, out_packed, m, n, k, split_ws, alpha_num, alpha_scale, stream, afmt, defer);
-  const int64_t a_row_bytes = afmt == 2 ? (int64_t)k / 32 * 72 : (int64_t)k * (afmt == 1 ? 3 : 4);
+  const int64_t a_row_bytes = gemm_a_row_bytes(afmt, k);
   for (int64_t m0 = 0; m0 < m; m0 += max_rows) {
     const int64_t mb = m - m0 < max_rows ? m - m0 : max_rows;
     if (int rc = gemm_nn_bf16_rows(tag, reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a) + m0 * a_row_bytes), bt_hi,
@@ -1228,6 +1223,10 @@ int launch_gemm_tn_bf16(const char* tag, const uint32_t* a, const uint32_t* b, f
   }
   ProfScope prof(tag, stream);
   const int64_t chunk = f.chunk, zs = f.zs;
+  const auto kernel = !f.fast      ? gemm_tn_bf16_kernel<false, 0>
+                      : f.afmt == 2 ? gemm_tn_bf16_kernel<true, 2>
+                      : f.afmt == 1 ? gemm_tn_bf16_kernel<true, 1>
+                                    : gemm_tn_bf16_kernel<true, 0>;
   for (int64_t z0 = 0; z0 < splits; z0 += zs) {
     const int64_t zn = splits - z0 < zs ? splits - z0 : zs, r0 = z0 * chunk;
     if (r0 >= m) {  // ranges past the last row (rounding of chunk): their partials are zeros
@@ -1236,16 +1235,10 @@ int launch_gemm_tn_bf16(const char* tag, const uint32_t* a, const uint32_t* b, f
     }
     const int64_t mb = m - r0 < zn * chunk ? m - r0 : zn * chunk;
     const dim3 grid((unsigned)((ka + 127) / 128), (unsigned)((n + BN - 1) / BN), (unsigned)zn);
-    const int64_t a_row_bytes = afmt == 2 ? (int64_t)ka / 32 * 72 : (int64_t)ka * (afmt == 1 ? 3 : 4);
-    const uint32_t* ab = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a) + r0 * a_row_bytes);
+    const uint32_t* ab = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a) + r0 * gemm_a_row_bytes(afmt, ka));
     const uint32_t* bb = b + r0 * n;
     float* pb = partials + z0 * ka * n;
-    switch (f.fast ? f.afmt : -1) {
-      case 2: hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 2>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk); break;
-      case 1: hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 1>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk); break;
-      case 0: hipLaunchKernelGGL((gemm_tn_bf16_kernel<true, 0>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk); break;
-      default: hipLaunchKernelGGL((gemm_tn_bf16_kernel<false, 0>), grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk); break;
-    }
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, ab, bb, pb, mb, ka, n, chunk);
   }
   if (defer) {
     defer->sum(partials, c, (int64_t)ka * n, splits, alpha_num, alpha_scale, false, out_ikn ? n : 0);

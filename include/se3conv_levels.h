@@ -46,6 +46,9 @@
  *     SE3_ERR_INVALID_ARGUMENT;
  *   - `workspace_bytes` below the query's value: SE3_ERR_WORKSPACE.
  *
+ * What reads the padded levels afterwards -- per-batch boxes, ball query, self-k-NN and PCA frames with the same kind of
+ * device-side row count -- is declared in se3conv_padded.h.
+ *
  * Launches per level: those of se3_grid_subsample for a level of cell averages; for a random level the pick, which also
  * gathers the level's points and batch ids, replaces the average and the batch-id kernel (one launch fewer).
  */

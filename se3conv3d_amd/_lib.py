@@ -138,6 +138,19 @@ FORMS_SIGNATURES = {
     "se3conv_forms": (C.c_int, [_SHP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _SZ]),
 }
 
+# the geometry builds on padded clouds -- row counts in device words -- declared in include/se3conv_padded.h (additions inside
+# ABI version 6 as well); must list every symbol that header declares
+PADDED_SIGNATURES = {
+    "se3_batch_aabb_padded": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P]),
+    "se3_ball_query_padded_workspace_bytes": (_SZ, [_I64, _I64]),
+    "se3_ball_query_padded": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I64, _I64, _P, _P, _I32, _P, _SZ, _I32, _P, _SZ, _I64, _P,
+                                        _P, _P, _P, _P]),
+    "se3_knn_grid_params_padded": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P]),
+    "se3_knn_query_padded_workspace_bytes": (_SZ, [_I64, _I32]),
+    "se3_knn_query_padded": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _I32, _P, _P, _SZ, _P]),
+    "se3_pca_frames_padded": (C.c_int, [_P, _P, _I64, _P, _I32, _I32, _P, _P]),
+}
+
 _lib = None
 
 
@@ -155,7 +168,8 @@ def load() -> C.CDLL:
     if lib.se3_abi_version() != ABI_VERSION:  # (checked before the symbols: an older library lacks some of them)
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
-    for name, (res, args) in list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items()) + list(FORMS_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items()) + list(FORMS_SIGNATURES.items())
+                                   + list(PADDED_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so

@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from .layers import PreProcessModule
+from .pc import refuse_padded
 
 FUSED = os.environ.get("SE3_BLOCKS_FUSED", "1") != "0"
 
@@ -38,6 +39,7 @@ class DropPathPC(torch.nn.Module):
         self.drop_prob_ = p_drop_prob
 
     def forward(self, p_x, p_pc):
+        refuse_padded(p_pc, "DropPathPC")
         if self.drop_prob_ == 0.0 or not self.training:
             return p_x
         keep = 1.0 - self.drop_prob_
@@ -57,6 +59,7 @@ class SkipConnection(torch.nn.Module):
         self.gamma_ = torch.nn.Parameter(torch.full((1, p_num_features), float(p_init_gamma)))
 
     def forward(self, p_x, p_y, p_pc):
+        refuse_padded(p_pc, "SkipConnection")
         # drop_prob >= 1 (keep <= 0): the reference divides by zero (DropPathPC.py:45) -- the plain formulation reproduces
         # that instead of handing the kernel keep = 0, which it reads as "the gate is the factor itself"
         if not _fused(p_x) or p_x.shape != p_y.shape or (self.training and self.drop_path_.drop_prob_ >= 1.0):
@@ -85,6 +88,7 @@ class BatchNormPC(NormLayerPC):
         self.layer_ = torch.nn.BatchNorm1d(p_num_features, momentum=0.2)
 
     def forward(self, p_x, p_pc):
+        refuse_padded(p_pc, "BatchNormPC (its statistics need the present-row count)")
         bn = self.layer_
         if not (_fused(p_x) and bn.training and bn.track_running_stats and bn.momentum is not None):
             return bn(p_x)
@@ -119,6 +123,7 @@ class ResNetFormer(Block):
             self.skip_conv_ = torch.nn.Linear(c_in, c_out)
 
     def forward(self, p_pc_in, p_in_features, p_neighborhood):
+        refuse_padded(p_pc_in, "ResNetFormer")
         x = self.spatial_conv_(p_pc_in=p_pc_in, p_pc_out=p_pc_in, p_in_features=self.norm_1_(p_in_features, p_pc_in),
                                p_neighborhood=p_neighborhood)
         x = self.skip_path_1_(x, p_in_features, p_pc_in)

@@ -504,10 +504,17 @@ int launch_prep_weights(const float* w, int c_in, int kb, int c_out, int mode, u
 // squared distance of the kNN kernels: one expression for the all-pairs scan and the grid search, so that both
 // order equal-looking candidates identically
 __device__ __forceinline__ float knn_dist2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
+// The number of present rows of an array of `n`: the device word `n_valid` clamped to [0, n], or n without one.  Read once
+// per kernel into a (wave-uniform) scalar, in front of its loops.
+__device__ __forceinline__ int64_t present_rows(const int32_t* __restrict__ n_valid, int64_t n) {
+  return n_valid ? max(min((int64_t)*n_valid, n), (int64_t)0) : n;
+}
+// n_valid (device word, may be NULL = every row): the padded self query of se3conv_padded.h -- queries and candidates are
+// the rows in front of it, the rows of `out` from it on are set to -1
 int launch_knn_bruteforce(const float* pts, const int32_t* batch_ids, int64_t n, const float* qpts, const int32_t* qbatch,
-                          int64_t m, int k, int32_t* out, hipStream_t stream);
+                          int64_t m, int k, int32_t* out, hipStream_t stream, const int32_t* n_valid = nullptr);
 int launch_knn_listed(const float* pts, const int32_t* batch_ids, int64_t n, int k, int32_t* out, const int32_t* list,
-                      const int32_t* list_count, hipStream_t stream);
+                      const int32_t* list_count, hipStream_t stream, const int32_t* n_valid = nullptr);
 
 // The K best (distance, index) pairs of a stream of candidates, ascending in (distance, index) -- the order of the
 // reference's sweep (knn_query.cu:68, strict '<' while scanning ascending indices).  Lists live in registers (K is a

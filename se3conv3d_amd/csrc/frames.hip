@@ -28,7 +28,18 @@ __global__ __launch_bounds__(kKnnQueries* S) void knn_kernel(const float* __rest
                                                              const int32_t* __restrict__ batch_ids, int64_t n,
                                                              const float* __restrict__ qpts,
                                                              const int32_t* __restrict__ qbatch, int64_t m, int k_out,
-                                                             int32_t* __restrict__ out) {
+                                                             int32_t* __restrict__ out,
+                                                             const int32_t* __restrict__ n_valid) {
+  // n_valid (padded self query, se3conv_padded.h): queries and candidates are the rows in front of *n_valid; the rows of
+  // `out` from there on get -1 and nothing of them is read.  A block without a present query is done before it reads.
+  const int64_t rows = m;
+  if (n_valid) {
+    m = n = present_rows(n_valid, m);
+    const int64_t q = (int64_t)blockIdx.x * kKnnQueries + (threadIdx.x & 63);
+    if ((threadIdx.x >> 6) == 0 && q >= m && q < rows)
+      for (int e = 0; e < k_out; ++e) out[q * k_out + e] = -1;
+    if ((int64_t)blockIdx.x * kKnnQueries >= m) return;
+  }
   __shared__ float4 tile[S][64];  // per wavefront: x, y, z, batch id (as bits)
   __shared__ float m_d[S][K][kKnnQueries];
   __shared__ int m_i[S][K][kKnnQueries];
@@ -147,9 +158,15 @@ __device__ __forceinline__ void jacobi3(float a[3][3], float v[3][3]) {
 
 // frames_out [n, NF, 9]: NF = 4 (axis_fixed < 0) or 2.
 __global__ void pca_frames_kernel(const float* __restrict__ pts, const int32_t* __restrict__ knn, int64_t n, int k,
-                                  int axis_fixed, float* __restrict__ frames) {
+                                  int axis_fixed, float* __restrict__ frames, const int32_t* __restrict__ n_valid) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  // an absent row of a padded cloud (se3conv_padded.h): the identity in every copy, nothing of the row is read
+  if (i >= present_rows(n_valid, n)) {
+    const int copies = axis_fixed >= 0 ? 2 : 4;
+    for (int t = 0; t < copies * 9; ++t) frames[i * copies * 9 + t] = (t % 9) % 4 == 0 ? 1.f : 0.f;
+    return;
+  }
   // neighbourhood matrix (missing neighbours -> the point itself, RotationFunctions.py:314-317)
   float mean[3] = {0.f, 0.f, 0.f};
   for (int e = 0; e < k; ++e) {
@@ -257,7 +274,9 @@ __global__ __launch_bounds__(64 * kListedWaves) void knn_listed_kernel(const flo
                                                                        const int32_t* __restrict__ batch_ids,
                                                                        int64_t n, int k_out, int32_t* __restrict__ out,
                                                                        const int32_t* __restrict__ list,
-                                                                       const int32_t* __restrict__ list_count) {
+                                                                       const int32_t* __restrict__ list_count,
+                                                                       const int32_t* __restrict__ n_valid) {
+  n = present_rows(n_valid, n);  // (padded cloud: the batch segments end with the present rows)
   __shared__ float w_d[kListedWaves][K];
   __shared__ int w_i[kListedWaves][K];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -311,10 +330,11 @@ __global__ __launch_bounds__(64 * kListedWaves) void knn_listed_kernel(const flo
 }  // namespace
 
 int launch_knn_bruteforce(const float* pts, const int32_t* batch_ids, int64_t n, const float* qpts, const int32_t* qbatch,
-                          int64_t m, int k, int32_t* out, hipStream_t s) {
+                          int64_t m, int k, int32_t* out, hipStream_t s, const int32_t* n_valid) {
   const dim3 grid((unsigned)((m + kKnnQueries - 1) / kKnnQueries));
 #define SE3_KNN(K, S) \
-  hipLaunchKernelGGL((knn_kernel<K, S>), grid, dim3(kKnnQueries * S), 0, s, pts, batch_ids, n, qpts, qbatch, m, k, out)
+  hipLaunchKernelGGL((knn_kernel<K, S>), grid, dim3(kKnnQueries * S), 0, s, pts, batch_ids, n, qpts, qbatch, m, k, out, \
+                     n_valid)
   if (k <= 8) SE3_KNN(8, kKnnSlices);
   else if (k <= 16) SE3_KNN(16, kKnnSlices);
   else if (k <= 32) SE3_KNN(32, kKnnSlices);
@@ -324,12 +344,12 @@ int launch_knn_bruteforce(const float* pts, const int32_t* batch_ids, int64_t n,
 }
 
 int launch_knn_listed(const float* pts, const int32_t* batch_ids, int64_t n, int k, int32_t* out, const int32_t* list,
-                      const int32_t* list_count, hipStream_t s) {
+                      const int32_t* list_count, hipStream_t s, const int32_t* n_valid) {
   // the list length lives on the device: a fixed grid of blocks strides over it
   const dim3 grid((unsigned)(n < 512 ? (n > 0 ? n : 1) : 512)), block(64 * kListedWaves);
-  if (k <= 8) hipLaunchKernelGGL(knn_listed_kernel<8>, grid, block, 0, s, pts, batch_ids, n, k, out, list, list_count);
-  else if (k <= 16) hipLaunchKernelGGL(knn_listed_kernel<16>, grid, block, 0, s, pts, batch_ids, n, k, out, list, list_count);
-  else hipLaunchKernelGGL(knn_listed_kernel<32>, grid, block, 0, s, pts, batch_ids, n, k, out, list, list_count);
+  if (k <= 8) hipLaunchKernelGGL(knn_listed_kernel<8>, grid, block, 0, s, pts, batch_ids, n, k, out, list, list_count, n_valid);
+  else if (k <= 16) hipLaunchKernelGGL(knn_listed_kernel<16>, grid, block, 0, s, pts, batch_ids, n, k, out, list, list_count, n_valid);
+  else hipLaunchKernelGGL(knn_listed_kernel<32>, grid, block, 0, s, pts, batch_ids, n, k, out, list, list_count, n_valid);
   return check_launch();
 }
 }  // namespace se3
@@ -402,6 +422,18 @@ extern "C" int se3_pca_frames(const float* pts, const int32_t* knn, int64_t n, i
   if (n == 0) return SE3_OK;
   if (!pts || !knn || !frames) return SE3_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(pca_frames_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (hipStream_t)stream, pts, knn,
-                     n, (int)k, axis_fixed < 0 ? -1 : (int)axis_fixed, frames);
+                     n, (int)k, axis_fixed < 0 ? -1 : (int)axis_fixed, frames, (const int32_t*)nullptr);
+  return check_launch();
+}
+
+// ---- padded clouds (include/se3conv_padded.h) ---------------------------------------------------------------------------
+extern "C" int se3_pca_frames_padded(const float* pts, const int32_t* knn, int64_t n_rows, const int32_t* n_valid, int32_t k,
+                                     int32_t axis_fixed, float* frames, void* stream) {
+  if (n_rows < 0 || k < 1 || axis_fixed > 2) return SE3_ERR_INVALID_ARGUMENT;
+  if (axis_fixed == 0 || n_rows >= (1ll << 31)) return SE3_ERR_UNSUPPORTED;
+  if (n_rows == 0) return SE3_OK;
+  if (!pts || !knn || !frames) return SE3_ERR_INVALID_ARGUMENT;
+  hipLaunchKernelGGL(pca_frames_kernel, dim3((unsigned)((n_rows + 127) / 128)), dim3(128), 0, (hipStream_t)stream, pts, knn,
+                     n_rows, (int)k, axis_fixed < 0 ? -1 : (int)axis_fixed, frames, n_valid);
   return check_launch();
 }

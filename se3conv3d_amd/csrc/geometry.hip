@@ -15,15 +15,11 @@
 #include "common.h"
 #include "../../include/se3conv_capped.h"
 #include "../../include/se3conv_levels.h"
+#include "../../include/se3conv_padded.h"
 
 namespace se3 {
 
 namespace {
-
-// The number of present rows of an array of `n`: the device word `n_valid` clamped to [0, n], or n without one.
-__device__ __forceinline__ int64_t present_rows(const int32_t* __restrict__ n_valid, int64_t n) {
-  return n_valid ? max(min((int64_t)*n_valid, n), (int64_t)0) : n;
-}
 
 __device__ __forceinline__ void cell_of(const float* __restrict__ pts, const int32_t* __restrict__ batch_ids,
                                         const float* __restrict__ aabb_min, const int nc[3], const float inv[3],
@@ -88,9 +84,16 @@ __global__ void compute_keys_kernel(const float* __restrict__ pts, const int32_t
   }
 }
 
+// n_valid (device, may be NULL = n): the sort has put the absent rows of a padded cloud behind position *n_valid; their
+// points are not read and their records are zeros
 __global__ void gather_sorted_points_kernel(const float* __restrict__ pts, const int32_t* __restrict__ ids, int64_t n,
-                                            float4* __restrict__ spts) {
+                                            float4* __restrict__ spts, const int32_t* __restrict__ n_valid) {
+  const int64_t valid = present_rows(n_valid, n);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (i >= valid) {
+      spts[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      continue;
+    }
     const int id = ids[i];
     spts[i] = make_float4(pts[(int64_t)id * 3], pts[(int64_t)id * 3 + 1], pts[(int64_t)id * 3 + 2], __int_as_float(id));
   }
@@ -112,14 +115,23 @@ template <class KEY>
 __global__ void find_ranges_kernel(const float* __restrict__ pts_dst, const int32_t* __restrict__ batch_dst,
                                    const float* __restrict__ aabb_min, const int32_t* __restrict__ num_cells,
                                    float radius, const typename KEY::type* __restrict__ skeys, int n_src, int64_t n_dst,
-                                   int2* __restrict__ ranges, const int32_t* __restrict__ order) {
+                                   int2* __restrict__ ranges, const int32_t* __restrict__ order,
+                                   const int32_t* __restrict__ n_valid_src, const int32_t* __restrict__ n_valid_dst) {
   const int nc[3] = {KEY::cells(num_cells[0]), KEY::cells(num_cells[1]), KEY::cells(num_cells[2])};
   const float inv_r = 1.0f / radius;
   const float inv[3] = {inv_r, inv_r, inv_r};
+  // padded clouds (se3conv_padded.h): the searches run over the present prefix of the sorted keys, and an absent sample --
+  // not read -- gets nine empty windows
+  n_src = (int)present_rows(n_valid_src, n_src);
+  const int64_t valid_dst = present_rows(n_valid_dst, n_dst);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_dst * 9; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t j = i / 9;
     const int o = (int)(i - j * 9);
     const int64_t s = order ? order[j] : j;  // a cloud against itself: samples in cell order (see BqPlan::ordered)
+    if (s >= valid_dst) {
+      ranges[s * 9 + o] = make_int2(0, 0);
+      continue;
+    }
     int cell[3], b;
     cell_of(pts_dst, batch_dst, aabb_min, nc, inv, s, cell, b);
     const int x = cell[0] + o / 3 - 1, y = cell[1] + o % 3 - 1;
@@ -246,6 +258,10 @@ struct BqScanArgs {
   const float* pts_src;
   const int32_t* batch_src;
   int n_src;
+  // padded clouds (se3conv_padded.h), device words, NULL = every row: sources and samples from the counts on are absent --
+  // never read, never listed, no hits
+  const int32_t* n_valid_src;
+  const int32_t* n_valid_dst;
 };
 
 // One sample of one pass, in the lanes of its wavefront: begin, consume 64 candidates at a time in candidate order, finish.
@@ -342,7 +358,9 @@ __global__ __launch_bounds__(256) void scan_candidates_kernel(const BqScanArgs a
   const int64_t s = a.order ? a.order[w] : w;  // the wavefronts of a workgroup then share their candidate windows
   BqSample<PASS, CAPPED> sample;
   if (!sample.begin(a, s, lane)) return;
-  const float sx = a.pts_dst[s * 3], sy = a.pts_dst[s * 3 + 1], sz = a.pts_dst[s * 3 + 2];
+  const bool present = s < present_rows(a.n_valid_dst, a.n_dst);  // (an absent sample's windows are empty)
+  const float sx = present ? a.pts_dst[s * 3] : 0.f, sy = present ? a.pts_dst[s * 3 + 1] : 0.f,
+              sz = present ? a.pts_dst[s * 3 + 2] : 0.f;
   int lo[9], pre[10];
   pre[0] = 0;
 #pragma unroll
@@ -385,21 +403,25 @@ template <BqPass PASS, bool CAPPED = false>
 __global__ __launch_bounds__(256) void scan_all_kernel(const BqScanArgs a) {
   static_assert(PASS != BqPass::kThreshold || CAPPED, "the threshold pass belongs to the capped query");
   const int lane = threadIdx.x & 63;
+  const int n_src = (int)present_rows(a.n_valid_src, a.n_src);
   if (PASS == BqPass::kCount) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < a.n_src)
+    if (t < n_src)
       a.recs[t] = make_float4(a.pts_src[t * 3], a.pts_src[t * 3 + 1], a.pts_src[t * 3 + 2], __int_as_float(a.batch_src[t]));
   }
   const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (s >= a.n_dst) return;
   BqSample<PASS, CAPPED> sample;
   if (!sample.begin(a, s, lane)) return;
-  const float sx = a.pts_dst[s * 3], sy = a.pts_dst[s * 3 + 1], sz = a.pts_dst[s * 3 + 2];
-  const int sb = a.batch_dst[s];
-  for (int c0 = 0; c0 < a.n_src; c0 += 64) {
+  const bool present = s < present_rows(a.n_valid_dst, a.n_dst);
+  const float sx = present ? a.pts_dst[s * 3] : 0.f, sy = present ? a.pts_dst[s * 3 + 1] : 0.f,
+              sz = present ? a.pts_dst[s * 3 + 2] : 0.f;
+  const int sb = present ? a.batch_dst[s] : -1;
+  const int n_scan = present ? n_src : 0;  // an absent sample has no candidates
+  for (int c0 = 0; c0 < n_scan; c0 += 64) {
     const int id = c0 + lane;
     bool hit = false;
-    if (id < a.n_src) {
+    if (id < n_scan) {
       float4 p;  // (the count pass cannot read the records other workgroups are still writing)
       if (PASS != BqPass::kCount) p = a.recs[id];
       else p = make_float4(a.pts_src[(int64_t)id * 3], a.pts_src[(int64_t)id * 3 + 1], a.pts_src[(int64_t)id * 3 + 2],
@@ -547,9 +569,20 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4* __restrict_
                                                        const int32_t* __restrict__ num_cells,
                                                        const float* __restrict__ cell_size, int n, int k_out,
                                                        int32_t* __restrict__ out, int32_t* __restrict__ list,
-                                                       int32_t* __restrict__ list_count) {
+                                                       int32_t* __restrict__ list_count,
+                                                       const int32_t* __restrict__ n_valid) {
   const int gtid = blockIdx.x * blockDim.x + threadIdx.x;
   const int g = gtid & (kKnnGroup - 1);
+  if (n_valid) {
+    // padded cloud (se3conv_padded.h): the sorted order holds the present rows in front of position *n_valid; the absent
+    // rows are the rows of `out` from there on and get -1
+    const int rows = n;
+    n = (int)present_rows(n_valid, n);
+    const int q = gtid / kKnnGroup;
+    if (g == 0 && q >= n && q < rows)
+      for (int e = 0; e < k_out; ++e) out[(int64_t)q * k_out + e] = -1;
+    if (n == 0) return;
+  }
   const int t = min(gtid / kKnnGroup, n - 1);  // whole groups stay together (shuffles below); extras repeat the last query
   const bool writer = g == 0 && gtid / kKnnGroup < n;
   const int nc[3] = {num_cells[0], num_cells[1], num_cells[2]};
@@ -614,8 +647,11 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4* __restrict_
 // sort (kernels and device-to-device copies only); above it, it is the one-sweep radix sort, which issues hipMemsetAsync
 // per pass and whose kernels use scratch memory -- and a captured graph with memset nodes faults on replay next to a live
 // RCCL communicator on the HIP runtime PyTorch 2.10 ships (see the note above se3_csr_transpose_bounded).  Larger inputs
-// therefore take the stable merge sort explicitly (keys here are non-negative with zero bits above end_bit, so both
-// orders agree).
+// therefore take the stable merge sort explicitly (keys of present rows are non-negative with zero bits above end_bit, so
+// both orders agree on them).  The key of an ABSENT row (se3_grid_levels, se3conv_padded.h) is the largest value of the key
+// type, with bits above end_bit also under the 32-bit ball-query keys (30 / 31 bits in use): it sorts last only because every
+// form taken here -- rocPRIM's merge sort below the limit, the stable merge sort above it -- compares FULL keys; begin_bit /
+// end_bit enter nothing but the size query.  A sort by the bits [begin_bit, end_bit) alone would need another absent key.
 constexpr int kRadixIsMergeLimit = 1 << 20;
 // The guard rests on rocPRIM's dispatch rule (device_radix_sort.hpp: block sort, then merge sort up to
 // radix_sort_config<>::merge_sort_limit for keys wider than 2 bytes, one-sweep above): a rocPRIM whose default limit is
@@ -809,7 +845,9 @@ namespace {
 __global__ __launch_bounds__(256) void knn_grid_params_kernel(const int32_t* __restrict__ batch_ids, int64_t n,
                                                               const float* __restrict__ box_min, const float* __restrict__ box_max,
                                                               int n_batches, int k, float cell_factor, float* __restrict__ aabb_min,
-                                                              int32_t* __restrict__ num_cells, float* __restrict__ cell_size) {
+                                                              int32_t* __restrict__ num_cells, float* __restrict__ cell_size,
+                                                              const int32_t* __restrict__ n_valid) {
+  n = present_rows(n_valid, n);  // (padded cloud: the counts are those of the present rows)
   __shared__ float s_c[256], s_e[256];
   __shared__ int s_cells[3][256];
   __shared__ float s_cell;
@@ -877,15 +915,27 @@ extern "C" int se3_knn_grid_params(const int32_t* batch_ids, int64_t n, const fl
   if (n < 0 || n_batches < 1 || k < 1 || !(cell_factor > 0.f)) return SE3_ERR_INVALID_ARGUMENT;
   if (!box_min || !box_max || !aabb_min || !num_cells || !cell_size || (n > 0 && !batch_ids)) return SE3_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(knn_grid_params_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, batch_ids, n, box_min, box_max,
-                     (int)n_batches, (int)k, cell_factor, aabb_min, num_cells, cell_size);
+                     (int)n_batches, (int)k, cell_factor, aabb_min, num_cells, cell_size, (const int32_t*)nullptr);
+  return check_launch();
+}
+
+extern "C" int se3_knn_grid_params_padded(const int32_t* batch_ids, int64_t n_rows, const int32_t* n_valid,
+                                          const float* box_min, const float* box_max, int32_t n_batches, int32_t k,
+                                          float cell_factor, float* aabb_min, int32_t* num_cells, float* cell_size,
+                                          void* stream) {
+  if (n_rows < 0 || n_batches < 1 || k < 1 || !(cell_factor > 0.f)) return SE3_ERR_INVALID_ARGUMENT;
+  if (!box_min || !box_max || !aabb_min || !num_cells || !cell_size || (n_rows > 0 && !batch_ids)) return SE3_ERR_INVALID_ARGUMENT;
+  hipLaunchKernelGGL(knn_grid_params_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, batch_ids, n_rows, box_min, box_max,
+                     (int)n_batches, (int)k, cell_factor, aabb_min, num_cells, cell_size, n_valid);
   return check_launch();
 }
 
 extern "C" size_t se3_knn_query_grid_workspace_bytes(int64_t n) { return knn_layout(n).total; }
 
-extern "C" int se3_knn_query_grid(const float* pts, const int32_t* batch_ids, const float* aabb_min,
-                                  const int32_t* num_cells, const float* cell_size, int64_t n, int32_t k, int32_t* out,
-                                  void* workspace, size_t workspace_bytes, void* stream_) {
+// n_valid (device word, may be NULL = n): the padded call of se3conv_padded.h
+static int knn_query_grid_impl(const float* pts, const int32_t* batch_ids, const float* aabb_min, const int32_t* num_cells,
+                               const float* cell_size, int64_t n, int32_t k, int32_t* out, void* workspace,
+                               size_t workspace_bytes, void* stream_, const int32_t* n_valid) {
   if (n < 0 || k < 1) return SE3_ERR_INVALID_ARGUMENT;
   if (k > 32 || n >= (1ll << 31)) return SE3_ERR_UNSUPPORTED;
   if (n == 0) return SE3_OK;
@@ -906,26 +956,52 @@ extern "C" int se3_knn_query_grid(const float* pts, const int32_t* batch_ids, co
   {
     ProfScope prof("knn_sort", stream);
     hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, aabb_min, num_cells,
-                       cell_size, 0.f, n, keys, ids, (const int32_t*)nullptr);
+                       cell_size, 0.f, n, keys, ids, n_valid);
     if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sids, (int)n, 0, 64, stream) !=
         hipSuccess)
       return SE3_ERR_LAUNCH;
-    hipLaunchKernelGGL(gather_sorted_points_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, pts, sids, n, spts);
+    hipLaunchKernelGGL(gather_sorted_points_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, pts, sids, n, spts, n_valid);
   }
   {
     ProfScope prof("knn_cells", stream);
     const dim3 grid((unsigned)((n * kKnnGroup + 255) / 256));
     if (k <= 8)
-      hipLaunchKernelGGL(knn_grid_kernel<8>, grid, dim3(256), 0, stream, spts, skeys, num_cells, cell_size, (int)n, (int)k, out, list, list_count);
+      hipLaunchKernelGGL(knn_grid_kernel<8>, grid, dim3(256), 0, stream, spts, skeys, num_cells, cell_size, (int)n, (int)k, out, list, list_count, n_valid);
     else if (k <= 16)
-      hipLaunchKernelGGL(knn_grid_kernel<16>, grid, dim3(256), 0, stream, spts, skeys, num_cells, cell_size, (int)n, (int)k, out, list, list_count);
+      hipLaunchKernelGGL(knn_grid_kernel<16>, grid, dim3(256), 0, stream, spts, skeys, num_cells, cell_size, (int)n, (int)k, out, list, list_count, n_valid);
     else
-      hipLaunchKernelGGL(knn_grid_kernel<32>, grid, dim3(256), 0, stream, spts, skeys, num_cells, cell_size, (int)n, (int)k, out, list, list_count);
+      hipLaunchKernelGGL(knn_grid_kernel<32>, grid, dim3(256), 0, stream, spts, skeys, num_cells, cell_size, (int)n, (int)k, out, list, list_count, n_valid);
     if (int rc = check_launch()) return rc;
   }
   ProfScope prof("knn_fallback", stream);
   // exact fallback for the queries the 27-cell block could not settle (sparse regions, cloud boundary)
-  return launch_knn_listed(pts, batch_ids, n, (int)k, out, list, list_count, stream);
+  return launch_knn_listed(pts, batch_ids, n, (int)k, out, list, list_count, stream, n_valid);
+}
+
+extern "C" int se3_knn_query_grid(const float* pts, const int32_t* batch_ids, const float* aabb_min,
+                                  const int32_t* num_cells, const float* cell_size, int64_t n, int32_t k, int32_t* out,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  return knn_query_grid_impl(pts, batch_ids, aabb_min, num_cells, cell_size, n, k, out, workspace, workspace_bytes, stream,
+                             nullptr);
+}
+
+extern "C" size_t se3_knn_query_padded_workspace_bytes(int64_t n_rows, int32_t use_grid) {
+  return use_grid ? knn_layout(n_rows).total : 0;
+}
+
+extern "C" int se3_knn_query_padded(const float* pts, const int32_t* batch_ids, int64_t n_rows, const int32_t* n_valid,
+                                    const float* aabb_min, const int32_t* num_cells, const float* cell_size, int32_t k,
+                                    int32_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_rows < 0 || k < 1) return SE3_ERR_INVALID_ARGUMENT;
+  const bool grid = aabb_min || num_cells || cell_size;
+  if (grid && !(aabb_min && num_cells && cell_size)) return SE3_ERR_INVALID_ARGUMENT;
+  if (k > 64 || (grid && k > 32) || n_rows >= (1ll << 31)) return SE3_ERR_UNSUPPORTED;
+  if (n_rows == 0) return SE3_OK;
+  if (!pts || !batch_ids || !out) return SE3_ERR_INVALID_ARGUMENT;
+  if (grid)
+    return knn_query_grid_impl(pts, batch_ids, aabb_min, num_cells, cell_size, n_rows, k, out, workspace, workspace_bytes,
+                               stream, n_valid);
+  return launch_knn_bruteforce(pts, batch_ids, n_rows, pts, batch_ids, n_rows, (int)k, out, (hipStream_t)stream, n_valid);
 }
 
 // ---- ball query, host side: one plan per call --------------------------------------------------------------------------
@@ -946,6 +1022,8 @@ struct BqCall {
   int32_t *ends, *neighbors, *sources, *info;
   int limit;  // rows of `neighbors`
   CapArgs cap;
+  // padded clouds (se3conv_padded.h): device words, NULL = every row
+  const int32_t *n_valid_src, *n_valid_dst;
 };
 
 // Every decision about a call's shape, taken once per entry-point call and read by the count, threshold and store stages.
@@ -984,7 +1062,8 @@ static BqPlan bq_plan(const BqCall& c, int32_t n_batches, bool bounded, bool gri
   // (count + prefix + store as one launch with a decoupled look-back was measured in round 4: slower, removed --
   // profiles/r04_ball_query_onepass_ab.txt)
   p.inline_prefix = bounded && p.all_pairs && c.n_dst <= kBqInlinePrefixMax;
-  p.ordered = !p.all_pairs && c.pts_src && c.pts_src == c.pts_dst && c.n_src == c.n_dst && c.batch_src == c.batch_dst;
+  p.ordered = !p.all_pairs && c.pts_src && c.pts_src == c.pts_dst && c.n_src == c.n_dst && c.batch_src == c.batch_dst &&
+              c.n_valid_src == c.n_valid_dst;
   p.build_grid = !p.all_pairs && !grid_valid;
   p.threshold = threshold, p.capped = capped;
   p.l = bq_layout(c.n_src, c.n_dst);
@@ -1004,6 +1083,7 @@ static BqScanArgs bq_scan_args(const BqCall& c, const BqPlan& p) {
   a.ranges = (const int2*)(ws + p.l.ranges);
   a.order = p.ordered ? (const int32_t*)(gws + p.l.sids) : nullptr;
   a.pts_src = c.pts_src, a.batch_src = c.batch_src, a.n_src = (int)c.n_src;
+  a.n_valid_src = c.n_valid_src, a.n_valid_dst = c.n_valid_dst;
   return a;
 }
 
@@ -1052,16 +1132,16 @@ static int bq_grid_windows(const BqCall& c, const BqPlan& p, int key_bits) {
     int32_t* ids = (int32_t*)(gws + p.l.ids);
     // cell size = radius in every dimension (BallQuery.py:39-40)
     hipLaunchKernelGGL(compute_keys_kernel<KEY>, dim3(blocks_for(c.n_src)), dim3(256), 0, c.stream, c.pts_src, c.batch_src,
-                       c.aabb_min, c.num_cells, (const float*)nullptr, c.radius, c.n_src, keys, ids, (const int32_t*)nullptr);
+                       c.aabb_min, c.num_cells, (const float*)nullptr, c.radius, c.n_src, keys, ids, c.n_valid_src);
     size_t temp_bytes = p.l.temp_bytes;
     if (sort_pairs_no_scratch(ws + p.l.temp, temp_bytes, keys, skeys, ids, sids, (int)c.n_src, 0, key_bits, c.stream) != hipSuccess)
       return SE3_ERR_LAUNCH;
     hipLaunchKernelGGL(gather_sorted_points_kernel, dim3(blocks_for(c.n_src)), dim3(256), 0, c.stream, c.pts_src, sids,
-                       c.n_src, (float4*)(gws + p.l.spts));
+                       c.n_src, (float4*)(gws + p.l.spts), c.n_valid_src);
   }
   hipLaunchKernelGGL(find_ranges_kernel<KEY>, dim3(blocks_for(c.n_dst * 9)), dim3(256), 0, c.stream, c.pts_dst, c.batch_dst,
                      c.aabb_min, c.num_cells, c.radius, skeys, (int)c.n_src, c.n_dst, (int2*)(ws + p.l.ranges),
-                     p.ordered ? sids : (const int32_t*)nullptr);
+                     p.ordered ? sids : (const int32_t*)nullptr, c.n_valid_src, c.n_valid_dst);
   return SE3_OK;
 }
 
@@ -1156,6 +1236,34 @@ extern "C" int se3_ball_query_bounded_shared(const float* pts_src, const float* 
            (hipStream_t)stream, grid, ends, neighbors, sources, info};
   const BqPlan p = bq_plan(c, n_batches, true, grid_valid != 0);
   if (!grid || grid_bytes < p.l.ranges) return SE3_ERR_WORKSPACE;  // (the source cloud's part of the layout ends at `ranges`)
+  return bq_bounded(c, p, capacity);
+}
+
+// ---- padded clouds (include/se3conv_padded.h) ---------------------------------------------------------------------------
+extern "C" int se3_batch_aabb_padded(const float* pts, const int32_t* batch_ids, int64_t n_rows, const int32_t* n_valid,
+                                     int32_t n_batches, float* aabb_min, float* aabb_max, void* stream_) {
+  if (n_rows < 0 || n_batches < 1) return SE3_ERR_INVALID_ARGUMENT;
+  if (!aabb_min || !aabb_max || (n_rows > 0 && (!pts || !batch_ids))) return SE3_ERR_INVALID_ARGUMENT;
+  return batch_aabb_impl(pts, batch_ids, n_rows, n_batches, aabb_min, aabb_max, nullptr, (hipStream_t)stream_, n_valid);
+}
+
+extern "C" size_t se3_ball_query_padded_workspace_bytes(int64_t n_rows_src, int64_t n_rows_dst) {
+  return bq_layout(n_rows_src, n_rows_dst).total;
+}
+
+extern "C" int se3_ball_query_padded(const float* pts_src, const float* pts_dst, const int32_t* batch_src,
+                                     const int32_t* batch_dst, const float* aabb_min, const int32_t* num_cells, float radius,
+                                     int64_t n_rows_src, int64_t n_rows_dst, const int32_t* n_valid_src,
+                                     const int32_t* n_valid_dst, int32_t n_batches, void* grid, size_t grid_bytes,
+                                     int32_t grid_valid, void* workspace, size_t workspace_bytes, int64_t capacity,
+                                     int32_t* neighbors, int32_t* sources, int32_t* ends, int32_t* info, void* stream) {
+  if (n_rows_src < 0 || n_rows_dst < 0 || n_batches < 1 || !(radius > 0.f)) return SE3_ERR_INVALID_ARGUMENT;
+  if (n_rows_src >= (1ll << 31) || n_rows_dst >= (1ll << 31) / 9) return SE3_ERR_UNSUPPORTED;  // (before any layout is sized)
+  BqCall c{pts_src, pts_dst, batch_src, batch_dst, aabb_min, num_cells, radius, n_rows_src, n_rows_dst, workspace,
+           workspace_bytes, (hipStream_t)stream, grid, ends, neighbors, sources, info};
+  c.n_valid_src = n_valid_src, c.n_valid_dst = n_valid_dst;
+  const BqPlan p = bq_plan(c, n_batches, true, grid && grid_valid != 0);
+  if (grid && grid_bytes < p.l.ranges) return SE3_ERR_WORKSPACE;
   return bq_bounded(c, p, capacity);
 }
 

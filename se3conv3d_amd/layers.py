@@ -188,6 +188,12 @@ class PNEConvLayerRotEquiv(IConvLayer):
       * there is no rot-tensor cache to hash (no D2H copy + SHA-256 per call, :71): the descriptors
         are recomputed inside the kernel.  ``rot_tensor_cache`` / ``empty_rot_tenors_cache`` /
         ``get_rot_tenors`` are kept for API compatibility.
+
+    Padded clouds (``Pointcloud(..., p_n_valid=)``, a neighbourhood built with ``p_capacity``) need nothing of the operator:
+    an absent sample has no edges, so its output rows are exactly 0, and an absent source has none either, so its ``dX``
+    rows are exactly 0.  The caller's obligation: the feature rows of absent points hold FINITE values (the weight gradient
+    is formed as ``sum_p f[p] * U[p]``, and ``U[p] = 0`` does not survive a NaN); which finite values changes no result.
+    ``pre_process_`` reads edge counts on the host: keep it off in a captured step.
     """
 
     rot_tensor_cache = {}

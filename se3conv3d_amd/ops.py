@@ -84,6 +84,25 @@ def _as(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return t.detach().to(dtype).contiguous()
 
 
+def _valid_word(n_valid, device, who: str) -> C.c_void_p:
+    """The row-count word of a padded cloud (include/se3conv_padded.h): one int32 on the device, or None = every row."""
+    p = _ptr(n_valid, torch.int32, "n_valid", device)
+    if n_valid is not None and n_valid.numel() != 1:
+        raise ValueError(f"{who}: n_valid is one int32 word on the device")
+    return p
+
+
+def _padded_cloud(pts, batch_ids, who: str):
+    """A padded cloud is taken as it is -- float32 [N,3] points, int32 [N] batch ids, contiguous: a conversion would read
+    the absent rows (and be a launch of its own)."""
+    if not isinstance(pts, torch.Tensor) or pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"{who}: only [N,3] point sets are supported")
+    _ptr(pts, torch.float32, "pts")
+    _ptr(batch_ids, torch.int32, "batch_ids", pts.device)
+    if tuple(batch_ids.shape) != (pts.shape[0],):
+        raise ValueError(f"{who}: batch_ids of shape {tuple(batch_ids.shape)} for {pts.shape[0]} points")
+
+
 # every buffer the library writes -- results, saved tensors, cached operands -- is allocated through these two names and
 # `_workspace` (tests/hostile_memory.py swaps all three for guard-banded, 0xFF-filled allocations)
 _empty = torch.empty
@@ -128,9 +147,23 @@ class ComputeKeys(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------- ball query (a10)
-def batch_aabb(pts, batch_ids, n_batches: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Per-batch bounding boxes ``(min [B,3], max [B,3])`` (the reference's scatter_min / scatter_max calls)."""
+def batch_aabb(pts, batch_ids, n_batches: Optional[int] = None, n_valid: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-batch bounding boxes ``(min [B,3], max [B,3])`` (the reference's scatter_min / scatter_max calls).
+    ``n_valid`` (int32 device word): a padded cloud -- only rows ``[0, n_valid)`` are present and read
+    (``se3_batch_aabb_padded``); ``n_batches`` is then required."""
     lib = _lib.load()
+    if n_valid is not None:
+        _padded_cloud(pts, batch_ids, "batch_aabb")
+        if n_batches is None:
+            raise ValueError("batch_aabb: a padded cloud needs n_batches (reading it from the batch ids would be a read-back)")
+        dev = pts.device
+        mn = _empty((int(n_batches), 3), dtype=torch.float32, device=dev)
+        mx = _empty((int(n_batches), 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.se3_batch_aabb_padded(_ptr(pts, torch.float32, "pts"), _ptr(batch_ids, torch.int32, "batch_ids", dev),
+                                             pts.shape[0], _valid_word(n_valid, dev, "batch_aabb"), int(n_batches),
+                                             _ptr(mn, torch.float32, "aabb_min"), _ptr(mx, torch.float32, "aabb_max"),
+                                             _stream(dev)), "se3_batch_aabb_padded")
+        return mn, mx
     pts = _as(pts, torch.float32)
     b = _as(batch_ids, torch.int32)
     if n_batches is None:
@@ -235,11 +268,14 @@ class SourceGrids:
         self.params = {}  # per radius: (shifted box minima, cell counts) of the grid (se3_ball_query_grid_from_box)
 
     @staticmethod
-    def key(pts, batch_ids, n_batches):
+    def key(pts, batch_ids, n_batches, n_valid=None):
         """What a grid is valid for: the cloud's OWN points and batch ids (storage and version), not converted copies -- a
-        temporary's address says nothing about the cloud and may be recycled by the next temporary."""
-        return (pts.data_ptr(), pts._version, batch_ids.data_ptr(), batch_ids._version, int(pts.shape[0]),
-                int(n_batches or 0), str(pts.device))
+        temporary's address says nothing about the cloud and may be recycled by the next temporary.  A padded cloud's grid
+        is also keyed on its row-count word (storage and version: a new count is a new grid), which keeps it apart from
+        the grids of the other queries."""
+        key = (pts.data_ptr(), pts._version, batch_ids.data_ptr(), batch_ids._version, int(pts.shape[0]),
+               int(n_batches or 0), str(pts.device))
+        return key if n_valid is None else key + (n_valid.data_ptr(), n_valid._version)
 
     def slot(self, key, radius, nbytes, device):
         """``(buffer, valid)`` for this radius; ``valid`` says the buffer already holds the grid of ``key``.  A buffer
@@ -287,15 +323,20 @@ def forget_source_grids(cloud) -> None:
 
 
 def _bounded_query(who, entries, pts_src, pts_dst, batch_src, batch_dst, radius, capacity, n_batches, neighbors_out, out_error,
-                   src_box, grids, rows_per_sample=0, want_sources=False, want_degrees=False, workspace_bytes=None, tail=None):
+                   src_box, grids, rows_per_sample=0, want_sources=False, want_degrees=False, workspace_bytes=None, tail=None,
+                   n_valid=None):
     """What ``ball_query_bounded`` and ``ball_query_capped`` share: conversions and validation, the result buffers, the
     workspace, the source cloud's shared grid (slot, parameters, commit) and the library call itself.  ``entries``: the C
     entry point without and with the grid arguments (the first None: the second is called either way, with a NULL grid).
     ``capacity=None``: ``n_dst * rows_per_sample`` rows.  ``workspace_bytes(n_src, n_dst)``: where the call needs more
-    than the bounded query.  ``tail(dev, degrees)``: checks and C arguments behind the stream.  Returns ``(neighbors, ends,
+    than the bounded query.  ``tail(dev, degrees)``: checks and C arguments behind the stream.  ``n_valid = (source word,
+    sample word)``: the padded call, which takes the two words behind the row counts and the clouds as they are.  Returns ``(neighbors, ends,
     info, sources, degrees)``."""
     lib = _lib.load()
     src_own, batch_own = pts_src, batch_src  # (what a source grid is keyed on: the caller's tensors, not their conversions)
+    if n_valid is not None:
+        _padded_cloud(pts_src, batch_src, who)
+        _padded_cloud(pts_dst, batch_dst, who)
     pts_src = _as(pts_src, torch.float32)
     pts_dst = _as(pts_dst, torch.float32)
     if pts_src.dim() != 2 or pts_src.shape[1] != 3 or pts_dst.dim() != 2 or pts_dst.shape[1] != 3:
@@ -323,10 +364,15 @@ def _bounded_query(who, entries, pts_src, pts_dst, batch_src, batch_dst, radius,
     needs_grid, ws_bytes, grid_bytes = _ball_query_sizes(n_src, n_dst)
     ws = _workspace(workspace_bytes(n_src, n_dst) if workspace_bytes is not None else ws_bytes, dev)
     grid, valid, key = None, False, None
-    if grids is not None and needs_grid and src_box is not None and SHARED_GRIDS and not torch.cuda.is_current_stream_capturing():
+    capturing = torch.cuda.is_current_stream_capturing()
+    # (a padded query also shares INSIDE a capture: the key then carries the capture's id, so only a grid built by an earlier
+    # node of the same graph counts, which every replay rebuilds first)
+    if grids is not None and needs_grid and src_box is not None and SHARED_GRIDS and (not capturing or n_valid is not None):
         # (src_box: the grid parameters are then a pure function of the cloud's cached boxes and the radius, so two calls
         # with the same key search the same cells -- and the parameters themselves are kept with the grid)
-        key = SourceGrids.key(src_own, batch_own, n_batches)
+        key = SourceGrids.key(src_own, batch_own, n_batches, n_valid[0] if n_valid is not None else None)
+        if capturing:
+            key += (_capture_id(dev),)
         grid, valid = grids.slot(key, radius, grid_bytes, dev)
         params = grids.params.get(float(radius)) if valid else None
         if params is None:
@@ -335,13 +381,14 @@ def _bounded_query(who, entries, pts_src, pts_dst, batch_src, batch_dst, radius,
     else:
         mn, nc = _batch_aabb_min_and_cells(pts_src, bs, radius, n_batches, src_box) if needs_grid else (None, None)
     with_grid = grid is not None or entries[0] is None
+    mid = (_valid_word(n_valid[0], dev, who), _valid_word(n_valid[1], dev, who)) if n_valid is not None else ()
     entry = entries[1] if with_grid else entries[0]
     grid_args = (C.c_void_p(grid.data_ptr() if grid is not None else 0), grid.numel() if grid is not None else 0,
                  int(valid)) if with_grid else ()
     _lib.check(getattr(lib, entry)(
         _ptr(pts_src, f32, "pts_src"), _ptr(pts_dst, f32, "pts_dst", dev), _ptr(bs, i32, "batch_src", dev),
         _ptr(bd, i32, "batch_dst", dev), _ptr(mn, f32, "aabb_min"), _ptr(nc, i32, "num_cells"), float(radius), n_src,
-        n_dst, int(n_batches or 0), *grid_args, C.c_void_p(ws.data_ptr()), ws.numel(), rows, _ptr(neighbors, i32, "neighbors"),
+        n_dst, *mid, int(n_batches or 0), *grid_args, C.c_void_p(ws.data_ptr()), ws.numel(), rows, _ptr(neighbors, i32, "neighbors"),
         _ptr(sources, i32, "sources"), _ptr(ends, i32, "ends"), _ptr(info, i32, "info"), _stream(dev), *extra), entry)
     if grid is not None and not valid:
         grids.commit(key, radius, grid, params)
@@ -364,6 +411,39 @@ def ball_query_bounded(pts_src, pts_dst, batch_src, batch_dst, radius: float, ca
         "ball_query_bounded", ("se3_ball_query_bounded", "se3_ball_query_bounded_shared"), pts_src, pts_dst, batch_src,
         batch_dst, radius, capacity, n_batches, neighbors_out, f"neighbors_out must be a contiguous int32 [{int(capacity)}, 2] tensor",
         src_box, grids, want_sources=want_sources)
+    return (neighbors, ends, info, sources) if want_sources else (neighbors, ends, info)
+
+
+def ball_query_padded(pts_src, pts_dst, batch_src, batch_dst, radius: float, capacity: int, n_batches: int,
+                      n_valid_src: Optional[torch.Tensor] = None, n_valid_dst: Optional[torch.Tensor] = None,
+                      want_sources: bool = False, neighbors_out: Optional[torch.Tensor] = None, src_box=None,
+                      grids: Optional[SourceGrids] = None):
+    """``ball_query_bounded`` between PADDED clouds (``se3_ball_query_padded``, include/se3conv_padded.h): only rows
+    ``[0, n_valid_src)`` of the source arrays and ``[0, n_valid_dst)`` of the sample arrays are present (int32 device
+    words; None = every row).  Absent rows are never read, absent sources never listed, absent samples have no edges
+    (their ``ends`` are flat).  Same results as ``ball_query_bounded`` -- ``(neighbors [capacity,2], ends [rows_dst], info
+    [2][, sources])`` -- and no host synchronisation: capturable, and a replay follows the words.  The clouds are taken as
+    they are (float32 / int32, contiguous); ``n_batches`` is required.  ``src_box``: the source cloud's
+    ``batch_aabb(..., n_valid=n_valid_src)`` when the caller has it.  ``grids``: as for ``ball_query_bounded``; a padded
+    cloud's grid is kept per value of its count word, and the padded queries of ONE graph capture share it too (only a grid
+    that an earlier node of the same graph builds is reused, never one from before the capture).  "Per value" is held
+    through the word's storage and version counter: a word that a graph replay rewrites changes value without moving its
+    version, so the clouds a captured build made must not be queried eagerly with a ``grids`` holder afterwards (build a
+    fresh cloud over the buffers, or ``forget_source_grids`` first)."""
+    lib = _lib.load()
+    if n_batches is None or int(n_batches) < 1:
+        raise ValueError("ball_query_padded: n_batches must be given (reading it from the batch ids would be a read-back)")
+    if capacity is None:
+        raise ValueError("ball_query_padded: needs a capacity")
+    _padded_cloud(pts_src, batch_src, "ball_query_padded")
+    if src_box is None and pts_src.shape[0] > 0 and pts_dst.shape[0] > 0 and ball_query_needs_grid(pts_src.shape[0]):
+        src_box = batch_aabb(pts_src, batch_src, int(n_batches), n_valid_src) if n_valid_src is not None else \
+            batch_aabb(pts_src, batch_src, int(n_batches))
+    neighbors, ends, info, sources, _ = _bounded_query(
+        "ball_query_padded", (None, "se3_ball_query_padded"), pts_src, pts_dst, batch_src, batch_dst, radius, capacity,
+        int(n_batches), neighbors_out, f"neighbors_out must be a contiguous int32 [{int(capacity)}, 2] tensor", src_box, grids,
+        want_sources=want_sources, workspace_bytes=lib.se3_ball_query_padded_workspace_bytes,
+        n_valid=(n_valid_src, n_valid_dst))
     return (neighbors, ends, info, sources) if want_sources else (neighbors, ends, info)
 
 
@@ -801,12 +881,17 @@ def _knn_cell_size(mn, mx, counts, k: int) -> torch.Tensor:
     return torch.maximum(c, (e1.max() * 1e-6).clamp_min(1e-30))
 
 
-def knn_query(pts, batch_ids, k: int, n_batches: Optional[int] = None, method: str = "auto", box=None) -> torch.Tensor:
+def knn_query(pts, batch_ids, k: int, n_batches: Optional[int] = None, method: str = "auto", box=None,
+              n_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``point_cloud_lib_ops.knn_query``: self-kNN inside each batch element, ``[N,k]`` int32 (self first,
     ascending distance, ties to the lower index, -1 padded).  ``method``: "grid" (cell grid + exact fallback),
     "scan" (all pairs inside the batch element) or "auto" (grid from KNN_GRID_MIN_POINTS points on).  ``box``: the
-    cloud's ``batch_aabb`` result when the caller has it (``Pointcloud.aabb()``)."""
+    cloud's ``batch_aabb`` result when the caller has it (``Pointcloud.aabb()``).  ``n_valid`` (int32 device word): a
+    padded cloud (``se3_knn_query_padded``) -- the present rows' neighbours are those of the call on the present rows alone,
+    absent rows get -1; the cell-grid search then needs ``n_batches``."""
     lib = _lib.load()
+    if n_valid is not None:
+        _padded_cloud(pts, batch_ids, "knn_query")
     pts = _as(pts, torch.float32)
     b = _as(batch_ids, torch.int32)
     if pts.dim() != 2 or pts.shape[1] != 3:
@@ -821,27 +906,39 @@ def knn_query(pts, batch_ids, k: int, n_batches: Optional[int] = None, method: s
                          "kernel has the same limit, knn_query.cu:167)")
     if method == "grid" and k > 32:
         raise ValueError("knn_query: the cell-grid search keeps at most 32 neighbours; use method='scan' or 'auto'")
-    if method == "scan" or (method == "auto" and (n < KNN_GRID_MIN_POINTS or k > 32)) or n == 0:
-        _lib.check(lib.se3_knn_query(_ptr(pts, f32, "pts"), _ptr(b, i32, "batch_ids", dev), n, int(k),
-                                     _ptr(out, i32, "out"), _stream(dev)), "se3_knn_query")
+    padded = n_valid is not None
+    mid = (_valid_word(n_valid, dev, "knn_query"),) if padded else ()  # the padded entry points take the word behind the row count
+    p_pts, p_b, p_out, stream = _ptr(pts, f32, "pts"), _ptr(b, i32, "batch_ids", dev), _ptr(out, i32, "out"), _stream(dev)
+
+    def search(mn, num_cells, cell3, ws):
+        """The search itself: through the cell grid with its parameters and workspace, all pairs with None."""
+        grid = [_ptr(t, dt, name) for t, dt, name in ((mn, f32, "aabb_min"), (num_cells, i32, "num_cells"), (cell3, f32, "cell_size"))]
+        space = (C.c_void_p(ws.data_ptr() if ws is not None else 0), ws.numel() if ws is not None else 0)
+        if padded:
+            _lib.check(lib.se3_knn_query_padded(p_pts, p_b, n, *mid, *grid, int(k), p_out, *space, stream), "se3_knn_query_padded")
+        elif mn is None:
+            _lib.check(lib.se3_knn_query(p_pts, p_b, n, int(k), p_out, stream), "se3_knn_query")
+        else:
+            _lib.check(lib.se3_knn_query_grid(p_pts, p_b, *grid, n, int(k), p_out, *space, stream), "se3_knn_query_grid")
         return out
+
+    if method == "scan" or (method == "auto" and (n < KNN_GRID_MIN_POINTS or k > 32)) or n == 0:
+        return search(None, None, None, None)
+    if padded and box is None and n_batches is None:
+        raise ValueError("knn_query: the cell-grid search of a padded cloud needs n_batches or the cloud's boxes")
     # boxes, then cell size / shifted minima / cell counts in ONE launch (se3_knn_grid_params: what _knn_cell_size and the
     # lines of BallQuery.py:34-38 compute -- as a dozen torch calls and a bincount they cost more than the search)
-    box_mn, mx = box if box is not None else batch_aabb(pts, b, n_batches)
+    box_mn, mx = box if box is not None else batch_aabb(pts, b, n_batches, n_valid)
     nb = box_mn.shape[0]
     mn = _empty((nb, 3), dtype=f32, device=dev)
     num_cells = _empty(3, dtype=i32, device=dev)
     cell3 = _empty(3, dtype=f32, device=dev)
-    _lib.check(lib.se3_knn_grid_params(_ptr(b, i32, "batch_ids", dev), n, _ptr(box_mn, f32, "box_min", dev),
-                                       _ptr(mx, f32, "box_max", dev), nb, int(k), float(KNN_CELL_FACTOR), _ptr(mn, f32, "aabb_min"),
-                                       _ptr(num_cells, i32, "num_cells"), _ptr(cell3, f32, "cell_size"), _stream(dev)),
-               "se3_knn_grid_params")
-    ws = _workspace(lib.se3_knn_query_grid_workspace_bytes(n), dev)
-    _lib.check(lib.se3_knn_query_grid(
-        _ptr(pts, f32, "pts"), _ptr(b, i32, "batch_ids", dev), _ptr(mn, f32, "aabb_min"), _ptr(num_cells, i32, "num_cells"),
-        _ptr(cell3, f32, "cell_size"), n, int(k), _ptr(out, i32, "out"), C.c_void_p(ws.data_ptr()), ws.numel(),
-        _stream(dev)), "se3_knn_query_grid")
-    return out
+    params = "se3_knn_grid_params_padded" if padded else "se3_knn_grid_params"
+    _lib.check(getattr(lib, params)(p_b, n, *mid, _ptr(box_mn, f32, "box_min", dev), _ptr(mx, f32, "box_max", dev), nb, int(k),
+                                    float(KNN_CELL_FACTOR), _ptr(mn, f32, "aabb_min"), _ptr(num_cells, i32, "num_cells"),
+                                    _ptr(cell3, f32, "cell_size"), stream), params)
+    ws_bytes = lib.se3_knn_query_padded_workspace_bytes(n, 1) if padded else lib.se3_knn_query_grid_workspace_bytes(n)
+    return search(mn, num_cells, cell3, _workspace(ws_bytes, dev))
 
 
 def knn_query_pair(pts_src, batch_src, pts_q, batch_q, k: int) -> torch.Tensor:
@@ -876,10 +973,14 @@ class KNNQuery(torch.autograd.Function):
         return None, None, None
 
 
-def pca_frames(pts, knn_ids, axis_fixed=None) -> torch.Tensor:
+def pca_frames(pts, knn_ids, axis_fixed=None, n_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``sample_reference_frames_pca`` on the GPU: ``[N,4,9]`` frames (``[N,2,9]`` with a fixed axis 1 or 2).
-    ``axis_fixed`` follows the reference: ``None`` / ``False`` / ``0`` all mean "not fixed"."""
+    ``axis_fixed`` follows the reference: ``None`` / ``False`` / ``0`` all mean "not fixed".  ``n_valid`` (int32 device
+    word): a padded cloud (``se3_pca_frames_padded``) -- absent rows get the identity in every copy and are not read."""
     lib = _lib.load()
+    if n_valid is not None:
+        _ptr(pts, torch.float32, "pts")
+        _ptr(knn_ids, torch.int32, "knn", pts.device)
     pts = _as(pts, torch.float32)
     ids = _as(knn_ids, torch.int32)
     n, k = ids.shape
@@ -888,6 +989,13 @@ def pca_frames(pts, knn_ids, axis_fixed=None) -> torch.Tensor:
         raise ValueError(f"axis_fixed = {axis_fixed}")
     nf = 4 if axis < 0 else 2
     frames = _empty((n, nf, 9), dtype=torch.float32, device=pts.device)
+    if n_valid is not None:
+        if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] != n:
+            raise ValueError(f"pca_frames: {tuple(pts.shape)} points for {n} rows of neighbour ids")
+        _lib.check(lib.se3_pca_frames_padded(_ptr(pts, torch.float32, "pts"), _ptr(ids, torch.int32, "knn", pts.device), n,
+                                             _valid_word(n_valid, pts.device, "pca_frames"), k, axis,
+                                             _ptr(frames, torch.float32, "frames"), _stream(pts.device)), "se3_pca_frames_padded")
+        return frames
     _lib.check(lib.se3_pca_frames(_ptr(pts, torch.float32, "pts"), _ptr(ids, torch.int32, "knn", pts.device), n, k, axis,
                                   _ptr(frames, torch.float32, "frames"), _stream(pts.device)), "se3_pca_frames")
     return frames

@@ -65,6 +65,19 @@ def _repeat_rows(t, times):
     return t[:, None].expand(-1, int(times)).reshape(-1)
 
 
+def is_padded(cloud) -> bool:
+    """Whether ``cloud`` is a padded cloud: buffers of which only the first ``n_valid_`` rows (a device word) exist."""
+    return getattr(cloud, "n_valid_", None) is not None
+
+
+def refuse_padded(cloud, what: str) -> None:
+    """The loud end of what padded clouds do not support yet (limits table)."""
+    if is_padded(cloud):
+        raise NotImplementedError(f"{what} on a padded cloud (p_n_valid) is not implemented: it reads every row of the "
+                                  "buffers, and the present-row count is a device word -- build the hierarchy with "
+                                  "p_padded=False for it")
+
+
 def _batches_of(cloud):
     """The batch count a grid sub-sample of ``cloud`` has: its own (every batch element that holds a point keeps a cell, so
     the largest id survives); None for foreign cloud objects."""
@@ -72,14 +85,37 @@ def _batches_of(cloud):
 
 
 class Pointcloud(object):
+    """``p_n_valid`` (extension, keyword): a PADDED cloud -- ``p_pts`` / ``p_batch_ids`` are buffers of which only the rows
+    ``[0, p_n_valid)`` exist, ``p_n_valid`` being a 1-element int32 device tensor (``n_valid_``; None for an ordinary
+    cloud).  Boxes, self-k-NN, PCA frames and ball-query neighbourhoods of such a cloud never read the other rows and never
+    read the count back (include/se3conv_padded.h), so they capture into a HIP graph that follows the word.  The buffers
+    are taken as they are (float32 / int32, contiguous) and ``num_batches`` is required.
+
+    What the cloud caches -- boxes, the k-NN table, shared source grids -- is keyed on the word's storage and version counter.
+    A graph replay rewrites the words, points and batch ids of the clouds a captured build made without moving a version:
+    such held clouds are for reading (``pts_``, ``n_valid_``, ``local_frames_``, the neighbourhoods built in the capture), not
+    for further eager queries, which could meet a box, table or grid of the replay before.  Query a fresh ``Pointcloud`` over
+    the same buffers instead (or call ``ops.forget_source_grids(cloud)`` and drop ``_se3_aabb`` / ``_se3_knn_ids``)."""
+
     def __init__(self, p_pts, p_batch_ids, **kwargs):
         self.pts_with_grads_ = bool(kwargs.pop("requires_grad", False))
+        self.n_valid_ = kwargs.pop("p_n_valid", None)
         # num_batches (extension): the batch count when the caller knows it (a hierarchy level has its parent's) -- spares
         # the read-back of batch_size_ the native calls' table sizes would otherwise cost once per cloud
         known_batches = kwargs.pop("num_batches", None)
         self.pts_ = torch.as_tensor(p_pts, **kwargs)
         self.batch_ids_ = torch.as_tensor(p_batch_ids, **kwargs)
-        self.batch_size_ = torch.max(self.batch_ids_) + 1
+        if self.n_valid_ is not None:
+            if known_batches is None:
+                raise ValueError("a padded cloud (p_n_valid) needs num_batches: the batch ids of absent rows say nothing, and "
+                                 "reading the largest present one would be a read-back")
+            w = self.n_valid_
+            if not isinstance(w, torch.Tensor) or w.dtype != torch.int32 or w.numel() != 1 or w.device != self.pts_.device:
+                raise ValueError("p_n_valid is a 1-element int32 tensor on the device of the points")
+            ops._padded_cloud(self.pts_, self.batch_ids_, "Pointcloud")
+            self.batch_size_ = torch.tensor(int(known_batches))  # (on the host: absent rows' ids are not looked at)
+        else:
+            self.batch_size_ = torch.max(self.batch_ids_) + 1
         if known_batches is not None:
             self._num_batches = int(known_batches)
         if self.pts_with_grads_:
@@ -89,6 +125,8 @@ class Pointcloud(object):
         self.pts_ = self.pts_.to(p_device)
         self.batch_ids_ = self.batch_ids_.to(p_device)
         self.batch_size_ = self.batch_size_.to(p_device)
+        if self.n_valid_ is not None:
+            self.n_valid_ = self.n_valid_.to(p_device)
 
     @staticmethod
     def _pool_rows_by(ids, p_in_tensor, p_pooling_method, n_out):
@@ -99,10 +137,12 @@ class Pointcloud(object):
 
     def global_pooling(self, p_in_tensor, p_pooling_method="avg"):
         """One row per batch element (pc/Pointcloud.py:58-76; classification heads -- [B, C] outputs, plain torch)."""
+        refuse_padded(self, "global_pooling")
         return self._pool_rows_by(self.batch_ids_, p_in_tensor, p_pooling_method, self.num_batches())
 
     def global_upsample(self, p_in_tensor):
         """pc/Pointcloud.py:79-88."""
+        refuse_padded(self, "global_upsample")
         return torch.index_select(p_in_tensor, 0, self.batch_ids_.to(torch.int64))
 
     def num_batches(self) -> int:
@@ -118,8 +158,19 @@ class Pointcloud(object):
         box = getattr(self, "_se3_aabb", None)
         # (points or batch ids replaced or changed in place: new boxes)
         key = (self.pts_.data_ptr(), self.pts_._version, self.batch_ids_.data_ptr(), self.batch_ids_._version)
+        if self.n_valid_ is not None:
+            # a padded cloud: the boxes of the present rows -- recomputed when the count word changes, and inside a graph
+            # capture once per capture (a replay must follow the word; boxes from an earlier node of the same graph do)
+            key += (self.n_valid_.data_ptr(), self.n_valid_._version)
+            if torch.cuda.is_current_stream_capturing():
+                key += (ops._capture_id(self.pts_.device),)
+                held = getattr(self, "_se3_aabb_captured", None)
+                if held is None or held[2] != key:
+                    mn, mx = ops.batch_aabb(self.pts_, self.batch_ids_, self.num_batches(), n_valid=self.n_valid_)
+                    held = self._se3_aabb_captured = (mn, mx, key)
+                return held[0], held[1]
         if box is None or box[2] != key:
-            mn, mx = ops.batch_aabb(self.pts_, self.batch_ids_, self.num_batches())
+            mn, mx = ops.batch_aabb(self.pts_, self.batch_ids_, self.num_batches(), n_valid=self.n_valid_)
             box = (mn, mx, key)
             self._se3_aabb = box
         return box[0], box[1]
@@ -131,6 +182,7 @@ class PointcloudRotEquiv(Pointcloud):
     def __init__(self, p_pts, p_batch_ids, p_ref_frames_config, ref_frames_pts=None, standard_knn=False, **kwargs):
         super().__init__(p_pts, p_batch_ids, **kwargs)
         kwargs.pop("num_batches", None)  # (consumed by Pointcloud.__init__; the rest are torch.as_tensor keywords)
+        kwargs.pop("p_n_valid", None)
         self.neigh_cache_ = {}
         self.local_frames_pca_cache_ = {}
         self.local_frames_config_ = p_ref_frames_config
@@ -159,6 +211,7 @@ class PointcloudRotEquiv(Pointcloud):
         if not hasattr(self, "neigh_cache_"):
             self.neigh_cache_, self.local_frames_pca_cache_ = {}, {}
         if self.ref_frames_pts is not None:
+            refuse_padded(self, "frames from ref_frames_pts")
             # PointcloudRotEquiv.py:80-128: a cloud with ONE point per batch element (classification heads) takes its
             # frames from the whole element's points, `ref_frames_pts [(B m), 3]`: the PCA of all m points
             # (sample_global_reference_frames_pca, RotationFunctions.py:265-304) or plain random frames
@@ -185,8 +238,10 @@ class PointcloudRotEquiv(Pointcloud):
                     # list and offsets: seven more launches) is built from the same table when somebody asks for it
                     # (get_ref_frame_neighborhood)
                     ids = self._self_knn_ids(cfg["neigh_kwargs"]["neigh_k"])
-                    self.local_frames_pca_cache_["se3-all"] = ops.pca_frames(self.pts_, ids, cfg.get("fixed_axis"))
+                    self.local_frames_pca_cache_["se3-all"] = ops.pca_frames(self.pts_, ids, cfg.get("fixed_axis"),
+                                                                             n_valid=self.n_valid_)
                 else:
+                    refuse_padded(self, "PCA frames from a ball-query neighbourhood")
                     nbh = self.get_ref_frame_neighborhood(cfg["neigh_method"], **cfg["neigh_kwargs"])
                     self.local_frames_pca_cache_["se3-all"] = sample_reference_frames_pca(
                         self.pts_, nbh, axis_fixed=cfg.get("fixed_axis"), device=self.pts_.device)
@@ -209,11 +264,14 @@ class PointcloudRotEquiv(Pointcloud):
         its lists from.  Not while a HIP graph is being captured: a table cached before would be baked into the graph, one
         cached during the capture holds nothing until the first replay."""
         grid = self.pts_.shape[0] >= ops.KNN_GRID_MIN_POINTS and k <= 32
-        query = lambda: ops.knn_query(self.pts_, self.batch_ids_, int(k), self.num_batches(), box=self.aabb() if grid else None)
+        query = lambda: ops.knn_query(self.pts_, self.batch_ids_, int(k), self.num_batches(), box=self.aabb() if grid else None,
+                                      n_valid=self.n_valid_)
         if self.pts_.is_cuda and torch.cuda.is_current_stream_capturing():
             return query()
         cache = self.__dict__.setdefault("_se3_knn_ids", {})
         key = (int(k), self.pts_.data_ptr(), self.pts_._version)
+        if self.n_valid_ is not None:
+            key += (self.n_valid_.data_ptr(), self.n_valid_._version)
         if key not in cache:
             cache.clear()
             cache[key] = query()
@@ -239,14 +297,17 @@ class PointcloudRotEquiv(Pointcloud):
 
     def global_pooling(self, p_in_tensor, p_pooling_method="avg"):
         """Rows are per (point, frame) here (pc/PointcloudRotEquiv.py:252-270)."""
+        refuse_padded(self, "global_pooling")
         return self._pool_rows_by(self.batch_ids_considering_frames_, p_in_tensor, p_pooling_method, self.num_batches())
 
     def global_upsample(self, p_in_tensor):
+        refuse_padded(self, "global_upsample")
         return torch.index_select(p_in_tensor, 0, self.batch_ids_considering_frames_.to(torch.int64))
 
     def global_pooling_specific_feature_pooling(self, p_in_tensor, p_global_pooling_method="avg",
                                                 p_feature_pooling_method="avg"):
         """Frames first, then batch elements (pc/PointcloudRotEquiv.py:195-222)."""
+        refuse_padded(self, "global_pooling_specific_feature_pooling")
         pooled = self.feature_pooling(p_in_tensor, p_pooling_method=p_feature_pooling_method)
         return self._pool_rows_by(self.batch_ids_, pooled, p_global_pooling_method, self.num_batches())
 
@@ -255,6 +316,7 @@ class PointcloudRotEquiv(Pointcloud):
         forward and one backward."""
         if p_pooling_method not in ops.POOL_MODES:
             raise ValueError(p_pooling_method)
+        refuse_padded(self, "feature_pooling")
         # Launched eagerly, a custom autograd.Function costs more in Python than this pass costs on the GPU (fwd + bwd
         # 0.099 ms through the library against 0.057 ms of stock torch ops at 65 k points, profiles/r03_next_rows.txt): outside
         # a graph capture the reduction over the frame axis is torch's own (max / min route their gradient to the winning
@@ -301,7 +363,11 @@ class BQNeighborhood(Neighborhood):
     generator); ``p_seed_tensor`` is a 1-element int32 device tensor added to it on the device (a captured build draws fresh
     subsets when it is updated).  A capped list is not symmetric, also for a cloud against itself, and a second query
     with the roles swapped would draw another subset: ``symmetric_`` is False, ``source_major()`` is None, and backward
-    reads the library's transposition of this very list."""
+    reads the library's transposition of this very list.
+
+    Padded clouds (``Pointcloud(..., p_n_valid=)``, either side): the query is ``ops.ball_query_padded`` -- absent rows are
+    never read, absent sources never listed, absent samples have no edges -- and so is ``source_major()``'s second query.
+    ``p_capacity`` is then required (``ValueError``), and ``p_max_neighbors > 0`` is not implemented."""
 
     def __init__(self, p_pc_src, p_samples, p_radius, p_max_neighbors=0, p_capacity=None, p_seed=None, p_seed_tensor=None):
         self.radius_ = p_radius
@@ -316,6 +382,13 @@ class BQNeighborhood(Neighborhood):
         # a cloud against itself: (s, p) is an edge iff (p, s) is -- the operator's backward then needs no
         # source-major copy of the edge list (ops.ConvGeometry.transpose)
         self.symmetric_ = p_pc_src is p_samples and p_max_neighbors <= 0
+        self.padded_ = is_padded(p_pc_src) or is_padded(p_samples)
+        if self.padded_ and p_max_neighbors > 0:
+            raise NotImplementedError("BQNeighborhood: p_max_neighbors > 0 on padded clouds (p_n_valid) is not implemented: "
+                                      "the capped query has no row-count words")
+        if self.padded_ and p_capacity is None:
+            raise ValueError("BQNeighborhood: padded clouds (p_n_valid) need p_capacity -- the edge count of a padded query "
+                             "is never read back to size the list")
         super().__init__(p_pc_src, p_samples)
 
     def __compute_neighborhood__(self):
@@ -325,7 +398,16 @@ class BQNeighborhood(Neighborhood):
         self.sources_i32_ = None
         # the source cloud's boxes: computed once per cloud (Pointcloud.aabb), not once per query
         src_box = self.pc_src_.aabb() if hasattr(self.pc_src_, "aabb") and ops.ball_query_needs_grid(self.pc_src_.pts_.shape[0]) else None
-        if self.max_neighbors_ > 0:
+        if self.padded_:
+            res = ops.ball_query_padded(self.pc_src_.pts_, self.samples_.pts_, self.pc_src_.batch_ids_,
+                                        self.samples_.batch_ids_, self.radius_, int(self.capacity_), self.pc_src_.num_batches(),
+                                        n_valid_src=getattr(self.pc_src_, "n_valid_", None),
+                                        n_valid_dst=getattr(self.samples_, "n_valid_", None), want_sources=self.symmetric_,
+                                        src_box=src_box, grids=ops.source_grids(self.pc_src_))
+            nb, self.start_ids_, self.edge_info_ = res[:3]
+            if self.symmetric_:
+                self.sources_i32_ = res[3]
+        elif self.max_neighbors_ > 0:
             res = ops.ball_query_capped(self.pc_src_.pts_, self.samples_.pts_, self.pc_src_.batch_ids_,
                                         self.samples_.batch_ids_, self.radius_, int(self.max_neighbors_), self.seed_,
                                         capacity=None if self.capacity_ is None else int(self.capacity_),
@@ -386,9 +468,16 @@ class BQNeighborhood(Neighborhood):
         cached = getattr(self, "_source_major", None)
         if cached is None:
             box = self.samples_.aabb() if hasattr(self.samples_, "aabb") and ops.ball_query_needs_grid(n_smp) else None
-            _, t_ends, info, t_samples = ops.ball_query_bounded(
-                self.samples_.pts_, self.pc_src_.pts_, self.samples_.batch_ids_, self.pc_src_.batch_ids_, self.radius_, rows,
-                self.samples_.num_batches(), want_sources=True, src_box=box, grids=ops.source_grids(self.samples_))
+            if getattr(self, "padded_", False):
+                _, t_ends, info, t_samples = ops.ball_query_padded(
+                    self.samples_.pts_, self.pc_src_.pts_, self.samples_.batch_ids_, self.pc_src_.batch_ids_, self.radius_, rows,
+                    self.samples_.num_batches(), n_valid_src=getattr(self.samples_, "n_valid_", None),
+                    n_valid_dst=getattr(self.pc_src_, "n_valid_", None), want_sources=True, src_box=box,
+                    grids=ops.source_grids(self.samples_))
+            else:
+                _, t_ends, info, t_samples = ops.ball_query_bounded(
+                    self.samples_.pts_, self.pc_src_.pts_, self.samples_.batch_ids_, self.pc_src_.batch_ids_, self.radius_, rows,
+                    self.samples_.num_batches(), want_sources=True, src_box=box, grids=ops.source_grids(self.samples_))
             cached = self._source_major = (t_samples, t_ends, info)
         return cached[0], cached[1]
 
@@ -423,6 +512,11 @@ class KnnNeighborhood(Neighborhood):
             raise NotImplementedError(f"KnnNeighborhood: k = {p_k}; the HIP k-NN keeps at most {self.MAX_K} neighbours "
                                       "per point (the limit of the reference's own kernel; its torch_cluster fallback "
                                       "for larger k is not implemented)")
+        if is_padded(p_pc_src) or is_padded(p_samples):
+            raise NotImplementedError("KnnNeighborhood between padded clouds (p_n_valid) is not implemented, a padded cloud "
+                                      "against itself included: the pair query has no row-count words and the list without "
+                                      "empty slots is sized by a read-back (PCA frames take the id table of "
+                                      "ops.knn_query(..., n_valid=) directly)")
         self.k_ = int(p_k)
         self.keep_empty_ = p_keep_empty
         self.standard_knn_ = p_standard_knn
@@ -540,18 +634,70 @@ def _make_sub_sample(p_point_cloud, p_samp_method, p_id, **kwargs):
     raise ValueError(f"unknown sub-sample method {p_samp_method!r} (grid_avg, grid_rnd)")
 
 
+class PaddedSubSample(object):
+    """The sub-sampling step between two PADDED levels (``PointHierarchy(..., p_padded=True)``): the tensors of
+    ``struct se3_level`` as ``ops.grid_levels_bounded`` wrote them (``level_`` -- ``cell_ids``, ``sorted_ids``,
+    ``cell_ends``, ``pts``, ``batch_ids`` and on random levels ``u``, ``ids``, ``picked``), every one of capacity size, and
+    the level's size and overflow flag on the device (``info_ [2]``).  Pooling and up-sampling feature rows through it is
+    not implemented."""
+
+    def __init__(self, p_pc_src, p_cell_size, p_level, p_info, p_rnd_sample=False):
+        self.pc_src_, self.cell_size_, self.level_, self.info_ = p_pc_src, p_cell_size, p_level, p_info
+        self.rnd_sample_ = bool(p_rnd_sample)
+        self.cell_ids_, self.sorted_ids_ = p_level["cell_ids"], p_level["sorted_ids"]
+        self.capacity_ = int(p_level["pts"].shape[0])
+
+    def __subsample_tensor__(self, p_tensor, p_method="avg"):
+        raise NotImplementedError("pool_tensor on padded levels (p_padded=True) is not implemented: the pooled rows would "
+                                  "need the level's present-row count, which is a device word")
+
+    def __upsample_tensor__(self, p_tensor):
+        raise NotImplementedError("upsample_tensor on padded levels (p_padded=True) is not implemented: the absent rows' "
+                                  "cell ids are -1")
+
+
 class PointHierarchy(object):
     """``p_capacities`` (extension): None builds level after level, each with its own read-back of the level size.
     ``"input"`` or one row count per level builds ALL levels with one library call into buffers of those sizes
     (``ops.grid_levels_bounded``; ``"input"``: the row count of level 0, which cannot overflow) and reads every level size
     back with one copy; the clouds and sub-sample objects are the same, bit for bit.  ``ops.LevelOverflow`` when a level
-    does not fit.  Neighbourhoods and frames are built on the trimmed levels either way."""
+    does not fit.  Neighbourhoods and frames are then built on the trimmed levels (on the padded ones: ``p_padded``).
 
-    def __init__(self, p_point_cloud, p_num_sub_samples, p_subsample_method="grid_avg", p_capacities=None, **kwargs):
+    ``p_padded=True`` (extension, needs ``p_capacities``): nothing is trimmed and nothing is read back.  Every level cloud is
+    the capacity-sized buffer of its level as a PADDED cloud (``Pointcloud(..., p_n_valid=)``) whose ``n_valid_`` word holds
+    ``min(level size, capacity)``; frames and ball-query neighbourhoods of the levels never read the absent rows
+    (include/se3conv_padded.h), so that hierarchy, frames, neighbourhoods and convolutions capture into one HIP graph that
+    can be replayed on a batch with another point count.  Level 0 may be a padded cloud itself.  ``level_sizes()`` and
+    ``overflowed()`` are the read-backs, done only when asked.  ``pool_tensor`` / ``upsample_tensor`` are not implemented
+    on padded levels."""
+
+    def __init__(self, p_point_cloud, p_num_sub_samples, p_subsample_method="grid_avg", p_capacities=None, p_padded=False,
+                 **kwargs):
         self.sub_sampled_objs_ = []
         self.pcs_ = [p_point_cloud]
+        self.padded_ = bool(p_padded)
+        self.level_info_ = None
         cur = p_point_cloud
-        if p_capacities is None:
+        if self.padded_:
+            if p_capacities is None:
+                raise ValueError("PointHierarchy: p_padded=True needs p_capacities ('input' or one row count per level)")
+            if p_subsample_method not in ("grid_avg", "grid_rnd"):
+                _make_sub_sample(p_point_cloud, p_subsample_method, 0, **kwargs)  # (raises: the methods' one error text)
+            if p_num_sub_samples > 0:
+                rnd = p_subsample_method == "grid_rnd"
+                radii = [kwargs["grid_radii"][i] for i in range(p_num_sub_samples)]
+                built = ops.grid_levels_bounded(cur.pts_, cur.batch_ids_, radii, p_capacities, cur.num_batches(),
+                                                n_valid=getattr(cur, "n_valid_", None), rnd=[rnd] * p_num_sub_samples)
+                self.level_info_ = built.info
+                self._levels_keep = built
+                for i, lv in enumerate(built.levels):
+                    # the level's row-count word: min(true cell count, capacity), formed on the device
+                    word = torch.clamp(built.info[i, 0:1], max=int(built.capacities[i]))
+                    samp = PaddedSubSample(cur, radii[i], lv, built.info[i], rnd)
+                    cur = self.__padded_level_cloud__(cur, lv["pts"], lv["batch_ids"], word)
+                    self.sub_sampled_objs_.append(samp)
+                    self.pcs_.append(cur)
+        elif p_capacities is None:
             for i in range(p_num_sub_samples):
                 new_pc, samp = self.__create_sub_sample__(cur, p_subsample_method, i, **kwargs)
                 self.sub_sampled_objs_.append(samp)
@@ -580,6 +726,27 @@ class PointHierarchy(object):
         new_bid = p_samp.__subsample_tensor__(p_point_cloud.batch_ids_, "max")
         return Pointcloud(new_pts, new_bid, num_batches=_batches_of(p_point_cloud))
 
+    def __padded_level_cloud__(self, p_point_cloud, p_pts, p_batch_ids, p_word):
+        return Pointcloud(p_pts, p_batch_ids, p_n_valid=p_word, num_batches=_batches_of(p_point_cloud))
+
+    def level_sizes(self):
+        """Present rows of every level as host integers (level 0 included): the read-back of a padded hierarchy, done
+        only when asked.  An ordinary hierarchy answers from its shapes."""
+        if not self.padded_:
+            return [int(pc.pts_.shape[0]) for pc in self.pcs_]
+        words = [pc.n_valid_.reshape(1) if is_padded(pc) else None for pc in self.pcs_]
+        vals = torch.cat([w for w in words if w is not None]).cpu().tolist() if any(w is not None for w in words) else []
+        out = []
+        for pc, w in zip(self.pcs_, words):
+            n = int(pc.pts_.shape[0])
+            out.append(n if w is None else min(max(int(vals.pop(0)), 0), n))
+        return out
+
+    def overflowed(self) -> bool:
+        """Whether a level of a padded hierarchy had more cells than its capacity (one read-back; the level and every
+        deeper one are then those of the truncated hierarchy: build again with larger capacities)."""
+        return self.level_info_ is not None and bool((self.level_info_[:, 1] != 0).any())
+
     def create_neighborhood(self, p_pc_src_id, p_pc_dest_id, p_neigh_method, **kwargs):
         """Memoised per (source level, destination level, method + its parameter), pc/PointHierarchy.py:60-79 (the k-NN
         keyword is spelled ``neihg_k`` there; ``neigh_k`` is accepted too).  ``bq_max_neighbors`` (> 0) and ``bq_seed`` cap a ball-query
@@ -592,11 +759,14 @@ class PointHierarchy(object):
         else:
             raise ValueError(f"unknown neighbourhood method {p_neigh_method!r} (ball_query, knn)")
         key = f"{p_pc_src_id}_{p_pc_dest_id}_{p_neigh_method}{param}"
+        capacity = kwargs.get("bq_capacity") if p_neigh_method == "ball_query" else None
+        if capacity is not None:  # (extension: a capacity-bounded list, BQNeighborhood(p_capacity=); padded levels need it)
+            key += f"_cap{int(capacity)}"
         if cap > 0:  # (a capped neighbourhood is another list, and so is one drawn with another seed)
             key += f"_max{cap}_seed{kwargs.get('bq_seed')}"
         if key not in self.neigh_cache_:
             src, dst = self.pcs_[p_pc_src_id], self.pcs_[p_pc_dest_id]
-            self.neigh_cache_[key] = BQNeighborhood(src, dst, param, cap, p_seed=kwargs.get("bq_seed")) \
+            self.neigh_cache_[key] = BQNeighborhood(src, dst, param, cap, p_capacity=capacity, p_seed=kwargs.get("bq_seed")) \
                 if p_neigh_method == "ball_query" else KnnNeighborhood(src, dst, param)
         return self.neigh_cache_[key]
 
@@ -619,4 +789,8 @@ class PointHierarchyRotEquiv(PointHierarchy):
         new_pts = p_samp.__subsample_tensor__(p_point_cloud.pts_, "avg")
         new_bid = p_samp.__subsample_tensor__(p_point_cloud.batch_ids_, "max")
         return PointcloudRotEquiv(new_pts, new_bid, p_point_cloud.local_frames_config_,
+                                  num_batches=_batches_of(p_point_cloud))
+
+    def __padded_level_cloud__(self, p_point_cloud, p_pts, p_batch_ids, p_word):
+        return PointcloudRotEquiv(p_pts, p_batch_ids, p_point_cloud.local_frames_config_, p_n_valid=p_word,
                                   num_batches=_batches_of(p_point_cloud))

@@ -151,6 +151,22 @@ PADDED_SIGNATURES = {
     "se3_pca_frames_padded": (C.c_int, [_P, _P, _I64, _P, _I32, _I32, _P, _P]),
 }
 
+# the row-wise passes of a network on padded clouds -- feature tensors padded like the points, the present-row count a device
+# word -- declared in include/se3conv_padded_rows.h (additions inside ABI version 6 as well); must list every symbol that
+# header declares
+PADDED_ROWS_SIGNATURES = {
+    "se3_bn_fwd_padded": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _I32, _F, _F, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "se3_bn_bwd_padded": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "se3_skip_fwd_padded": (C.c_int, [_P, _P, _P, _P, _F, _P, _I64, _I32, _P, _I32, _P, _P]),
+    "se3_skip_bwd_padded": (C.c_int, [_P, _P, _P, _P, _F, _P, _I64, _I32, _P, _I32, _P, _P, _P, _SZ, _P]),
+    "se3_channel_sums_padded": (C.c_int, [_P, _I64, _I32, _P, _I32, _P, _P, _SZ, _P]),
+    "se3_frame_pool_padded": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _P, _P, _P]),
+    "se3_frame_unpool_padded": (C.c_int, [_P, _P, _I64, _I32, _P, _I32, _I32, _P, _P]),
+    "se3_segment_unpool_padded": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _P, _P]),
+    "se3_rows_gather_padded": (C.c_int, [_P, _P, _I64, _I64, _P, _P]),
+    "se3_rows_unpick_padded": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P]),
+}
+
 _lib = None
 
 
@@ -169,7 +185,7 @@ def load() -> C.CDLL:
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
     for name, (res, args) in (list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items()) + list(FORMS_SIGNATURES.items())
-                                   + list(PADDED_SIGNATURES.items())):
+                                   + list(PADDED_SIGNATURES.items()) + list(PADDED_ROWS_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so

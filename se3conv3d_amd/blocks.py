@@ -11,6 +11,17 @@ profiles/r03_block_glue_timing.txt); the forward and input-gradient C x C produc
   SkipConnection  layers/SkipConnection.py        drop_path(x * gamma_) + y, gamma_ initialised to 1e-6
   BatchNormPC     layers/BatchNormPC.py:22-32     BatchNorm1d(momentum=0.2) on the feature rows (the cloud is unused)
   ResNetFormer    layers/ResNetFormer.py:33-88    norm -> conv -> skip; norm -> linear (x2) -> GELU -> linear -> skip
+
+Padded clouds.  A cloud built with ``p_n_valid`` alone is refused by every module here.  One built with
+``p_padded_rows=True`` (pc.py) has feature tensors padded like its points, and the modules run the library's padded passes
+(include/se3conv_padded_rows.h; ops.BatchNormTrainPadded / SkipDropPathPadded): statistics, ``1/N`` and channel sums over the
+present rows alone -- bit for bit those of the trimmed tensors --, no absent row read (an absent row's batch id never
+indexes the drop-path gate), zeros written at the absent rows.  The invariant a network gets: every library pass leaves
+zeros at absent rows, the stock torch ops in between (Linear, GELU) are row-wise and keep them finite; the caller's part is
+finite level-0 input features and a loss that ignores absent rows (``pc.present_mask``), so that the gradient arriving
+there is zero.  There is no torch fallback on such a cloud: a configuration that would need one (non-fp32 input,
+``FUSED = False``, ``drop_prob >= 1``, training without running statistics) raises ``NotImplementedError``; eval-mode batch
+norm stays the row-wise torch path.
 """
 import os
 
@@ -18,7 +29,7 @@ import torch
 
 from . import ops
 from .layers import PreProcessModule
-from .pc import refuse_padded
+from .pc import padded_rows, refuse_unflagged
 
 FUSED = os.environ.get("SE3_BLOCKS_FUSED", "1") != "0"
 
@@ -33,16 +44,44 @@ def _fused(t: torch.Tensor) -> bool:
     return FUSED and t.is_cuda and t.dim() == 2 and t.dtype == torch.float32
 
 
+def _need_fused_on_padded_rows(who: str, t: torch.Tensor, ok: bool = True, limit: str = "") -> None:
+    """The loud end of a flagged padded cloud (``p_padded_rows``): the torch formulations read every row of the buffers."""
+    if not _fused(t):
+        raise NotImplementedError(f"{who} on padded feature rows (p_padded_rows) runs the library's kernels only: [rows, C] "
+                                  "float32 GPU tensors with blocks.FUSED on -- the torch formulation would read absent rows")
+    if not ok:
+        raise NotImplementedError(f"{who} on padded feature rows (p_padded_rows): {limit} is not implemented -- it would need "
+                                  "the torch formulation, which reads absent rows")
+
+
+def _row_layout(p_x, p_pc):
+    """``(frames, row batch ids)`` of a feature tensor on a padded cloud: one row per (point, frame) or one per point."""
+    n = int(p_pc.pts_.shape[0])
+    f = int(getattr(p_pc, "n_frames_", 1))
+    if p_x.shape[0] == n * f and f > 1:
+        return f, p_pc.batch_ids_considering_frames_
+    if p_x.shape[0] == n:
+        return 1, p_pc.batch_ids_
+    raise ValueError(f"{p_x.shape[0]} feature rows on a padded cloud of {n} rows with {f} frame(s)")
+
+
 class DropPathPC(torch.nn.Module):
     def __init__(self, p_drop_prob):
         super().__init__()
         self.drop_prob_ = p_drop_prob
 
     def forward(self, p_x, p_pc):
-        refuse_padded(p_pc, "DropPathPC")
+        refuse_unflagged(p_pc, "DropPathPC")
         if self.drop_prob_ == 0.0 or not self.training:
             return p_x
         keep = 1.0 - self.drop_prob_
+        if padded_rows(p_pc):
+            # through the skip kernel's gate path (x * 1 * gate + 0): an absent row's batch id never indexes the gate
+            _need_fused_on_padded_rows("DropPathPC", p_x, self.drop_prob_ < 1.0, "drop_prob >= 1")
+            frames, ids = _row_layout(p_x, p_pc)
+            gate = torch.rand((_num_batches(p_pc),), dtype=p_x.dtype, device=p_x.device)
+            one = torch.ones((1, p_x.shape[1]), dtype=p_x.dtype, device=p_x.device)
+            return ops.SkipDropPathPadded.apply(p_x, torch.zeros_like(p_x), one, gate, ids, keep, p_pc.n_valid_, frames)
         # one uniform draw per batch element, keep where keep + u >= 1; rows of a cloud with frames carry the batch id
         # of their point (batch_ids_considering_frames_)
         gate = torch.floor(keep + torch.rand((_num_batches(p_pc),), dtype=p_x.dtype, device=p_x.device))
@@ -59,7 +98,20 @@ class SkipConnection(torch.nn.Module):
         self.gamma_ = torch.nn.Parameter(torch.full((1, p_num_features), float(p_init_gamma)))
 
     def forward(self, p_x, p_y, p_pc):
-        refuse_padded(p_pc, "SkipConnection")
+        refuse_unflagged(p_pc, "SkipConnection")
+        if padded_rows(p_pc):
+            _need_fused_on_padded_rows("SkipConnection", p_x, not (self.training and self.drop_path_.drop_prob_ >= 1.0),
+                                       "drop_prob >= 1")
+            if p_x.shape != p_y.shape:
+                raise NotImplementedError("SkipConnection on padded feature rows (p_padded_rows): x and y of different shapes "
+                                          "would need the torch formulation, which reads absent rows")
+            frames, ids = _row_layout(p_x, p_pc)
+            gate, keep = None, 0.0
+            if self.drop_path_.drop_prob_ != 0.0 and self.training:
+                keep = 1.0 - self.drop_path_.drop_prob_
+                gate = torch.rand((_num_batches(p_pc),), dtype=p_x.dtype, device=p_x.device)
+            return ops.SkipDropPathPadded.apply(p_x, p_y, self.gamma_, gate, ids if gate is not None else None, keep,
+                                                p_pc.n_valid_, frames)
         # drop_prob >= 1 (keep <= 0): the reference divides by zero (DropPathPC.py:45) -- the plain formulation reproduces
         # that instead of handing the kernel keep = 0, which it reads as "the gate is the factor itself"
         if not _fused(p_x) or p_x.shape != p_y.shape or (self.training and self.drop_path_.drop_prob_ >= 1.0):
@@ -88,8 +140,14 @@ class BatchNormPC(NormLayerPC):
         self.layer_ = torch.nn.BatchNorm1d(p_num_features, momentum=0.2)
 
     def forward(self, p_x, p_pc):
-        refuse_padded(p_pc, "BatchNormPC (its statistics need the present-row count)")
+        refuse_unflagged(p_pc, "BatchNormPC (its statistics need the present-row count)")
         bn = self.layer_
+        if padded_rows(p_pc) and (bn.training or not bn.track_running_stats):  # (batch statistics; eval mode is row-wise)
+            _need_fused_on_padded_rows("BatchNormPC", p_x, bn.training and bn.track_running_stats and bn.momentum is not None,
+                                       "training without running statistics (or with momentum None)")
+            frames, _ = _row_layout(p_x, p_pc)
+            return ops.BatchNormTrainPadded.apply(p_x, p_pc.n_valid_, frames, bn.weight, bn.bias, bn.running_mean,
+                                                  bn.running_var, bn.momentum, bn.eps, bn.num_batches_tracked)
         if not (_fused(p_x) and bn.training and bn.track_running_stats and bn.momentum is not None):
             return bn(p_x)
         return ops.BatchNormTrain.apply(p_x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
@@ -123,7 +181,22 @@ class ResNetFormer(Block):
             self.skip_conv_ = torch.nn.Linear(c_in, c_out)
 
     def forward(self, p_pc_in, p_in_features, p_neighborhood):
-        refuse_padded(p_pc_in, "ResNetFormer")
+        refuse_unflagged(p_pc_in, "ResNetFormer")
+        if padded_rows(p_pc_in):
+            _need_fused_on_padded_rows("ResNetFormer", p_in_features)
+            frames, _ = _row_layout(p_in_features, p_pc_in)
+            word = p_pc_in.n_valid_
+            # the linear layers with their bias gradients summed by the library over the present rows (ops.LinearPadded: no
+            # memset node in a captured step)
+            x = self.spatial_conv_(p_pc_in=p_pc_in, p_pc_out=p_pc_in, p_in_features=self.norm_1_(p_in_features, p_pc_in),
+                                   p_neighborhood=p_neighborhood)
+            x = self.skip_path_1_(x, p_in_features, p_pc_in)
+            h = ops.BiasGelu.apply(ops.Linear.apply(self.norm_2_(x, p_pc_in), self.linear_1_.weight, None), self.linear_1_.bias)
+            y = ops.LinearPadded.apply(h, self.linear_2_.weight, self.linear_2_.bias, word, frames)
+            skip = x
+            if self.feat_input_size_ != self.feat_output_size_:
+                skip = ops.LinearPadded.apply(x, self.skip_conv_.weight, self.skip_conv_.bias, word, frames)
+            return self.skip_path_2_(y, skip, p_pc_in)
         x = self.spatial_conv_(p_pc_in=p_pc_in, p_pc_out=p_pc_in, p_in_features=self.norm_1_(p_in_features, p_pc_in),
                                p_neighborhood=p_neighborhood)
         x = self.skip_path_1_(x, p_in_features, p_pc_in)

@@ -27,7 +27,8 @@ HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "edge_bf16_body.h"
            os.path.join(os.path.dirname(PKG), "include", "se3conv_capped.h"),
            os.path.join(os.path.dirname(PKG), "include", "se3conv_levels.h"),
            os.path.join(os.path.dirname(PKG), "include", "se3conv_forms.h"),
-           os.path.join(os.path.dirname(PKG), "include", "se3conv_padded.h")]
+           os.path.join(os.path.dirname(PKG), "include", "se3conv_padded.h"),
+           os.path.join(os.path.dirname(PKG), "include", "se3conv_padded_rows.h")]
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP pass packs adjacent fp32 ops into v_pk_fma_f32 / v_pk_mul_f32, which issue slower than the
 # two scalar ops they replace on gfx950 (edge_t_fwd at the headline shape: 0.55 ms packed, 0.44 ms scalar) and need

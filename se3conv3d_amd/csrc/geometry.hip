@@ -16,6 +16,7 @@
 #include "../../include/se3conv_capped.h"
 #include "../../include/se3conv_levels.h"
 #include "../../include/se3conv_padded.h"
+#include "../../include/se3conv_padded_rows.h"
 
 namespace se3 {
 
@@ -1612,8 +1613,10 @@ __global__ void segment_pool_kernel(const float* __restrict__ src, const int32_t
 }
 
 // the maps from cells back to rows: MODE sum = plain gather (the up-sampling itself and the gradient of a sum),
-// avg = gather / cell size, max / min = the gradient goes to the row that supplied the extremum
-template <int MODE>
+// avg = gather / cell size, max / min = the gradient goes to the row that supplied the extremum.  PAD
+// (se3_segment_unpool_padded): a row whose cell id is negative -- an absent row or one of a dropped cell, as se3_grid_levels
+// writes them -- reads nothing and gets zeros.
+template <int MODE, bool PAD>
 __global__ void segment_unpool_kernel(const float* __restrict__ cell_vals, const int32_t* __restrict__ cell_ids,
                                       const int32_t* __restrict__ cell_ends, const int32_t* __restrict__ arg, int64_t n,
                                       int c, float* __restrict__ out) {
@@ -1621,6 +1624,10 @@ __global__ void segment_unpool_kernel(const float* __restrict__ cell_vals, const
     const int64_t row = idx / c;
     const int ch = (int)(idx - row * c);
     const int cell = cell_ids[row];
+    if (PAD && cell < 0) {
+      out[idx] = 0.f;
+      continue;
+    }
     float v = cell_vals[(int64_t)cell * c + ch];
     if (MODE == kPoolAvg) v = __fdiv_rn(v, (float)(cell_ends[cell] - (cell > 0 ? cell_ends[cell - 1] : 0)));
     if (MODE == kPoolMax || MODE == kPoolMin) v = arg[(int64_t)cell * c + ch] == (int32_t)row ? v : 0.f;
@@ -1638,13 +1645,25 @@ __global__ void cell_batch_ids_kernel(const int32_t* __restrict__ batch_ids, con
     out[cell] = cell < n_cells ? batch_ids[sorted_ids[cell > 0 ? cell_ends[cell - 1] : 0]] : -1;  // the batch id is part of the key
 }
 
-// Frame pooling (scope row f-3, pc/PointcloudRotEquiv.py:224-251): rows point*F + frame -> one row per point
+// Frame pooling (scope row f-3, pc/PointcloudRotEquiv.py:224-251): rows point*F + frame -> one row per point.
+// n_valid != nullptr (a padded cloud, se3conv_padded_rows.h): points from clamp(*n_valid, 0, n_pts) on are absent -- not
+// read, 0 in `out` / `grad_x` and -1 in `arg`.
+__device__ __forceinline__ int64_t present_points(int64_t n_pts, const int32_t* __restrict__ n_valid) {
+  return n_valid ? min(max((int64_t)*n_valid, (int64_t)0), n_pts) : n_pts;
+}
+
 template <int MODE>
 __global__ void frame_pool_kernel(const float* __restrict__ x, int64_t n_pts, int f, int c, float* __restrict__ out,
-                                  int32_t* __restrict__ arg) {
+                                  int32_t* __restrict__ arg, const int32_t* __restrict__ n_valid) {
+  const int64_t present = present_points(n_pts, n_valid);
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n_pts * c; idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t p = idx / c;
     const int ch = (int)(idx - p * c);
+    if (p >= present) {
+      out[idx] = 0.f;
+      if (arg) arg[idx] = -1;
+      continue;
+    }
     float acc = 0.f;
     int best = -1;
     for (int a = 0; a < f; ++a) {
@@ -1660,13 +1679,18 @@ __global__ void frame_pool_kernel(const float* __restrict__ x, int64_t n_pts, in
 
 template <int MODE>
 __global__ void frame_unpool_kernel(const float* __restrict__ g, const int32_t* __restrict__ arg, int64_t n_pts, int f,
-                                    int c, float* __restrict__ out) {
+                                    int c, float* __restrict__ out, const int32_t* __restrict__ n_valid) {
+  const int64_t present = present_points(n_pts, n_valid);
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n_pts * f * c;
        idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t row = idx / c;
     const int ch = (int)(idx - row * c);
     const int64_t p = row / f;
     const int a = (int)(row - p * f);
+    if (p >= present) {
+      out[idx] = 0.f;
+      continue;
+    }
     float v = g[p * c + ch];
     if (MODE == kPoolAvg) v = __fdiv_rn(v, (float)f);
     if (MODE == kPoolMax || MODE == kPoolMin) v = arg[p * c + ch] == a ? v : 0.f;
@@ -1776,17 +1800,24 @@ extern "C" int se3_segment_pool(const float* src, const int32_t* sorted_ids, con
   return check_launch();
 }
 
-extern "C" int se3_segment_unpool(const float* cell_vals, const int32_t* cell_ids, const int32_t* cell_ends,
-                                  const int32_t* arg, int64_t n, int32_t channels, int32_t mode, float* out,
-                                  void* stream_) {
+static int segment_unpool_impl(bool pad, const float* cell_vals, const int32_t* cell_ids, const int32_t* cell_ends,
+                               const int32_t* arg, int64_t n, int32_t channels, int32_t mode, float* out, void* stream_) {
   if (n < 0 || channels < 1 || mode < kPoolAvg || mode > kPoolSum) return SE3_ERR_INVALID_ARGUMENT;
+  if (pad && n >= (1ll << 31)) return SE3_ERR_UNSUPPORTED;
   if (n == 0) return SE3_OK;
   if (!cell_vals || !cell_ids || !out || (mode == kPoolAvg && !cell_ends)) return SE3_ERR_INVALID_ARGUMENT;
   if ((mode == kPoolMax || mode == kPoolMin) && !arg) return SE3_ERR_INVALID_ARGUMENT;
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid(blocks_for(n * channels)), block(256);
-#define SE3_UNPOOL(M) \
-  hipLaunchKernelGGL(segment_unpool_kernel<M>, grid, block, 0, stream, cell_vals, cell_ids, cell_ends, arg, n, channels, out)
+#define SE3_UNPOOL(M)                                                                                                    \
+  do {                                                                                                                   \
+    if (pad)                                                                                                             \
+      hipLaunchKernelGGL((segment_unpool_kernel<M, true>), grid, block, 0, stream, cell_vals, cell_ids, cell_ends, arg, n, \
+                         channels, out);                                                                                 \
+    else                                                                                                                 \
+      hipLaunchKernelGGL((segment_unpool_kernel<M, false>), grid, block, 0, stream, cell_vals, cell_ids, cell_ends, arg,  \
+                         n, channels, out);                                                                              \
+  } while (0)
   if (mode == kPoolAvg) SE3_UNPOOL(kPoolAvg);
   else if (mode == kPoolMax) SE3_UNPOOL(kPoolMax);
   else if (mode == kPoolMin) SE3_UNPOOL(kPoolMin);
@@ -1795,14 +1826,27 @@ extern "C" int se3_segment_unpool(const float* cell_vals, const int32_t* cell_id
   return check_launch();
 }
 
-extern "C" int se3_frame_pool(const float* x, int64_t n_points, int32_t frames, int32_t channels, int32_t mode, float* out,
-                              int32_t* arg, void* stream_) {
+extern "C" int se3_segment_unpool(const float* cell_vals, const int32_t* cell_ids, const int32_t* cell_ends,
+                                  const int32_t* arg, int64_t n, int32_t channels, int32_t mode, float* out,
+                                  void* stream_) {
+  return segment_unpool_impl(false, cell_vals, cell_ids, cell_ends, arg, n, channels, mode, out, stream_);
+}
+
+extern "C" int se3_segment_unpool_padded(const float* cell_vals, const int32_t* cell_ids, const int32_t* cell_ends,
+                                         const int32_t* arg, int64_t n_rows, int32_t channels, int32_t mode, float* out,
+                                         void* stream_) {
+  return segment_unpool_impl(true, cell_vals, cell_ids, cell_ends, arg, n_rows, channels, mode, out, stream_);
+}
+
+static int frame_pool_impl(const float* x, int64_t n_points, int32_t frames, const int32_t* n_valid, int32_t channels,
+                           int32_t mode, float* out, int32_t* arg, void* stream_) {
   if (n_points < 0 || frames < 1 || channels < 1 || mode < kPoolAvg || mode > kPoolSum) return SE3_ERR_INVALID_ARGUMENT;
   if (n_points == 0) return SE3_OK;
   if (!x || !out || ((mode == kPoolMax || mode == kPoolMin) && !arg)) return SE3_ERR_INVALID_ARGUMENT;
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid(blocks_for(n_points * channels)), block(256);
-#define SE3_FPOOL(M) hipLaunchKernelGGL(frame_pool_kernel<M>, grid, block, 0, stream, x, n_points, frames, channels, out, arg)
+#define SE3_FPOOL(M) \
+  hipLaunchKernelGGL(frame_pool_kernel<M>, grid, block, 0, stream, x, n_points, frames, channels, out, arg, n_valid)
   if (mode == kPoolAvg) SE3_FPOOL(kPoolAvg);
   else if (mode == kPoolMax) SE3_FPOOL(kPoolMax);
   else if (mode == kPoolMin) SE3_FPOOL(kPoolMin);
@@ -1811,21 +1855,50 @@ extern "C" int se3_frame_pool(const float* x, int64_t n_points, int32_t frames, 
   return check_launch();
 }
 
-extern "C" int se3_frame_unpool(const float* grad_out, const int32_t* arg, int64_t n_points, int32_t frames,
-                                int32_t channels, int32_t mode, float* grad_x, void* stream_) {
+extern "C" int se3_frame_pool(const float* x, int64_t n_points, int32_t frames, int32_t channels, int32_t mode, float* out,
+                              int32_t* arg, void* stream_) {
+  return frame_pool_impl(x, n_points, frames, nullptr, channels, mode, out, arg, stream_);
+}
+
+// n_rows * frames >= 2^31 (frames >= 1)
+static bool padded_rows_too_many(int64_t n_rows, int32_t frames) {
+  return n_rows >= (1ll << 31) / frames + ((1ll << 31) % frames != 0);
+}
+
+extern "C" int se3_frame_pool_padded(const float* x, int64_t n_rows, int32_t frames, const int32_t* n_valid,
+                                     int32_t channels, int32_t mode, float* out, int32_t* arg, void* stream_) {
+  if (n_rows >= 0 && frames >= 1 && padded_rows_too_many(n_rows, frames)) return SE3_ERR_UNSUPPORTED;
+  return frame_pool_impl(x, n_rows, frames, n_valid, channels, mode, out, arg, stream_);
+}
+
+static int frame_unpool_impl(const float* grad_out, const int32_t* arg, int64_t n_points, int32_t frames,
+                             const int32_t* n_valid, int32_t channels, int32_t mode, float* grad_x, void* stream_) {
   if (n_points < 0 || frames < 1 || channels < 1 || mode < kPoolAvg || mode > kPoolSum) return SE3_ERR_INVALID_ARGUMENT;
   if (n_points == 0) return SE3_OK;
   if (!grad_out || !grad_x || ((mode == kPoolMax || mode == kPoolMin) && !arg)) return SE3_ERR_INVALID_ARGUMENT;
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid(blocks_for(n_points * frames * channels)), block(256);
-#define SE3_FUNPOOL(M) \
-  hipLaunchKernelGGL(frame_unpool_kernel<M>, grid, block, 0, stream, grad_out, arg, n_points, frames, channels, grad_x)
+#define SE3_FUNPOOL(M)                                                                                                  \
+  hipLaunchKernelGGL(frame_unpool_kernel<M>, grid, block, 0, stream, grad_out, arg, n_points, frames, channels, grad_x, \
+                     n_valid)
   if (mode == kPoolAvg) SE3_FUNPOOL(kPoolAvg);
   else if (mode == kPoolMax) SE3_FUNPOOL(kPoolMax);
   else if (mode == kPoolMin) SE3_FUNPOOL(kPoolMin);
   else SE3_FUNPOOL(kPoolSum);
 #undef SE3_FUNPOOL
   return check_launch();
+}
+
+extern "C" int se3_frame_unpool(const float* grad_out, const int32_t* arg, int64_t n_points, int32_t frames,
+                                int32_t channels, int32_t mode, float* grad_x, void* stream_) {
+  return frame_unpool_impl(grad_out, arg, n_points, frames, nullptr, channels, mode, grad_x, stream_);
+}
+
+extern "C" int se3_frame_unpool_padded(const float* grad_out, const int32_t* arg, int64_t n_rows, int32_t frames,
+                                       const int32_t* n_valid, int32_t channels, int32_t mode, float* grad_x,
+                                       void* stream_) {
+  if (n_rows >= 0 && frames >= 1 && padded_rows_too_many(n_rows, frames)) return SE3_ERR_UNSUPPORTED;
+  return frame_unpool_impl(grad_out, arg, n_rows, frames, n_valid, channels, mode, grad_x, stream_);
 }
 
 // ---- random one-point-per-cell sub-sampling (GridSubSample(..., p_rnd_sample=True), pc/GridSubSample.py:43-54) -------
@@ -1875,6 +1948,23 @@ __global__ void rows_move_kernel(const W* __restrict__ src, const int32_t* __res
     const int64_t other = (int64_t)idx[r] * row_words + w;
     if (SCATTER) out[other] = src[t];
     else out[t] = src[other];
+  }
+}
+
+// Padded levels (se3conv_padded_rows.h), rows of W-sized words.  UNPICK false: out[r] = src[idx[r]], a zero row where
+// idx[r] < 0 (the pooling of a random level through `picked`, whose rows behind the kept cells hold -1).  UNPICK true: the
+// way back, written as a gather so that nothing has to be zeroed first: out[r] = src[cell] for cell = idx[r] when
+// cell >= 0 and picked[cell] == r (row r is the one that represents its cell), a zero row otherwise.
+template <bool UNPICK, typename W>
+__global__ void rows_gather_padded_kernel(const W* __restrict__ src, const int32_t* __restrict__ idx,
+                                          const int32_t* __restrict__ picked, int64_t n_rows, int64_t row_words,
+                                          W* __restrict__ out) {
+  const int64_t total = n_rows * row_words;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = t / row_words, w = t - r * row_words;
+    int from = idx[r];
+    if (UNPICK && from >= 0 && (int64_t)picked[from] != r) from = -1;
+    out[t] = from >= 0 ? src[(int64_t)from * row_words + w] : (W)0;
   }
 }
 }  // namespace
@@ -1975,4 +2065,37 @@ extern "C" int se3_rows_gather(const void* src, const int32_t* idx, int64_t n_ou
 
 extern "C" int se3_rows_scatter(const void* src, const int32_t* idx, int64_t n_src, int64_t row_bytes, void* out, void* stream) {
   return rows_move(true, src, idx, n_src, row_bytes, out, stream);
+}
+
+static int rows_gather_padded(bool unpick, const void* src, const int32_t* idx, const int32_t* picked, int64_t n_rows,
+                              int64_t row_bytes, void* out, void* stream_) {
+  if (n_rows < 0 || row_bytes < 1) return SE3_ERR_INVALID_ARGUMENT;
+  if (n_rows >= (1ll << 31)) return SE3_ERR_UNSUPPORTED;
+  if (n_rows == 0) return SE3_OK;
+  if (!src || !idx || !out || (unpick && !picked)) return SE3_ERR_INVALID_ARGUMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  const bool words = row_bytes % 4 == 0 && ((uintptr_t)src | (uintptr_t)out) % 4 == 0;
+  const int64_t rw = words ? row_bytes / 4 : row_bytes;
+  const dim3 grid(blocks_for(n_rows * rw)), block(256);
+#define SE3_ROWS(U, W) \
+  hipLaunchKernelGGL((rows_gather_padded_kernel<U, W>), grid, block, 0, stream, (const W*)src, idx, picked, n_rows, rw, (W*)out)
+  if (words) {
+    if (unpick) SE3_ROWS(true, uint32_t);
+    else SE3_ROWS(false, uint32_t);
+  } else {
+    if (unpick) SE3_ROWS(true, uint8_t);
+    else SE3_ROWS(false, uint8_t);
+  }
+#undef SE3_ROWS
+  return check_launch();
+}
+
+extern "C" int se3_rows_gather_padded(const void* src, const int32_t* idx, int64_t n_out, int64_t row_bytes, void* out,
+                                      void* stream) {
+  return rows_gather_padded(false, src, idx, nullptr, n_out, row_bytes, out, stream);
+}
+
+extern "C" int se3_rows_unpick_padded(const void* src, const int32_t* cell_ids, const int32_t* picked, int64_t n_in,
+                                      int64_t row_bytes, void* out, void* stream) {
+  return rows_gather_padded(true, src, cell_ids, picked, n_in, row_bytes, out, stream);
 }

@@ -1565,3 +1565,310 @@ class Linear(torch.autograd.Function):
         if ctx.has_b and ctx.needs_input_grad[2]:
             gb = g2.sum(0)
         return gx, gw, gb
+
+
+# ---------------------------------------------- row-wise passes on padded clouds (include/se3conv_padded_rows.h)
+# Feature tensors padded like their cloud: [n_rows * frames, C] of which the first clamp(*n_valid) * frames rows exist.  Every
+# function below takes the cloud's row-count word, never reads an absent row and leaves zeros there; the tensors are taken as
+# they are (float32, contiguous rows): nothing converts, and nothing is a torch fallback.
+def _padded_rows(t: torch.Tensor, frames: int, who: str) -> Tuple[torch.Tensor, int]:
+    """``t`` as the [n_rows * frames, C] float32 matrix the library reads, and ``n_rows``."""
+    t2 = _as(t, torch.float32)
+    if t2.dim() != 2 or not t2.is_cuda:
+        raise ValueError(f"{who}: expected [rows, C] features on the GPU (the HIP path has no CPU fallback)")
+    if int(frames) < 1 or t2.shape[0] % int(frames):
+        raise ValueError(f"{who}: {t2.shape[0]} rows are not a multiple of the frame count {frames}")
+    return t2, t2.shape[0] // int(frames)
+
+
+class BatchNormTrainPadded(torch.autograd.Function):
+    """``BatchNormTrain`` on the feature rows of a padded cloud (``se3_bn_fwd_padded`` / ``se3_bn_bwd_padded``): statistics
+    and gradient over the present rows alone, bit for bit those of ``BatchNormTrain`` on the trimmed tensor."""
+
+    @staticmethod
+    def forward(ctx, x, n_valid, n_frames, weight, bias, running_mean, running_var, momentum, eps, num_batches_tracked=None):
+        lib = _lib.load()
+        f32 = torch.float32
+        x2, n_rows = _padded_rows(x, n_frames, "BatchNormTrainPadded")
+        c, dev = x2.shape[1], x2.device
+        y = _empty_like(x2)
+        mean = _empty(c, dtype=f32, device=dev)
+        invstd = _empty(c, dtype=f32, device=dev)
+        w = _as(weight, f32) if weight is not None else None
+        b = _as(bias, f32) if bias is not None else None
+        ws = _glue_ws(c, dev)
+        _lib.check(lib.se3_bn_fwd_padded(
+            _ptr(x2, f32, "x"), _ptr(w, f32, "weight", dev), _ptr(b, f32, "bias", dev), n_rows, int(n_frames),
+            _valid_word(n_valid, dev, "BatchNormTrainPadded"), c, float(eps), float(momentum),
+            _ptr(running_mean, f32, "running_mean", dev), _ptr(running_var, f32, "running_var", dev),
+            _ptr(num_batches_tracked, torch.int64, "num_batches_tracked", dev), _ptr(y, f32, "y"), _ptr(mean, f32, "mean"),
+            _ptr(invstd, f32, "invstd"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_bn_fwd_padded")
+        ctx.save_for_backward(x2, w if w is not None else torch.empty(0, device=dev), mean, invstd)
+        ctx.has_w, ctx.n_valid, ctx.frames = w is not None, n_valid, int(n_frames)
+        ctx.mark_non_differentiable(*[t for t in (running_mean, running_var, num_batches_tracked) if t is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f32 = torch.float32
+        x2, w, mean, invstd = ctx.saved_tensors
+        g2 = _as(g, f32)
+        c, dev = x2.shape[1], x2.device
+        dx = _empty_like(x2)
+        dgamma = _empty(c, dtype=f32, device=dev)
+        dbeta = _empty(c, dtype=f32, device=dev)
+        ws = _glue_ws(c, dev)
+        _lib.check(lib.se3_bn_bwd_padded(
+            _ptr(g2, f32, "dy", dev), _ptr(x2, f32, "x"), _ptr(mean, f32, "mean"), _ptr(invstd, f32, "invstd"),
+            _ptr(w if ctx.has_w else None, f32, "weight"), x2.shape[0] // ctx.frames, ctx.frames,
+            _valid_word(ctx.n_valid, dev, "BatchNormTrainPadded"), c, _ptr(dx, f32, "dx"), _ptr(dgamma, f32, "dgamma"),
+            _ptr(dbeta, f32, "dbeta"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_bn_bwd_padded")
+        ng = ctx.needs_input_grad
+        return (dx if ng[0] else None, None, None, dgamma if ng[3] else None, dbeta if ng[4] else None, None, None, None,
+                None, None)
+
+
+class SkipDropPathPadded(torch.autograd.Function):
+    """``SkipDropPath`` on the feature rows of a padded cloud (``se3_skip_fwd_padded`` / ``se3_skip_bwd_padded``): the batch
+    id of an absent row is never used to index the gate."""
+
+    @staticmethod
+    def forward(ctx, x, y, gamma, gate, row_batch, gate_keep, n_valid, n_frames):
+        lib = _lib.load()
+        f32, i32 = torch.float32, torch.int32
+        x2, n_rows = _padded_rows(x, n_frames, "SkipDropPathPadded")
+        y2 = _as(y, f32)
+        if x2.shape != y2.shape:
+            raise ValueError("SkipDropPathPadded: x and y must be [rows, C] of the same shape")
+        c, dev = x2.shape[1], x2.device
+        ga = _as(gamma, f32).reshape(-1)
+        gt = _as(gate, f32) if gate is not None else None
+        rb = row_batch if gate is not None else None
+        if gt is not None and (rb is None or rb.shape[0] != x2.shape[0]):
+            raise ValueError("SkipDropPathPadded: one batch id per row expected")
+        out = _empty_like(x2)
+        _lib.check(lib.se3_skip_fwd_padded(
+            _ptr(x2, f32, "x"), _ptr(y2, f32, "y", dev), _ptr(ga, f32, "gamma", dev), _ptr(gt, f32, "gate", dev),
+            float(gate_keep), _ptr(rb, i32, "row_batch", dev), n_rows, int(n_frames),
+            _valid_word(n_valid, dev, "SkipDropPathPadded"), c, _ptr(out, f32, "out"), _stream(dev)), "se3_skip_fwd_padded")
+        ctx.save_for_backward(x2, ga, gt if gt is not None else torch.empty(0, device=dev),
+                              rb if rb is not None else torch.empty(0, dtype=i32, device=dev))
+        ctx.gated, ctx.gamma_shape, ctx.gate_keep = gt is not None, gamma.shape, float(gate_keep)
+        ctx.n_valid, ctx.frames = n_valid, int(n_frames)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f32, i32 = torch.float32, torch.int32
+        x2, ga, gt, rb = ctx.saved_tensors
+        g2 = _as(g, f32)
+        c, dev = x2.shape[1], x2.device
+        ng = ctx.needs_input_grad
+        dx = _empty_like(x2) if ng[0] else None
+        dgamma = _empty(c, dtype=f32, device=dev)
+        ws = _glue_ws(c, dev)
+        _lib.check(lib.se3_skip_bwd_padded(
+            _ptr(g2, f32, "g", dev), _ptr(x2, f32, "x"), _ptr(ga, f32, "gamma"), _ptr(gt if ctx.gated else None, f32, "gate"),
+            ctx.gate_keep, _ptr(rb if ctx.gated else None, i32, "row_batch"), x2.shape[0] // ctx.frames, ctx.frames,
+            _valid_word(ctx.n_valid, dev, "SkipDropPathPadded"), c, _ptr(dx, f32, "dx"), _ptr(dgamma, f32, "dgamma"),
+            C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_skip_bwd_padded")
+        return (dx, (g2 if ng[1] else None), (dgamma.reshape(ctx.gamma_shape) if ng[2] else None), None, None, None, None,
+                None)
+
+
+class FramePoolPadded(torch.autograd.Function):
+    """``FramePool`` on a padded cloud (``se3_frame_pool_padded`` / ``se3_frame_unpool_padded``): [n_rows * F, C] ->
+    [n_rows, C], absent points zero."""
+
+    @staticmethod
+    def forward(ctx, x, n_frames, method, n_valid):
+        lib = _lib.load()
+        mode = POOL_MODES[method]
+        x2, n = _padded_rows(x, n_frames, "FramePoolPadded")
+        c, dev = x2.shape[1], x2.device
+        out = _empty((n, c), dtype=torch.float32, device=dev)
+        arg = _empty((n, c), dtype=torch.int32, device=dev) if mode in (1, 2) else None
+        _lib.check(lib.se3_frame_pool_padded(_ptr(x2, torch.float32, "x"), n, int(n_frames),
+                                             _valid_word(n_valid, dev, "FramePoolPadded"), c, mode,
+                                             _ptr(out, torch.float32, "out"), _ptr(arg, torch.int32, "arg"), _stream(dev)),
+                   "se3_frame_pool_padded")
+        ctx.mode, ctx.arg, ctx.f, ctx.n_valid = mode, arg, int(n_frames), n_valid
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        g2 = _as(g, torch.float32)
+        n, c = g2.shape
+        dev = g2.device
+        gx = _empty((n * ctx.f, c), dtype=torch.float32, device=dev)
+        _lib.check(lib.se3_frame_unpool_padded(_ptr(g2, torch.float32, "grad_out"), _ptr(ctx.arg, torch.int32, "arg"), n, ctx.f,
+                                               _valid_word(ctx.n_valid, dev, "FramePoolPadded"), c, ctx.mode,
+                                               _ptr(gx, torch.float32, "grad_x"), _stream(dev)), "se3_frame_unpool_padded")
+        return gx, None, None, None
+
+
+def _level_pool(level, x2, mode: int, want_arg: bool):
+    """``se3_segment_pool`` over ALL ``capacity`` cells of a level of ``grid_levels_bounded``: ``cell_ends`` behind the kept
+    cells holds the present-row count, so those segments are empty -- 0 in ``out``, -1 in ``arg`` -- and only rows that kept
+    cells list are read."""
+    lib = _lib.load()
+    cap, c = level["cell_ends"].shape[0], x2.shape[1]
+    if x2.shape[0] != level["cell_ids"].shape[0]:
+        raise ValueError(f"pooling {x2.shape[0]} rows through a level with {level['cell_ids'].shape[0]} input rows")
+    out = _empty((cap, c), dtype=torch.float32, device=x2.device)
+    arg = _empty((cap, c), dtype=torch.int32, device=x2.device) if want_arg else None
+    _lib.check(lib.se3_segment_pool(_ptr(x2, torch.float32, "src"), _ptr(level["sorted_ids"], torch.int32, "sorted_ids"),
+                                    _ptr(level["cell_ends"], torch.int32, "cell_ends"), cap, c, mode,
+                                    _ptr(out, torch.float32, "out"), _ptr(arg, torch.int32, "arg"), _stream(x2.device)),
+               "se3_segment_pool")
+    return out, arg
+
+
+def _level_unpool(level, v2, arg, mode: int):
+    lib = _lib.load()
+    n, c = level["cell_ids"].shape[0], v2.shape[1]
+    if v2.shape[0] != level["cell_ends"].shape[0]:
+        raise ValueError(f"up-sampling {v2.shape[0]} rows through a level of capacity {level['cell_ends'].shape[0]}")
+    out = _empty((n, c), dtype=torch.float32, device=v2.device)
+    _lib.check(lib.se3_segment_unpool_padded(
+        _ptr(v2, torch.float32, "cell_vals"), _ptr(level["cell_ids"], torch.int32, "cell_ids"),
+        _ptr(level["cell_ends"], torch.int32, "cell_ends"), _ptr(arg, torch.int32, "arg"), n, c, mode,
+        _ptr(out, torch.float32, "out"), _stream(v2.device)), "se3_segment_unpool_padded")
+    return out
+
+
+class GridPoolPadded(torch.autograd.Function):
+    """``GridPool`` between two padded levels (``level``: one dict of ``BoundedLevels.levels``): [n_in, ...] -> [capacity, ...]
+    with zeros behind the kept cells; the gradient is ``se3_segment_unpool_padded``."""
+
+    @staticmethod
+    def forward(ctx, x, level, method):
+        mode = POOL_MODES[method]
+        x2 = _rows2d(_as(x, torch.float32))
+        out, arg = _level_pool(level, x2, mode, mode in (1, 2))
+        ctx.level, ctx.mode, ctx.arg, ctx.shape = level, mode, arg, x.shape
+        return out.reshape((out.shape[0],) + tuple(x.shape[1:]))
+
+    @staticmethod
+    def backward(ctx, g):
+        g2 = _rows2d(_as(g, torch.float32))
+        return _level_unpool(ctx.level, g2, ctx.arg, ctx.mode).reshape(ctx.shape), None, None
+
+
+class GridUpsamplePadded(torch.autograd.Function):
+    """``GridUpsample`` between two padded levels: rows of absent points and of dropped cells get zeros; the gradient is the
+    segment sum over all ``capacity`` cells."""
+
+    @staticmethod
+    def forward(ctx, x, level):
+        x2 = _rows2d(_as(x, torch.float32))
+        ctx.level, ctx.shape = level, x.shape
+        out = _level_unpool(level, x2, None, 3)
+        return out.reshape((out.shape[0],) + tuple(x.shape[1:]))
+
+    @staticmethod
+    def backward(ctx, g):
+        g2 = _rows2d(_as(g, torch.float32))
+        return _level_pool(ctx.level, g2, 3, False)[0].reshape(ctx.shape), None
+
+
+def rows_gather_padded(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """``src[idx]`` along dim 0 with a zero row where ``idx < 0`` (``se3_rows_gather_padded``)."""
+    if not src.is_cuda:
+        raise ValueError("rows_gather_padded: expected a GPU tensor (the HIP path has no CPU fallback)")
+    src = src.detach().contiguous()
+    out = _empty((idx.shape[0],) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if idx.shape[0] and out.numel():
+        _lib.check(_lib.load().se3_rows_gather_padded(
+            C.c_void_p(src.data_ptr()), _ptr(idx, torch.int32, "idx", src.device), idx.shape[0],
+            out[0].numel() * out.element_size(), C.c_void_p(out.data_ptr()), _stream(src.device)), "se3_rows_gather_padded")
+    return out
+
+
+def rows_unpick_padded(src: torch.Tensor, cell_ids: torch.Tensor, picked: torch.Tensor) -> torch.Tensor:
+    """``out[r] = src[cell_ids[r]]`` where row ``r`` is the one its cell picked (``picked[cell_ids[r]] == r``), zero rows
+    elsewhere (``se3_rows_unpick_padded``): the scatter of ``rows_scatter`` written as a gather."""
+    if not src.is_cuda:
+        raise ValueError("rows_unpick_padded: expected a GPU tensor (the HIP path has no CPU fallback)")
+    src = src.detach().contiguous()
+    if src.shape[0] != picked.shape[0]:
+        raise ValueError(f"rows_unpick_padded: {src.shape[0]} rows for {picked.shape[0]} cells")
+    out = _empty((cell_ids.shape[0],) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if cell_ids.shape[0] and out.numel():
+        _lib.check(_lib.load().se3_rows_unpick_padded(
+            C.c_void_p(src.data_ptr()), _ptr(cell_ids, torch.int32, "cell_ids", src.device),
+            _ptr(picked, torch.int32, "picked", src.device), cell_ids.shape[0], out[0].numel() * out.element_size(),
+            C.c_void_p(out.data_ptr()), _stream(src.device)), "se3_rows_unpick_padded")
+    return out
+
+
+class RowsGatherPadded(torch.autograd.Function):
+    """Pooling through a padded random level: ``x[picked]``, zero rows behind the kept cells; the gradient is
+    ``rows_unpick_padded``."""
+
+    @staticmethod
+    def forward(ctx, x, cell_ids, picked):
+        ctx.cell_ids, ctx.picked = cell_ids, picked
+        return rows_gather_padded(x, picked)
+
+    @staticmethod
+    def backward(ctx, g):
+        return rows_unpick_padded(g, ctx.cell_ids, ctx.picked), None, None
+
+
+class RowsUnpickPadded(torch.autograd.Function):
+    """Up-sampling through a padded random level (``rows_unpick_padded``); the gradient is ``rows_gather_padded``."""
+
+    @staticmethod
+    def forward(ctx, x, cell_ids, picked):
+        ctx.picked = picked
+        return rows_unpick_padded(x, cell_ids, picked)
+
+    @staticmethod
+    def backward(ctx, g):
+        return rows_gather_padded(g, ctx.picked), None, None
+
+
+def channel_sums(x2: torch.Tensor, n_valid: Optional[torch.Tensor] = None, n_frames: int = 1) -> torch.Tensor:
+    """``x2[:present].sum(0)`` of a [n_rows * frames, C] float32 matrix (``se3_channel_sums_padded``): fp64 partial sums in a
+    fixed order, and -- unlike torch's multi-block column sum, which zeroes its semaphores -- no memset node in a captured
+    graph."""
+    lib = _lib.load()
+    f32 = torch.float32
+    x2, n_rows = _padded_rows(x2, n_frames, "channel_sums")
+    c, dev = x2.shape[1], x2.device
+    out = _empty(c, dtype=f32, device=dev)
+    ws = _glue_ws(c, dev)
+    _lib.check(lib.se3_channel_sums_padded(_ptr(x2, f32, "x"), n_rows, int(n_frames), _valid_word(n_valid, dev, "channel_sums"), c,
+                                           _ptr(out, f32, "sums"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)),
+               "se3_channel_sums_padded")
+    return out
+
+
+class LinearPadded(torch.autograd.Function):
+    """``Linear`` on the feature rows of a padded cloud.  Forward and input gradient are the row-wise GEMMs (absent rows stay
+    finite: they hold the bias); the weight gradient is the library's row-split GEMM over all rows -- the gradient rows of
+    absent points are zero (pc.py: the invariant) --, and the bias gradient is ``channel_sums`` over the present rows
+    instead of ``g.sum(0)``, so that a captured step holds no memset node.  ``n_valid`` None: every row is present."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, n_valid, n_frames):
+        ctx.save_for_backward(x, weight)
+        ctx.has_b, ctx.n_valid, ctx.frames = bias is not None, n_valid, int(n_frames)
+        return torch.nn.functional.linear(x, weight, bias)
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, gw, _ = Linear.backward(_NoBias(ctx), g)
+        gb = channel_sums(_as(g, torch.float32), ctx.n_valid, ctx.frames) if ctx.has_b and ctx.needs_input_grad[2] else None
+        return gx, gw, gb, None, None
+
+
+class _NoBias:
+    """The context of ``LinearPadded`` as ``Linear.backward`` reads it, with the bias gradient left to the caller."""
+
+    def __init__(self, ctx):
+        self.saved_tensors, self.needs_input_grad, self.has_b = ctx.saved_tensors, ctx.needs_input_grad, False

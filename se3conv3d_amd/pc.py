@@ -12,6 +12,17 @@ Only what the convolution and the benchmark stack need:
     pc/Grid.py:37-57, pc/PointHierarchy.py:10-93, pc/PointHierarchyRotEquiv.py:7-44): grid-average and
     random one-point-per-cell sub-sampling (``se3_grid_subsample`` / ``se3_grid_pick``), neighbourhood memo
     (ball query and k-NN).
+
+Padded feature rows (``p_padded_rows=True`` on a padded cloud or hierarchy, include/se3conv_padded_rows.h).  The feature
+tensors of such a cloud are padded like its points: ``[n_rows * F, C]`` of which the first ``n_valid_ * F`` rows exist.  What
+a network gets:
+
+  * Every library pass on a flagged cloud -- batch norm, skip connection, drop path, frame pooling, ``pool_tensor`` /
+    ``upsample_tensor`` -- reads no absent row and leaves ZEROS at the absent rows of what it returns, so the convolution's
+    "absent feature rows are finite" obligation holds by construction.
+  * Stock torch ops between the library passes (Linear, GELU) are row-wise: they keep absent rows finite.
+  * The caller's obligations: the level-0 input features are finite in every row of the buffer, and the loss ignores the
+    absent rows (``present_mask``), so that the gradient arriving there is zero.
 """
 from __future__ import annotations
 
@@ -78,6 +89,30 @@ def refuse_padded(cloud, what: str) -> None:
                                   "p_padded=False for it")
 
 
+def padded_rows(cloud) -> bool:
+    """Whether the feature tensors of ``cloud`` are padded like its points (``p_padded_rows=True``): the row-wise passes then
+    skip the absent rows and write zeros there instead of refusing."""
+    return bool(getattr(cloud, "padded_rows_", False))
+
+
+def refuse_unflagged(cloud, what: str) -> None:
+    """``refuse_padded`` unless the cloud was built with ``p_padded_rows=True``."""
+    if not padded_rows(cloud):
+        refuse_padded(cloud, what)
+
+
+def present_mask(cloud, per_frame: bool = False) -> torch.Tensor:
+    """Bool ``[n_rows]`` (``per_frame``: ``[n_rows * F]``, one entry per feature row) that is True at the present rows of
+    ``cloud``: ``arange < word`` built with torch ops, no read-back -- what a loss uses to ignore the absent rows.  All True
+    for an ordinary cloud."""
+    n = int(cloud.pts_.shape[0])
+    f = int(getattr(cloud, "n_frames_", 1)) if per_frame else 1
+    idx = torch.arange(n * f, device=cloud.pts_.device)
+    if not is_padded(cloud):
+        return idx >= 0
+    return idx < torch.clamp(cloud.n_valid_, 0, n) * f
+
+
 def _batches_of(cloud):
     """The batch count a grid sub-sample of ``cloud`` has: its own (every batch element that holds a point keeps a cell, so
     the largest id survives); None for foreign cloud objects."""
@@ -95,11 +130,19 @@ class Pointcloud(object):
     A graph replay rewrites the words, points and batch ids of the clouds a captured build made without moving a version:
     such held clouds are for reading (``pts_``, ``n_valid_``, ``local_frames_``, the neighbourhoods built in the capture), not
     for further eager queries, which could meet a box, table or grid of the replay before.  Query a fresh ``Pointcloud`` over
-    the same buffers instead (or call ``ops.forget_source_grids(cloud)`` and drop ``_se3_aabb`` / ``_se3_knn_ids``)."""
+    the same buffers instead (or call ``ops.forget_source_grids(cloud)`` and drop ``_se3_aabb`` / ``_se3_knn_ids``).
+
+    ``p_padded_rows=True`` (extension, keyword, needs ``p_n_valid``; attribute ``padded_rows_``): the feature tensors of this
+    cloud are padded like its points.  The row-wise glue (blocks.py, ``feature_pooling``) then skips the absent rows and
+    writes zeros there (include/se3conv_padded_rows.h; the invariant a network gets: module docstring).  Without it that
+    glue refuses a padded cloud."""
 
     def __init__(self, p_pts, p_batch_ids, **kwargs):
         self.pts_with_grads_ = bool(kwargs.pop("requires_grad", False))
         self.n_valid_ = kwargs.pop("p_n_valid", None)
+        self.padded_rows_ = bool(kwargs.pop("p_padded_rows", False))
+        if self.padded_rows_ and self.n_valid_ is None:
+            raise ValueError("p_padded_rows=True needs p_n_valid: only a padded cloud has padded feature rows")
         # num_batches (extension): the batch count when the caller knows it (a hierarchy level has its parent's) -- spares
         # the read-back of batch_size_ the native calls' table sizes would otherwise cost once per cloud
         known_batches = kwargs.pop("num_batches", None)
@@ -183,6 +226,7 @@ class PointcloudRotEquiv(Pointcloud):
         super().__init__(p_pts, p_batch_ids, **kwargs)
         kwargs.pop("num_batches", None)  # (consumed by Pointcloud.__init__; the rest are torch.as_tensor keywords)
         kwargs.pop("p_n_valid", None)
+        kwargs.pop("p_padded_rows", None)
         self.neigh_cache_ = {}
         self.local_frames_pca_cache_ = {}
         self.local_frames_config_ = p_ref_frames_config
@@ -278,10 +322,20 @@ class PointcloudRotEquiv(Pointcloud):
         return cache[key]
 
     @classmethod
-    def from_frames(cls, p_pts, p_batch_ids, p_frames, p_ref_frames_config=None):
-        """Cloud with externally supplied frames ``[N,F,9]`` (e.g. PCA frames computed upstream)."""
+    def from_frames(cls, p_pts, p_batch_ids, p_frames, p_ref_frames_config=None, p_n_valid=None, num_batches=None,
+                    p_padded_rows=False):
+        """Cloud with externally supplied frames ``[N,F,9]`` (e.g. PCA frames computed upstream).  ``p_n_valid``,
+        ``num_batches``, ``p_padded_rows``: as in the constructor (a padded cloud; the frames of absent rows are not
+        looked at)."""
         self = cls.__new__(cls)
-        Pointcloud.__init__(self, p_pts, p_batch_ids)
+        extra = {}
+        if p_n_valid is not None:
+            extra["p_n_valid"] = p_n_valid
+        if num_batches is not None:
+            extra["num_batches"] = num_batches
+        if p_padded_rows:
+            extra["p_padded_rows"] = True
+        Pointcloud.__init__(self, p_pts, p_batch_ids, **extra)
         self.local_frames_ = torch.as_tensor(p_frames).reshape(self.pts_.shape[0], -1, 9)
         self.n_frames_ = self.local_frames_.shape[1]
         self.local_frames_config_ = p_ref_frames_config or {"pca": False, "n_frames": self.n_frames_,
@@ -316,7 +370,9 @@ class PointcloudRotEquiv(Pointcloud):
         forward and one backward."""
         if p_pooling_method not in ops.POOL_MODES:
             raise ValueError(p_pooling_method)
-        refuse_padded(self, "feature_pooling")
+        refuse_unflagged(self, "feature_pooling")
+        if padded_rows(self):  # always the library's kernel, eager or captured: torch's reduction would read the absent rows
+            return ops.FramePoolPadded.apply(p_in_tensor, self.n_frames_, p_pooling_method, self.n_valid_)
         # Launched eagerly, a custom autograd.Function costs more in Python than this pass costs on the GPU (fwd + bwd
         # 0.099 ms through the library against 0.057 ms of stock torch ops at 65 k points, profiles/r03_next_rows.txt): outside
         # a graph capture the reduction over the frame axis is torch's own (max / min route their gradient to the winning
@@ -638,20 +694,46 @@ class PaddedSubSample(object):
     """The sub-sampling step between two PADDED levels (``PointHierarchy(..., p_padded=True)``): the tensors of
     ``struct se3_level`` as ``ops.grid_levels_bounded`` wrote them (``level_`` -- ``cell_ids``, ``sorted_ids``,
     ``cell_ends``, ``pts``, ``batch_ids`` and on random levels ``u``, ``ids``, ``picked``), every one of capacity size, and
-    the level's size and overflow flag on the device (``info_ [2]``).  Pooling and up-sampling feature rows through it is
-    not implemented."""
+    the level's size and overflow flag on the device (``info_ [2]``).  Pooling and up-sampling feature rows through it
+    needs ``p_padded_rows`` (``PointHierarchy(..., p_padded=True, p_padded_rows=True)``): ``[n_in, ...]`` floating-point
+    tensors padded like the source level become ``[capacity, ...]`` tensors padded like this one and back -- averaged
+    levels through ``ops.GridPoolPadded`` / ``ops.GridUpsamplePadded`` (``avg`` / ``max``), random levels through
+    ``ops.RowsGatherPadded`` / ``ops.RowsUnpickPadded``; no absent row or dropped cell is read, and their rows are zero."""
 
-    def __init__(self, p_pc_src, p_cell_size, p_level, p_info, p_rnd_sample=False):
+    def __init__(self, p_pc_src, p_cell_size, p_level, p_info, p_rnd_sample=False, p_padded_rows=False):
         self.pc_src_, self.cell_size_, self.level_, self.info_ = p_pc_src, p_cell_size, p_level, p_info
         self.rnd_sample_ = bool(p_rnd_sample)
+        self.padded_rows_ = bool(p_padded_rows)
         self.cell_ids_, self.sorted_ids_ = p_level["cell_ids"], p_level["sorted_ids"]
         self.capacity_ = int(p_level["pts"].shape[0])
 
     def __subsample_tensor__(self, p_tensor, p_method="avg"):
+        if self.padded_rows_:
+            if p_tensor is self.pc_src_.pts_ and p_method == "avg" and not p_tensor.requires_grad:
+                return self.level_["pts"]
+            if p_tensor is self.pc_src_.batch_ids_ and p_method == "max":
+                return self.level_["batch_ids"]
+            if not p_tensor.is_floating_point():
+                raise ValueError("pool_tensor on padded levels takes floating-point tensors only (the level's points and "
+                                 "batch ids are its own buffers)")
+            if self.rnd_sample_:
+                return ops.RowsGatherPadded.apply(p_tensor, self.cell_ids_, self.level_["picked"])
+            if p_method not in ("avg", "max"):
+                raise ValueError(p_method)
+            return ops.GridPoolPadded.apply(p_tensor, self.level_, p_method)
         raise NotImplementedError("pool_tensor on padded levels (p_padded=True) is not implemented: the pooled rows would "
                                   "need the level's present-row count, which is a device word")
 
     def __upsample_tensor__(self, p_tensor):
+        if self.padded_rows_:
+            if not p_tensor.is_floating_point():
+                raise ValueError("upsample_tensor on padded levels takes floating-point tensors only")
+            if self.rnd_sample_:
+                if p_tensor.dim() != 2:
+                    raise ValueError("__upsample_tensor__ of a random grid sub-sample takes [cells, C] tensors (as the "
+                                     "reference)")
+                return ops.RowsUnpickPadded.apply(p_tensor, self.cell_ids_, self.level_["picked"])
+            return ops.GridUpsamplePadded.apply(p_tensor, self.level_)
         raise NotImplementedError("upsample_tensor on padded levels (p_padded=True) is not implemented: the absent rows' "
                                   "cell ids are -1")
 
@@ -669,13 +751,20 @@ class PointHierarchy(object):
     (include/se3conv_padded.h), so that hierarchy, frames, neighbourhoods and convolutions capture into one HIP graph that
     can be replayed on a batch with another point count.  Level 0 may be a padded cloud itself.  ``level_sizes()`` and
     ``overflowed()`` are the read-backs, done only when asked.  ``pool_tensor`` / ``upsample_tensor`` are not implemented
-    on padded levels."""
+    on padded levels unless the hierarchy is flagged:
+
+    ``p_padded_rows=True`` (extension, needs ``p_padded``): every level cloud the hierarchy builds carries the flag
+    (``Pointcloud(..., p_padded_rows=True)``: feature tensors padded like the points, the glue skips absent rows and writes
+    zeros there), and ``pool_tensor`` / ``upsample_tensor`` work on such tensors (``PaddedSubSample``)."""
 
     def __init__(self, p_point_cloud, p_num_sub_samples, p_subsample_method="grid_avg", p_capacities=None, p_padded=False,
-                 **kwargs):
+                 p_padded_rows=False, **kwargs):
         self.sub_sampled_objs_ = []
         self.pcs_ = [p_point_cloud]
         self.padded_ = bool(p_padded)
+        self.padded_rows_ = bool(p_padded_rows)
+        if self.padded_rows_ and not self.padded_:
+            raise ValueError("PointHierarchy: p_padded_rows=True needs p_padded=True")
         self.level_info_ = None
         cur = p_point_cloud
         if self.padded_:
@@ -693,7 +782,7 @@ class PointHierarchy(object):
                 for i, lv in enumerate(built.levels):
                     # the level's row-count word: min(true cell count, capacity), formed on the device
                     word = torch.clamp(built.info[i, 0:1], max=int(built.capacities[i]))
-                    samp = PaddedSubSample(cur, radii[i], lv, built.info[i], rnd)
+                    samp = PaddedSubSample(cur, radii[i], lv, built.info[i], rnd, self.padded_rows_)
                     cur = self.__padded_level_cloud__(cur, lv["pts"], lv["batch_ids"], word)
                     self.sub_sampled_objs_.append(samp)
                     self.pcs_.append(cur)
@@ -727,7 +816,8 @@ class PointHierarchy(object):
         return Pointcloud(new_pts, new_bid, num_batches=_batches_of(p_point_cloud))
 
     def __padded_level_cloud__(self, p_point_cloud, p_pts, p_batch_ids, p_word):
-        return Pointcloud(p_pts, p_batch_ids, p_n_valid=p_word, num_batches=_batches_of(p_point_cloud))
+        return Pointcloud(p_pts, p_batch_ids, p_n_valid=p_word, num_batches=_batches_of(p_point_cloud),
+                          p_padded_rows=self.padded_rows_)
 
     def level_sizes(self):
         """Present rows of every level as host integers (level 0 included): the read-back of a padded hierarchy, done
@@ -793,4 +883,4 @@ class PointHierarchyRotEquiv(PointHierarchy):
 
     def __padded_level_cloud__(self, p_point_cloud, p_pts, p_batch_ids, p_word):
         return PointcloudRotEquiv(p_pts, p_batch_ids, p_point_cloud.local_frames_config_, p_n_valid=p_word,
-                                  num_batches=_batches_of(p_point_cloud))
+                                  num_batches=_batches_of(p_point_cloud), p_padded_rows=self.padded_rows_)

@@ -209,8 +209,15 @@ int se3_ball_query_grid_from_box(const float* box_min, const float* box_max, int
  *   store: second pass over the same windows; writes neighbors[E,2] = (sample, source) grouped
  *          by sample.  Order inside a sample is deterministic here (pencil order, then sorted
  *          position); the reference's is not (atomics).
- * Predicate: sqrt(sum(((s - p) * (1/r))^2)) < 1 in fp32 and equal batch id
- *   (count_neighbors.cu:84-89).  `aabb_min`/`num_cells` as BallQuery.py:34-38 builds them.
+ * Predicate: sqrt(sum(((s - p) * (1/r))^2)) < 1 in fp32, every operation rounded on its own, and equal batch id
+ *   (count_neighbors.cu:84-89).  The predicate DEFINES the edge set: every entry point below returns exactly it on
+ *   either route (all pairs, cell grid), for any number of sources.  `aabb_min`/`num_cells` as BallQuery.py:34-38
+ *   builds them.  The grid route's own cells are a search aid, not the reference's: size radius * (1 + 2^-21 * (n + 8))
+ *   in fp32, n = the largest of the three cell counts (with 32-bit keys: at most 1024).  With the reference's cell =
+ *   radius the 3x3x3 window holds the ball in exact arithmetic only -- in fp32 a source just inside the radius of a
+ *   sample on a cell face can land two cells away, and the reference's windows drop that edge; the margin is the
+ *   rounding bound under which a pair the predicate accepts is never more than one cell apart (derivation:
+ *   bq_search_cell, csrc/geometry.hip).  se3_compute_keys keeps the reference's cells bit for bit.
  * The workspace written by `count` must be passed unchanged to `store`.
  * ------------------------------------------------------------------------------------------- */
 /* 0 when the source set is small enough for the all-pairs path of the two phases below (aabb_min / num_cells may

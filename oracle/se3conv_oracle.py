@@ -81,9 +81,15 @@ def ball_query(pts_src, pts_dst, batch_src, batch_dst, radius: float, chunk: int
     """Radius neighbours, brute force, with the CUDA predicate.
 
     Predicate (OPS/ball_query/count_neighbors.cu:84-89, math_helper.cuh:316-320):
-    ``sqrt(sum(((s - p) * (1/r))**2)) < 1`` in fp32, same batch id; the candidate set of
-    the grid search (3x3 pencils x [key-1, key+1] in z, find_ranges_grid_ds.cu:41-166) is
-    a superset of that ball for cell size = radius, so brute force gives the same edge SET.
+    ``sqrt(sum(((s - p) * (1/r))**2)) < 1`` in fp32, every operation rounded on its own, same
+    batch id.  This predicate DEFINES the edge set: every search route of the library returns
+    exactly it.  The candidate set of the reference's grid search (3x3 pencils x [key-1, key+1]
+    in z, find_ranges_grid_ds.cu:41-166, cell size = radius) is a superset of that ball in
+    exact arithmetic only.  In fp32 the two cell coordinates of a pair are rounded apart from
+    the pair's own difference, and a source just inside the radius of a sample on a cell face
+    can land two cells away: in ``[[0,0,0],[0.279999,0,0],[0.209999,0,0],[0.5,0.5,0.5]]`` with
+    r = 0.07, points 1 and 2 are neighbours here, get x cells 4 and 2, and ``ball_query_grid``
+    lists neither direction (tests/boundary_pairs.py plants such pairs).
     Output follows ball_query.cu:92-101 / store_neighbors.cu: ``neighbors[E,2]`` int64 with
     col0 = sample id, col1 = source id, grouped by sample; ``ends[M]`` int32 inclusive end
     offsets.  Order inside a sample is undefined in the reference (atomics); here it is
@@ -114,8 +120,10 @@ def ball_query_grid(pts_src, pts_dst, batch_src, batch_dst, radius: float):
 
     keys -> argsort -> pencil table -> 9 (dx,dy) offsets x z-window [cz-1, cz+1] clamped to
     the grid -> distance test.  (ball_query.cu:22-103, build_grid_ds.cu:31-66,
-    find_ranges_grid_ds.cu:41-166, count_neighbors.cu:36-103.)  Used by the tests to show
-    that the candidate windows lose no neighbour w.r.t. ``ball_query`` above.
+    find_ranges_grid_ds.cu:41-166, count_neighbors.cu:36-103.)  A restatement of the
+    reference's windows, not the definition of the edge set: on ``torch.rand`` clouds it
+    equals ``ball_query`` above (tests/test_oracle_golden.py), on pairs just inside the radius
+    across a cell face it loses edges (see there; tests/test_boundary_pairs.py).
     """
     mn, nc = ball_query_grid_params(pts_src, batch_src, radius)
     cs = torch.full((3,), radius, dtype=torch.float32)

@@ -60,14 +60,43 @@ struct Key32 {
   }
 };
 
+// ---- the ball query's search cell ---------------------------------------------------------------------------------------
+// The edge set is defined by the predicate (within_ball below), and the grid path has to list every pair the predicate
+// accepts.  With cell = radius that holds in exact arithmetic only: the two `rel` values of a pair (cell_of) are rounded
+// apart from the pair's own difference, so a source just inside the radius of a sample that sits on a cell face can land TWO
+// cells away, outside the 3x3x3 window.  The search therefore uses a cell a hair larger than the radius,
+//     cell = radius * (1 + m),   m = 2^-21 * (n + 8),   n = the largest cell count per axis that the keys are built with,
+// from this bound (u = 2^-24, one fp32 rounding; per axis):
+//   * a hit has |d| < 1 for d = fl(fl(s - p) * fl(1/r)), hence |fl(s - p)| < r / (1 - u) and |s - p| < r (1 + 3u);
+//   * rel(x) = fl(fl(x - min) * fl(1/cell)) = (x - min) * fl(1/cell) * (1 + e), |e| <= 2u + u^2, so
+//       |rel(s) - rel(p)| <= (1 + u) / cell * (|s - p| + (2u + u^2) (|s - min| + |p - min|));
+//   * a source lies in the box the cell counts were taken from, at most (n + 1) r above `min` (the box's 1e-6 shifts
+//     included, for r > 2e-6), and a sample that hits it within r (1 + 3u) of it: |x - min| <= (n + 2) r for both.  (Key32
+//     beyond its stride: once the lower index of a pair reaches 1023 both clamp to 1023, so only pairs whose lower point
+//     lies below 1023 cells, which is below 1023.5 r, count, and for those the same holds with n = 1024);
+//   * with cell >= r (1 + m)(1 - 2u):  |rel(s) - rel(p)| < (1 + 7u + 4.2u (n + 2)) / (1 + m), which is below 1 as soon as
+//     m > 7u + 4.2u (n + 2): m = 8u (n + 8) satisfies it for every n, with a factor of almost two to spare.
+// |rel(s) - rel(p)| < 1 puts the floors at most one apart, and the clamps are monotone: a hit is never more than one cell
+// away.  aabb_min / num_cells stay the caller's (BallQuery.py:34-38): the indices only shrink, so the clamps still hold.
+// At 40 cells per axis m is 2.3e-5; the cost is a candidate volume larger by (1 + m)^3.  The keys of se3_compute_keys, of
+// the grid sub-sampling and of the k-NN are cell DEFINITIONS and keep their cell size.
+template <class KEY>
+__device__ __forceinline__ float bq_search_cell(float radius, const int32_t* __restrict__ num_cells) {
+#pragma clang fp contract(off)
+  const int n = KEY::cells(max(num_cells[0], max(num_cells[1], num_cells[2])));
+  return radius * (1.0f + 0x1p-21f * ((float)n + 8.0f));
+}
+
 template <class KEY>
 __global__ void compute_keys_kernel(const float* __restrict__ pts, const int32_t* __restrict__ batch_ids,
                                     const float* __restrict__ aabb_min, const int32_t* __restrict__ num_cells,
                                     const float* __restrict__ cell_size, float cell_scalar, int64_t n,
                                     typename KEY::type* __restrict__ keys, int32_t* __restrict__ iota,
-                                    const int32_t* __restrict__ n_valid) {
-  // cell_size == nullptr: the same cell size `cell_scalar` in every dimension (ball query: cell = radius)
+                                    const int32_t* __restrict__ n_valid, bool search_cell) {
+  // cell_size == nullptr: the same cell size `cell_scalar` in every dimension (grid sub-sampling), or with `search_cell`
+  // the ball query's search cell for the radius `cell_scalar`
   const int nc[3] = {KEY::cells(num_cells[0]), KEY::cells(num_cells[1]), KEY::cells(num_cells[2])};
+  if (search_cell) cell_scalar = bq_search_cell<KEY>(cell_scalar, num_cells);
   const float inv[3] = {1.0f / (cell_size ? cell_size[0] : cell_scalar), 1.0f / (cell_size ? cell_size[1] : cell_scalar),
                         1.0f / (cell_size ? cell_size[2] : cell_scalar)};
   // n_valid (device, may be NULL = n): rows from *n_valid on are absent (se3_grid_levels).  They are not read and get
@@ -119,8 +148,8 @@ __global__ void find_ranges_kernel(const float* __restrict__ pts_dst, const int3
                                    int2* __restrict__ ranges, const int32_t* __restrict__ order,
                                    const int32_t* __restrict__ n_valid_src, const int32_t* __restrict__ n_valid_dst) {
   const int nc[3] = {KEY::cells(num_cells[0]), KEY::cells(num_cells[1]), KEY::cells(num_cells[2])};
-  const float inv_r = 1.0f / radius;
-  const float inv[3] = {inv_r, inv_r, inv_r};
+  const float inv_cell = 1.0f / bq_search_cell<KEY>(radius, num_cells);  // the cell the source keys were built with
+  const float inv[3] = {inv_cell, inv_cell, inv_cell};
   // padded clouds (se3conv_padded.h): the searches run over the present prefix of the sorted keys, and an absent sample --
   // not read -- gets nine empty windows
   n_src = (int)present_rows(n_valid_src, n_src);
@@ -763,7 +792,7 @@ extern "C" int se3_compute_keys(const float* pts, const int32_t* batch_ids, cons
     return SE3_ERR_INVALID_ARGUMENT;
   if (n == 0) return SE3_OK;
   hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pts, batch_ids,
-                     aabb_min, num_cells, cell_size, 0.f, n, keys, (int32_t*)nullptr, (const int32_t*)nullptr);
+                     aabb_min, num_cells, cell_size, 0.f, n, keys, (int32_t*)nullptr, (const int32_t*)nullptr, false);
   return check_launch();
 }
 
@@ -957,7 +986,7 @@ static int knn_query_grid_impl(const float* pts, const int32_t* batch_ids, const
   {
     ProfScope prof("knn_sort", stream);
     hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, aabb_min, num_cells,
-                       cell_size, 0.f, n, keys, ids, n_valid);
+                       cell_size, 0.f, n, keys, ids, n_valid, false);
     if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sids, (int)n, 0, 64, stream) !=
         hipSuccess)
       return SE3_ERR_LAUNCH;
@@ -1131,9 +1160,9 @@ static int bq_grid_windows(const BqCall& c, const BqPlan& p, int key_bits) {
   if (p.build_grid) {
     K* keys = (K*)(gws + p.l.keys);
     int32_t* ids = (int32_t*)(gws + p.l.ids);
-    // cell size = radius in every dimension (BallQuery.py:39-40)
+    // the search cell of the radius in every dimension (bq_search_cell; the reference: cell = radius, BallQuery.py:39-40)
     hipLaunchKernelGGL(compute_keys_kernel<KEY>, dim3(blocks_for(c.n_src)), dim3(256), 0, c.stream, c.pts_src, c.batch_src,
-                       c.aabb_min, c.num_cells, (const float*)nullptr, c.radius, c.n_src, keys, ids, c.n_valid_src);
+                       c.aabb_min, c.num_cells, (const float*)nullptr, c.radius, c.n_src, keys, ids, c.n_valid_src, true);
     size_t temp_bytes = p.l.temp_bytes;
     if (sort_pairs_no_scratch(ws + p.l.temp, temp_bytes, keys, skeys, ids, sids, (int)c.n_src, 0, key_bits, c.stream) != hipSuccess)
       return SE3_ERR_LAUNCH;
@@ -1740,7 +1769,7 @@ static int grid_cells_impl(const float* pts, const int32_t* batch_ids, int64_t n
     hipLaunchKernelGGL(grid_params_kernel, dim3((n_batches * 3 + 255) / 256), dim3(256), 0, stream, box_min, box_max,
                        n_batches, cell_size, 1e-6f, num_cells);
     hipLaunchKernelGGL(compute_keys_kernel<Key64>, dim3(blocks_for(n)), dim3(256), 0, stream, pts, batch_ids, box_min,
-                       num_cells, (const float*)nullptr, cell_size, n, keys, ids, n_valid);
+                       num_cells, (const float*)nullptr, cell_size, n, keys, ids, n_valid, false);
     size_t temp_bytes = l.temp_bytes;
     if (sort_pairs_no_scratch(ws + l.temp, temp_bytes, keys, skeys, ids, sorted_ids, (int)n, 0, 64, stream) !=
         hipSuccess)

@@ -5,6 +5,7 @@ neighbourhood + convolution step captured into one HIP graph."""
 import pytest
 import torch
 
+from boundary_pairs import search_cell
 from conftest import canon_edges, rel_err
 from oracle import se3conv_oracle as O
 from se3conv3d_amd.workloads import radius_for_degree
@@ -53,7 +54,8 @@ def test_bounded_equals_two_phase_and_oracle(amd, n_src, n_dst, batches, r):
     if int(nc.max()) <= 1024:
         order = torch.arange(e)                       # (the oracle lists a sample's hits in ascending source id)
         if amd.ops.ball_query_needs_grid(n_src):
-            key = O.compute_keys(ps, bs, mn, nc, cell_size=torch.full((3,), r))
+            # (the grid key: of the library's search cell, a hair larger than the radius -- include/se3conv.h)
+            key = O.compute_keys(ps, bs, mn, nc, cell_size=search_cell(r, nc))
             order = torch.argsort(key[nb_r[:, 1]], stable=True)
             order = order[torch.argsort(nb_r[order, 0], stable=True)]
         assert torch.equal(ends2.cpu(), ends_r)       # (so equal lists are equal segment by segment)

@@ -67,7 +67,8 @@ def test_ball_query_matches_reference_edges(path):
 
 @pytest.mark.parametrize("name", ["layer_down_n512_n128_f2.npz", "layer_sparse_n200_f2.npz", "layer_n256_f2_c64.npz"])
 def test_grid_search_loses_no_neighbour(name):
-    """The reference's grid windows (3x3 pencils x [z-1,z+1]) give the brute-force edge set."""
+    """The reference's grid windows (3x3 pencils x [z-1,z+1]) give the brute-force edge set on these fixtures (not on
+    every cloud: tests/test_boundary_pairs.py)."""
     d = load_npz(os.path.join(GOLDEN, name))
     nb_g, ends_g = O.ball_query_grid(d["pts_in"], d["pts_out"], d["batch_in"], d["batch_out"], float(d["radius"]))
     assert torch.equal(ends_g, d["ends"])

@@ -14,9 +14,10 @@ profiles/r03_block_glue_timing.txt); the forward and input-gradient C x C produc
 
 Padded clouds.  A cloud built with ``p_n_valid`` alone is refused by every module here.  One built with
 ``p_padded_rows=True`` (pc.py) has feature tensors padded like its points, and the modules run the library's padded passes
-(include/se3conv_padded_rows.h; ops.BatchNormTrainPadded / SkipDropPathPadded): statistics, ``1/N`` and channel sums over the
-present rows alone -- bit for bit those of the trimmed tensors --, no absent row read (an absent row's batch id never
-indexes the drop-path gate), zeros written at the absent rows.  The invariant a network gets: every library pass leaves
+(include/se3conv_padded_rows.h; the same ops.BatchNormTrain / SkipDropPath / Linear, handed the cloud's row-count word and
+the frame count of the rows, ``_rows_of``): statistics, ``1/N`` and channel sums over the present rows alone -- bit for bit
+those of the trimmed tensors --, no absent row read (an absent row's batch id never indexes the drop-path gate), zeros
+written at the absent rows.  The invariant a network gets: every library pass leaves
 zeros at absent rows, the stock torch ops in between (Linear, GELU) are row-wise and keep them finite; the caller's part is
 finite level-0 input features and a loss that ignores absent rows (``pc.present_mask``), so that the gradient arriving
 there is zero.  There is no torch fallback on such a cloud: a configuration that would need one (non-fp32 input,
@@ -54,14 +55,19 @@ def _need_fused_on_padded_rows(who: str, t: torch.Tensor, ok: bool = True, limit
                                   "the torch formulation, which reads absent rows")
 
 
-def _row_layout(p_x, p_pc):
-    """``(frames, row batch ids)`` of a feature tensor on a padded cloud: one row per (point, frame) or one per point."""
+def _rows_of(p_x, p_pc):
+    """``(n_valid, n_frames, row batch ids)`` of a feature tensor on a cloud, as the row-wise ops take them.  An ordinary
+    cloud: no word, and rows of a cloud with frames carry the batch id of their point (batch_ids_considering_frames_).  A
+    flagged padded cloud: its word, and one row per (point, frame) or one per point."""
+    if not padded_rows(p_pc):
+        ids = getattr(p_pc, "batch_ids_considering_frames_", None)
+        return None, 1, ids if ids is not None else getattr(p_pc, "batch_ids_", None)
     n = int(p_pc.pts_.shape[0])
     f = int(getattr(p_pc, "n_frames_", 1))
     if p_x.shape[0] == n * f and f > 1:
-        return f, p_pc.batch_ids_considering_frames_
+        return p_pc.n_valid_, f, p_pc.batch_ids_considering_frames_
     if p_x.shape[0] == n:
-        return 1, p_pc.batch_ids_
+        return p_pc.n_valid_, 1, p_pc.batch_ids_
     raise ValueError(f"{p_x.shape[0]} feature rows on a padded cloud of {n} rows with {f} frame(s)")
 
 
@@ -74,21 +80,18 @@ class DropPathPC(torch.nn.Module):
         refuse_unflagged(p_pc, "DropPathPC")
         if self.drop_prob_ == 0.0 or not self.training:
             return p_x
-        keep = 1.0 - self.drop_prob_
-        if padded_rows(p_pc):
-            # through the skip kernel's gate path (x * 1 * gate + 0): an absent row's batch id never indexes the gate
+        padded = padded_rows(p_pc)
+        if padded:
             _need_fused_on_padded_rows("DropPathPC", p_x, self.drop_prob_ < 1.0, "drop_prob >= 1")
-            frames, ids = _row_layout(p_x, p_pc)
-            gate = torch.rand((_num_batches(p_pc),), dtype=p_x.dtype, device=p_x.device)
+        n_valid, frames, ids = _rows_of(p_x, p_pc)
+        # one uniform draw per batch element, keep where keep + u >= 1
+        keep = 1.0 - self.drop_prob_
+        u = torch.rand((_num_batches(p_pc),), dtype=p_x.dtype, device=p_x.device)
+        if padded:
+            # through the skip kernel's gate path (x * 1 * gate + 0): an absent row's batch id never indexes the gate
             one = torch.ones((1, p_x.shape[1]), dtype=p_x.dtype, device=p_x.device)
-            return ops.SkipDropPathPadded.apply(p_x, torch.zeros_like(p_x), one, gate, ids, keep, p_pc.n_valid_, frames)
-        # one uniform draw per batch element, keep where keep + u >= 1; rows of a cloud with frames carry the batch id
-        # of their point (batch_ids_considering_frames_)
-        gate = torch.floor(keep + torch.rand((_num_batches(p_pc),), dtype=p_x.dtype, device=p_x.device))
-        ids = getattr(p_pc, "batch_ids_considering_frames_", None)
-        if ids is None:
-            ids = p_pc.batch_ids_
-        return p_x.div(keep) * gate.index_select(0, ids.to(torch.int64)).reshape(-1, 1)
+            return ops.SkipDropPath.apply(p_x, torch.zeros_like(p_x), one, u, ids, keep, n_valid, frames)
+        return p_x.div(keep) * torch.floor(keep + u).index_select(0, ids.to(torch.int64)).reshape(-1, 1)
 
 
 class SkipConnection(torch.nn.Module):
@@ -105,27 +108,17 @@ class SkipConnection(torch.nn.Module):
             if p_x.shape != p_y.shape:
                 raise NotImplementedError("SkipConnection on padded feature rows (p_padded_rows): x and y of different shapes "
                                           "would need the torch formulation, which reads absent rows")
-            frames, ids = _row_layout(p_x, p_pc)
-            gate, keep = None, 0.0
-            if self.drop_path_.drop_prob_ != 0.0 and self.training:
-                keep = 1.0 - self.drop_path_.drop_prob_
-                gate = torch.rand((_num_batches(p_pc),), dtype=p_x.dtype, device=p_x.device)
-            return ops.SkipDropPathPadded.apply(p_x, p_y, self.gamma_, gate, ids if gate is not None else None, keep,
-                                                p_pc.n_valid_, frames)
         # drop_prob >= 1 (keep <= 0): the reference divides by zero (DropPathPC.py:45) -- the plain formulation reproduces
         # that instead of handing the kernel keep = 0, which it reads as "the gate is the factor itself"
-        if not _fused(p_x) or p_x.shape != p_y.shape or (self.training and self.drop_path_.drop_prob_ >= 1.0):
+        elif not _fused(p_x) or p_x.shape != p_y.shape or (self.training and self.drop_path_.drop_prob_ >= 1.0):
             return self.drop_path_(p_x * self.gamma_, p_pc) + p_y
-        gate = ids = None
-        keep = 0.0
+        n_valid, frames, ids = _rows_of(p_x, p_pc)
+        gate, keep = None, 0.0
         if self.drop_path_.drop_prob_ != 0.0 and self.training:
             keep = 1.0 - self.drop_path_.drop_prob_
             # the same draw as DropPathPC (one uniform per batch element); floor(keep + u) / keep is evaluated in the kernel
             gate = torch.rand((_num_batches(p_pc),), dtype=p_x.dtype, device=p_x.device)
-            ids = getattr(p_pc, "batch_ids_considering_frames_", None)
-            if ids is None:
-                ids = p_pc.batch_ids_
-        return ops.SkipDropPath.apply(p_x, p_y, self.gamma_, gate, ids, keep)
+        return ops.SkipDropPath.apply(p_x, p_y, self.gamma_, gate, ids if gate is not None else None, keep, n_valid, frames)
 
 
 class NormLayerPC(torch.nn.Module):
@@ -142,16 +135,14 @@ class BatchNormPC(NormLayerPC):
     def forward(self, p_x, p_pc):
         refuse_unflagged(p_pc, "BatchNormPC (its statistics need the present-row count)")
         bn = self.layer_
+        kernel_form = bn.training and bn.track_running_stats and bn.momentum is not None
         if padded_rows(p_pc) and (bn.training or not bn.track_running_stats):  # (batch statistics; eval mode is row-wise)
-            _need_fused_on_padded_rows("BatchNormPC", p_x, bn.training and bn.track_running_stats and bn.momentum is not None,
-                                       "training without running statistics (or with momentum None)")
-            frames, _ = _row_layout(p_x, p_pc)
-            return ops.BatchNormTrainPadded.apply(p_x, p_pc.n_valid_, frames, bn.weight, bn.bias, bn.running_mean,
-                                                  bn.running_var, bn.momentum, bn.eps, bn.num_batches_tracked)
-        if not (_fused(p_x) and bn.training and bn.track_running_stats and bn.momentum is not None):
+            _need_fused_on_padded_rows("BatchNormPC", p_x, kernel_form, "training without running statistics (or with momentum None)")
+        elif not (_fused(p_x) and kernel_form):
             return bn(p_x)
+        n_valid, frames, _ = _rows_of(p_x, p_pc)
         return ops.BatchNormTrain.apply(p_x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-                                        bn.num_batches_tracked)
+                                        bn.num_batches_tracked, n_valid, frames)
 
 
 class Block(PreProcessModule):
@@ -182,32 +173,24 @@ class ResNetFormer(Block):
 
     def forward(self, p_pc_in, p_in_features, p_neighborhood):
         refuse_unflagged(p_pc_in, "ResNetFormer")
-        if padded_rows(p_pc_in):
+        padded = padded_rows(p_pc_in)
+        n_valid = frames = None
+        if padded:
+            # the bias gradients of the linear layers are then summed by the library over the present rows (no memset node
+            # in a captured step); on an ordinary cloud they stay torch's column sum
             _need_fused_on_padded_rows("ResNetFormer", p_in_features)
-            frames, _ = _row_layout(p_in_features, p_pc_in)
-            word = p_pc_in.n_valid_
-            # the linear layers with their bias gradients summed by the library over the present rows (ops.LinearPadded: no
-            # memset node in a captured step)
-            x = self.spatial_conv_(p_pc_in=p_pc_in, p_pc_out=p_pc_in, p_in_features=self.norm_1_(p_in_features, p_pc_in),
-                                   p_neighborhood=p_neighborhood)
-            x = self.skip_path_1_(x, p_in_features, p_pc_in)
-            h = ops.BiasGelu.apply(ops.Linear.apply(self.norm_2_(x, p_pc_in), self.linear_1_.weight, None), self.linear_1_.bias)
-            y = ops.LinearPadded.apply(h, self.linear_2_.weight, self.linear_2_.bias, word, frames)
-            skip = x
-            if self.feat_input_size_ != self.feat_output_size_:
-                skip = ops.LinearPadded.apply(x, self.skip_conv_.weight, self.skip_conv_.bias, word, frames)
-            return self.skip_path_2_(y, skip, p_pc_in)
+            n_valid, frames, _ = _rows_of(p_in_features, p_pc_in)
         x = self.spatial_conv_(p_pc_in=p_pc_in, p_pc_out=p_pc_in, p_in_features=self.norm_1_(p_in_features, p_pc_in),
                                p_neighborhood=p_neighborhood)
         x = self.skip_path_1_(x, p_in_features, p_pc_in)
         h = self.norm_2_(x, p_pc_in)
-        if _fused(h):
+        if padded or _fused(h):
             # bias + GELU in one pass behind a bias-free GEMM; the linear layers' weight gradients on the row-split GEMM
             h = ops.BiasGelu.apply(ops.Linear.apply(h, self.linear_1_.weight, None), self.linear_1_.bias)
-            y = ops.Linear.apply(h, self.linear_2_.weight, self.linear_2_.bias)
+            y = ops.Linear.apply(h, self.linear_2_.weight, self.linear_2_.bias, n_valid, frames)
             skip = x
             if self.feat_input_size_ != self.feat_output_size_:
-                skip = ops.Linear.apply(x, self.skip_conv_.weight, self.skip_conv_.bias)
+                skip = ops.Linear.apply(x, self.skip_conv_.weight, self.skip_conv_.bias, n_valid, frames)
         else:
             h = self.act_func_(self.linear_1_(h))
             y = self.linear_2_(h)

@@ -92,6 +92,48 @@ def _valid_word(n_valid, device, who: str) -> C.c_void_p:
     return p
 
 
+# Row-wise passes on padded clouds (include/se3conv_padded_rows.h).  A feature tensor padded like its cloud is
+# [n_rows * frames, C], of which the first clamp(*n_valid) * frames rows exist.  A pass that is handed the cloud's row-count
+# word never reads an absent row and leaves zeros there; it takes the tensor as it is (float32, contiguous rows, on the GPU),
+# and nothing is a torch fallback.  Without a word every row exists, and the same pass converts what it is given.
+def _padded_rows(t: torch.Tensor, frames: int, who: str) -> Tuple[torch.Tensor, int]:
+    """``t`` as the [n_rows * frames, C] float32 matrix the library reads, and ``n_rows``."""
+    t2 = _as(t, torch.float32)
+    if t2.dim() != 2 or not t2.is_cuda:
+        raise ValueError(f"{who}: expected [rows, C] features on the GPU (the HIP path has no CPU fallback)")
+    if int(frames) < 1 or t2.shape[0] % int(frames):
+        raise ValueError(f"{who}: {t2.shape[0]} rows are not a multiple of the frame count {frames}")
+    return t2, t2.shape[0] // int(frames)
+
+
+def _feature_rows(t: torch.Tensor, n_valid, frames: int, who: str) -> torch.Tensor:
+    """``t`` as the [rows, C] float32 matrix of a glue pass; with a row-count word, the feature rows of a padded cloud under
+    the checks of ``_padded_rows`` (on the GPU, whole points)."""
+    if n_valid is not None:
+        return _padded_rows(t, frames, who)[0]
+    t2 = _as(t, torch.float32)
+    if t2.dim() != 2:
+        raise ValueError(f"{who}: expected [rows, C] features")
+    return t2
+
+
+def _row_pass(name: str, n_valid):
+    """The entry point of a row-wise pass and its name: ``name`` (include/se3conv.h) without a row-count word, its ``_padded``
+    form (include/se3conv_padded_rows.h) with one.  The library has one ``*_impl`` behind both, and a padded call with a null
+    word launches what the ordinary call does -- but only its host side refuses ``n_rows * frames >= 2^31``, and the ordinary
+    entry points are what callers without padded clouds are tested on, so such callers keep them."""
+    if n_valid is not None:
+        name += "_padded"
+    return getattr(_lib.load(), name), name
+
+
+def _glue_rows(x2: torch.Tensor, n_valid, frames: int, who: str) -> tuple:
+    """The arguments of a glue pass that say which rows of ``x2`` exist: ``rows`` (every one), or ``n_rows, frames, n_valid``."""
+    if n_valid is None:
+        return (x2.shape[0],)
+    return (x2.shape[0] // frames, frames, _valid_word(n_valid, x2.device, who))
+
+
 def _padded_cloud(pts, batch_ids, who: str):
     """A padded cloud is taken as it is -- float32 [N,3] points, int32 [N] batch ids, contiguous: a conversion would read
     the absent rows (and be a launch of its own)."""
@@ -544,11 +586,23 @@ POOL_MODES = {"avg": 0, "max": 1, "min": 2, "sum": 3}
 class GridCells:
     """Result of one grid sub-sampling step (``se3_grid_subsample``): the cell of every point (what
     ``torch.unique(keys, return_inverse=True)`` returns in Grid.py:45), the points grouped by cell, the cell sizes
-    as inclusive end offsets, and the next level's points / batch ids (PointHierarchy.py:46-49)."""
+    as inclusive end offsets, and the next level's points / batch ids (PointHierarchy.py:46-49).  ``padded``: the level of
+    a padded hierarchy (``of_level``), whose absent points carry the cell id -1."""
 
     def __init__(self, cell_ids, sorted_ids, cell_ends, n_cells, pts, batch_ids):
         self.cell_ids, self.sorted_ids, self.cell_ends, self.n_cells = cell_ids, sorted_ids, cell_ends, n_cells
         self.pts, self.batch_ids = pts, batch_ids
+        self.padded = False
+
+    @classmethod
+    def of_level(cls, level) -> "GridCells":
+        """One level dict of ``BoundedLevels.levels`` as it stands, nothing read back: the capacity-sized tensors and ALL
+        ``capacity`` cells.  ``cell_ends`` behind the kept cells holds the present-row count, so those segments are empty --
+        pooling writes 0 in ``out`` and -1 in ``arg`` there and reads only rows that kept cells list."""
+        cells = cls(level["cell_ids"], level["sorted_ids"], level["cell_ends"], level["cell_ends"].shape[0], level["pts"],
+                    level["batch_ids"])
+        cells.padded = True
+        return cells
 
 
 def grid_subsample(pts, batch_ids, cell_size: float, n_batches: Optional[int] = None) -> GridCells:
@@ -703,6 +757,8 @@ def _rows2d(t):
 def _segment_pool(cells: GridCells, x2, mode: int, want_arg: bool):
     lib = _lib.load()
     c = x2.shape[1]
+    if x2.shape[0] != cells.cell_ids.shape[0]:
+        raise ValueError(f"pooling {x2.shape[0]} rows through a level with {cells.cell_ids.shape[0]} input rows")
     out = _empty((cells.n_cells, c), dtype=torch.float32, device=x2.device)
     arg = _empty((cells.n_cells, c), dtype=torch.int32, device=x2.device) if want_arg else None
     _lib.check(lib.se3_segment_pool(_ptr(x2, torch.float32, "src"), _ptr(cells.sorted_ids, torch.int32, "sorted_ids"),
@@ -715,10 +771,15 @@ def _segment_pool(cells: GridCells, x2, mode: int, want_arg: bool):
 def _segment_unpool(cells: GridCells, v2, arg, mode: int):
     lib = _lib.load()
     n, c = cells.cell_ids.shape[0], v2.shape[1]
+    if v2.shape[0] != cells.n_cells:
+        raise ValueError(f"up-sampling {v2.shape[0]} rows through a level of {cells.n_cells} cells")
+    # (two instantiations of one kernel: the padded one writes a zero row where the cell id is negative -- an absent point
+    # or one of a dropped cell)
+    name = "se3_segment_unpool_padded" if cells.padded else "se3_segment_unpool"
     out = _empty((n, c), dtype=torch.float32, device=v2.device)
-    _lib.check(lib.se3_segment_unpool(_ptr(v2, torch.float32, "cell_vals"), _ptr(cells.cell_ids, torch.int32, "cell_ids"),
-                                      _ptr(cells.cell_ends, torch.int32, "cell_ends"), _ptr(arg, torch.int32, "arg"),
-                                      n, c, mode, _ptr(out, torch.float32, "out"), _stream(v2.device)), "se3_segment_unpool")
+    _lib.check(getattr(lib, name)(_ptr(v2, torch.float32, "cell_vals"), _ptr(cells.cell_ids, torch.int32, "cell_ids"),
+                                  _ptr(cells.cell_ends, torch.int32, "cell_ends"), _ptr(arg, torch.int32, "arg"),
+                                  n, c, mode, _ptr(out, torch.float32, "out"), _stream(v2.device)), name)
     return out
 
 
@@ -800,7 +861,9 @@ class RowsScatter(torch.autograd.Function):
 
 
 class GridPool(torch.autograd.Function):
-    """``pool_tensor`` of one level step (GridSubSample.py:63-77): rows of level l -> rows of level l+1."""
+    """``pool_tensor`` of one level step (GridSubSample.py:63-77): rows of level l -> rows of level l+1.  Through padded
+    cells (``GridCells.of_level``): [n_in, ...] -> [capacity, ...] with zeros behind the kept cells, and a gradient of zero
+    rows at absent points and dropped cells."""
 
     @staticmethod
     def forward(ctx, x, cells, method):
@@ -818,7 +881,8 @@ class GridPool(torch.autograd.Function):
 
 class GridUpsample(torch.autograd.Function):
     """``upsample_tensor`` (GridSubSample.py:93: ``p_tensor[cell_ids]``); the gradient is a segment sum in fixed order
-    instead of the atomics of an index_add."""
+    instead of the atomics of an index_add.  Through padded cells the rows of absent points and of dropped cells get zeros,
+    and the gradient is the segment sum over all ``capacity`` cells."""
 
     @staticmethod
     def forward(ctx, x, cells):
@@ -834,32 +898,38 @@ class GridUpsample(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------ frame pooling (row f-3)
 class FramePool(torch.autograd.Function):
-    """``PointcloudRotEquiv.feature_pooling`` (pc/PointcloudRotEquiv.py:224-251): [N*F, C] -> [N, C]."""
+    """``PointcloudRotEquiv.feature_pooling`` (pc/PointcloudRotEquiv.py:224-251): [N*F, C] -> [N, C].  ``n_valid``: the
+    row-count word of a padded cloud -- ``x`` is then taken as it is ([n_rows * F, C] float32 on the GPU), absent points
+    are not read and get zeros both ways."""
 
     @staticmethod
-    def forward(ctx, x, n_frames, method):
-        lib = _lib.load()
+    def forward(ctx, x, n_frames, method, n_valid=None):
         mode = POOL_MODES[method]
-        x2 = _rows2d(_as(x, torch.float32))
-        if x2.shape[0] % n_frames:
-            raise ValueError("feature_pooling: rows are not a multiple of the frame count")
-        n, c = x2.shape[0] // n_frames, x2.shape[1]
-        out = _empty((n, c), dtype=torch.float32, device=x2.device)
-        arg = _empty((n, c), dtype=torch.int32, device=x2.device) if mode in (1, 2) else None
-        _lib.check(lib.se3_frame_pool(_ptr(x2, torch.float32, "x"), n, n_frames, c, mode, _ptr(out, torch.float32, "out"),
-                                      _ptr(arg, torch.int32, "arg"), _stream(x2.device)), "se3_frame_pool")
-        ctx.mode, ctx.arg, ctx.f, ctx.shape = mode, arg, n_frames, x.shape
+        if n_valid is not None:
+            x2 = _padded_rows(x, n_frames, "FramePool")[0]
+        else:
+            x2 = _rows2d(_as(x, torch.float32))
+            if x2.shape[0] % n_frames:
+                raise ValueError("feature_pooling: rows are not a multiple of the frame count")
+        n, c, dev = x2.shape[0] // n_frames, x2.shape[1], x2.device
+        out = _empty((n, c), dtype=torch.float32, device=dev)
+        arg = _empty((n, c), dtype=torch.int32, device=dev) if mode in (1, 2) else None
+        ctx.word = (_valid_word(n_valid, dev, "FramePool"),) if n_valid is not None else ()
+        fn, name = _row_pass("se3_frame_pool", n_valid)
+        _lib.check(fn(_ptr(x2, torch.float32, "x"), n, int(n_frames), *ctx.word, c, mode, _ptr(out, torch.float32, "out"),
+                      _ptr(arg, torch.int32, "arg"), _stream(dev)), name)
+        ctx.mode, ctx.arg, ctx.f, ctx.shape, ctx.n_valid = mode, arg, int(n_frames), x.shape, n_valid
         return out.reshape((n,) + tuple(x.shape[1:]))
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         g2 = _rows2d(_as(g, torch.float32))
         n, c = g2.shape
         gx = _empty((n * ctx.f, c), dtype=torch.float32, device=g2.device)
-        _lib.check(lib.se3_frame_unpool(_ptr(g2, torch.float32, "grad_out"), _ptr(ctx.arg, torch.int32, "arg"), n, ctx.f, c,
-                                        ctx.mode, _ptr(gx, torch.float32, "grad_x"), _stream(g2.device)), "se3_frame_unpool")
-        return gx.reshape(ctx.shape), None, None
+        fn, name = _row_pass("se3_frame_unpool", ctx.n_valid)
+        _lib.check(fn(_ptr(g2, torch.float32, "grad_out"), _ptr(ctx.arg, torch.int32, "arg"), n, ctx.f, *ctx.word, c,
+                      ctx.mode, _ptr(gx, torch.float32, "grad_x"), _stream(g2.device)), name)
+        return gx.reshape(ctx.shape), None, None, None
 
 
 # ------------------------------------------------------------------------------- frames (row f-1)
@@ -1397,101 +1467,103 @@ def _glue_ws(c: int, dev) -> torch.Tensor:
 
 class BatchNormTrain(torch.autograd.Function):
     """Training-mode ``torch.nn.BatchNorm1d`` on ``[rows, C]`` (layers/BatchNormPC.py:22-32): channel sums in fp64 and
-    a fixed order, running statistics updated in place, 3 launches forward and 3 backward."""
+    a fixed order, running statistics updated in place, 3 launches forward and 3 backward.  ``n_valid``, ``n_frames``: the
+    feature rows of a padded cloud ([n_rows * n_frames, C], taken as they are) -- statistics and gradient over the present
+    rows alone, bit for bit those of the call on the trimmed tensor, zeros at the absent rows."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, num_batches_tracked=None):
-        lib = _lib.load()
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, num_batches_tracked=None, n_valid=None,
+                n_frames=1):
         f32 = torch.float32
-        x2 = _as(x, f32)
-        if x2.dim() != 2:
-            raise ValueError("BatchNormTrain: expected [rows, C] features")
-        rows, c = x2.shape
-        dev = x2.device
+        x2 = _feature_rows(x, n_valid, n_frames, "BatchNormTrain")
+        c, dev = x2.shape[1], x2.device
         y = _empty_like(x2)
         mean = _empty(c, dtype=f32, device=dev)
         invstd = _empty(c, dtype=f32, device=dev)
         w = _as(weight, f32) if weight is not None else None
         b = _as(bias, f32) if bias is not None else None
         ws = _glue_ws(c, dev)
-        _lib.check(lib.se3_bn_fwd(_ptr(x2, f32, "x"), _ptr(w, f32, "weight", dev), _ptr(b, f32, "bias", dev), rows, c,
-                                  float(eps), float(momentum), _ptr(running_mean, f32, "running_mean", dev),
-                                  _ptr(running_var, f32, "running_var", dev),
-                                  _ptr(num_batches_tracked, torch.int64, "num_batches_tracked", dev), _ptr(y, f32, "y"),
-                                  _ptr(mean, f32, "mean"),
-                                  _ptr(invstd, f32, "invstd"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)),
-                   "se3_bn_fwd")
+        fn, name = _row_pass("se3_bn_fwd", n_valid)
+        _lib.check(fn(_ptr(x2, f32, "x"), _ptr(w, f32, "weight", dev), _ptr(b, f32, "bias", dev),
+                      *_glue_rows(x2, n_valid, int(n_frames), "BatchNormTrain"), c, float(eps), float(momentum),
+                      _ptr(running_mean, f32, "running_mean", dev), _ptr(running_var, f32, "running_var", dev),
+                      _ptr(num_batches_tracked, torch.int64, "num_batches_tracked", dev), _ptr(y, f32, "y"),
+                      _ptr(mean, f32, "mean"), _ptr(invstd, f32, "invstd"), C.c_void_p(ws.data_ptr()), ws.numel(),
+                      _stream(dev)), name)
         ctx.save_for_backward(x2, w if w is not None else torch.empty(0, device=dev), mean, invstd)
-        ctx.has_w = w is not None
+        ctx.has_w, ctx.n_valid, ctx.frames = w is not None, n_valid, int(n_frames)
         ctx.mark_non_differentiable(*[t for t in (running_mean, running_var, num_batches_tracked) if t is not None])
         return y
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         f32 = torch.float32
         x2, w, mean, invstd = ctx.saved_tensors
         g2 = _as(g, f32)
-        rows, c = x2.shape
-        dev = x2.device
+        c, dev = x2.shape[1], x2.device
         dx = _empty_like(x2)
         dgamma = _empty(c, dtype=f32, device=dev)
         dbeta = _empty(c, dtype=f32, device=dev)
         ws = _glue_ws(c, dev)
-        _lib.check(lib.se3_bn_bwd(_ptr(g2, f32, "dy", dev), _ptr(x2, f32, "x"), _ptr(mean, f32, "mean"),
-                                  _ptr(invstd, f32, "invstd"), _ptr(w if ctx.has_w else None, f32, "weight"), rows, c,
-                                  _ptr(dx, f32, "dx"), _ptr(dgamma, f32, "dgamma"), _ptr(dbeta, f32, "dbeta"),
-                                  C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_bn_bwd")
+        fn, name = _row_pass("se3_bn_bwd", ctx.n_valid)
+        _lib.check(fn(_ptr(g2, f32, "dy", dev), _ptr(x2, f32, "x"), _ptr(mean, f32, "mean"), _ptr(invstd, f32, "invstd"),
+                      _ptr(w if ctx.has_w else None, f32, "weight"), *_glue_rows(x2, ctx.n_valid, ctx.frames, "BatchNormTrain"),
+                      c, _ptr(dx, f32, "dx"), _ptr(dgamma, f32, "dgamma"), _ptr(dbeta, f32, "dbeta"),
+                      C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), name)
         ng = ctx.needs_input_grad
-        return (dx if ng[0] else None, dgamma if ng[1] else None, dbeta if ng[2] else None, None, None, None, None, None)
+        return (dx if ng[0] else None, dgamma if ng[1] else None, dbeta if ng[2] else None) + (None,) * 7
 
 
 class SkipDropPath(torch.autograd.Function):
     """``drop_path(x * gamma_) + y`` of layers/SkipConnection.py with the per-batch gate of layers/DropPathPC.py:30-46
     (``gate [B]`` holds keep-mask / keep_prob -- or, with ``gate_keep = keep_prob > 0``, the uniform draws themselves, the
     kernel then evaluates floor(keep + u) / keep; ``row_batch [rows]`` int32 maps rows to batch elements; both None: no drop
-    path) -- one launch forward, two backward."""
+    path) -- one launch forward, two backward.  ``n_valid``, ``n_frames``: the feature rows of a padded cloud
+    ([n_rows * n_frames, C], taken as they are, ``row_batch`` too) -- the batch id of an absent row is never used to index
+    the gate, and the absent rows get zeros."""
 
     @staticmethod
-    def forward(ctx, x, y, gamma, gate, row_batch, gate_keep=0.0):
-        lib = _lib.load()
+    def forward(ctx, x, y, gamma, gate, row_batch, gate_keep=0.0, n_valid=None, n_frames=1):
         f32, i32 = torch.float32, torch.int32
-        x2, y2 = _as(x, f32), _as(y, f32)
-        if x2.shape != y2.shape or x2.dim() != 2:
+        x2, y2 = _feature_rows(x, n_valid, n_frames, "SkipDropPath"), _as(y, f32)
+        if x2.shape != y2.shape:
             raise ValueError("SkipDropPath: x and y must be [rows, C] of the same shape")
-        rows, c = x2.shape
-        dev = x2.device
+        c, dev = x2.shape[1], x2.device
         ga = _as(gamma, f32).reshape(-1)
         gt = _as(gate, f32) if gate is not None else None
-        rb = _as(row_batch, i32) if gate is not None else None
-        if gt is not None and rb.shape[0] != rows:
+        rb = None
+        if gate is not None:
+            rb = row_batch if n_valid is not None else _as(row_batch, i32)
+        if gt is not None and (rb is None or rb.shape[0] != x2.shape[0]):
             raise ValueError("SkipDropPath: one batch id per row expected")
         out = _empty_like(x2)
-        _lib.check(lib.se3_skip_fwd(_ptr(x2, f32, "x"), _ptr(y2, f32, "y", dev), _ptr(ga, f32, "gamma", dev),
-                                    _ptr(gt, f32, "gate", dev), float(gate_keep), _ptr(rb, i32, "row_batch", dev), rows, c,
-                                    _ptr(out, f32, "out"), _stream(dev)), "se3_skip_fwd")
+        fn, name = _row_pass("se3_skip_fwd", n_valid)
+        _lib.check(fn(_ptr(x2, f32, "x"), _ptr(y2, f32, "y", dev), _ptr(ga, f32, "gamma", dev), _ptr(gt, f32, "gate", dev),
+                      float(gate_keep), _ptr(rb, i32, "row_batch", dev), *_glue_rows(x2, n_valid, int(n_frames), "SkipDropPath"),
+                      c, _ptr(out, f32, "out"), _stream(dev)), name)
         ctx.save_for_backward(x2, ga, gt if gt is not None else torch.empty(0, device=dev),
                               rb if rb is not None else torch.empty(0, dtype=i32, device=dev))
         ctx.gated, ctx.gamma_shape, ctx.gate_keep = gt is not None, gamma.shape, float(gate_keep)
+        ctx.n_valid, ctx.frames = n_valid, int(n_frames)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         f32, i32 = torch.float32, torch.int32
         x2, ga, gt, rb = ctx.saved_tensors
         g2 = _as(g, f32)
-        rows, c = x2.shape
-        dev = x2.device
+        c, dev = x2.shape[1], x2.device
         ng = ctx.needs_input_grad
         dx = _empty_like(x2) if ng[0] else None
         dgamma = _empty(c, dtype=f32, device=dev)
         ws = _glue_ws(c, dev)
-        _lib.check(lib.se3_skip_bwd(_ptr(g2, f32, "g", dev), _ptr(x2, f32, "x"), _ptr(ga, f32, "gamma"),
-                                    _ptr(gt if ctx.gated else None, f32, "gate"), ctx.gate_keep,
-                                    _ptr(rb if ctx.gated else None, i32, "row_batch"), rows, c, _ptr(dx, f32, "dx"), _ptr(dgamma, f32, "dgamma"), C.c_void_p(ws.data_ptr()),
-                                    ws.numel(), _stream(dev)), "se3_skip_bwd")
-        return dx, (g2 if ng[1] else None), (dgamma.reshape(ctx.gamma_shape) if ng[2] else None), None, None, None
+        fn, name = _row_pass("se3_skip_bwd", ctx.n_valid)
+        _lib.check(fn(_ptr(g2, f32, "g", dev), _ptr(x2, f32, "x"), _ptr(ga, f32, "gamma"),
+                      _ptr(gt if ctx.gated else None, f32, "gate"), ctx.gate_keep,
+                      _ptr(rb if ctx.gated else None, i32, "row_batch"), *_glue_rows(x2, ctx.n_valid, ctx.frames, "SkipDropPath"),
+                      c, _ptr(dx, f32, "dx"), _ptr(dgamma, f32, "dgamma"), C.c_void_p(ws.data_ptr()), ws.numel(),
+                      _stream(dev)), name)
+        return (dx, (g2 if ng[1] else None), (dgamma.reshape(ctx.gamma_shape) if ng[2] else None)) + (None,) * 5
 
 
 class BiasGelu(torch.autograd.Function):
@@ -1535,12 +1607,19 @@ class Linear(torch.autograd.Function):
     forward and the input gradient are plain BLAS GEMMs (fine as they are, 20-35 us at 131 k rows), the weight gradient --
     a reduction over every row of the cloud into a ``[n_out, n_in]`` matrix -- is what the generic heuristics run on a
     handful of workgroups (0.28-0.36 ms at 131 k rows against ~0.03 here).  The block's ``torch.nn.Linear`` layers
-    (layers/ResNetFormer.py:42-49, 80-86)."""
+    (layers/ResNetFormer.py:42-49, 80-86).
+
+    ``n_frames`` (an integer): the bias gradient is ``channel_sums`` over the present rows (``n_valid``; None: every row)
+    instead of ``g.sum(0)`` -- on the feature rows of a padded cloud, and wherever a captured step shall hold no memset node.
+    The rest is the same there: the GEMMs are row-wise (absent rows stay finite: they hold the bias), and the weight
+    gradient runs over all rows, the gradient rows of absent points being zero (pc.py: the invariant)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, n_valid=None, n_frames=None):
+        if n_valid is not None and n_frames is None:
+            raise ValueError("Linear: a row-count word needs the frame count of the rows")
         ctx.save_for_backward(x, weight)
-        ctx.has_b = bias is not None
+        ctx.has_b, ctx.n_valid, ctx.frames = bias is not None, n_valid, n_frames
         return torch.nn.functional.linear(x, weight, bias)
 
     @staticmethod
@@ -1563,218 +1642,11 @@ class Linear(torch.autograd.Function):
                                             _ptr(gw, f32, "grad_w"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)),
                        "se3_linear_wgrad")
         if ctx.has_b and ctx.needs_input_grad[2]:
-            gb = g2.sum(0)
-        return gx, gw, gb
+            gb = g2.sum(0) if ctx.frames is None else channel_sums(g2, ctx.n_valid, ctx.frames)
+        return gx, gw, gb, None, None
 
 
-# ---------------------------------------------- row-wise passes on padded clouds (include/se3conv_padded_rows.h)
-# Feature tensors padded like their cloud: [n_rows * frames, C] of which the first clamp(*n_valid) * frames rows exist.  Every
-# function below takes the cloud's row-count word, never reads an absent row and leaves zeros there; the tensors are taken as
-# they are (float32, contiguous rows): nothing converts, and nothing is a torch fallback.
-def _padded_rows(t: torch.Tensor, frames: int, who: str) -> Tuple[torch.Tensor, int]:
-    """``t`` as the [n_rows * frames, C] float32 matrix the library reads, and ``n_rows``."""
-    t2 = _as(t, torch.float32)
-    if t2.dim() != 2 or not t2.is_cuda:
-        raise ValueError(f"{who}: expected [rows, C] features on the GPU (the HIP path has no CPU fallback)")
-    if int(frames) < 1 or t2.shape[0] % int(frames):
-        raise ValueError(f"{who}: {t2.shape[0]} rows are not a multiple of the frame count {frames}")
-    return t2, t2.shape[0] // int(frames)
-
-
-class BatchNormTrainPadded(torch.autograd.Function):
-    """``BatchNormTrain`` on the feature rows of a padded cloud (``se3_bn_fwd_padded`` / ``se3_bn_bwd_padded``): statistics
-    and gradient over the present rows alone, bit for bit those of ``BatchNormTrain`` on the trimmed tensor."""
-
-    @staticmethod
-    def forward(ctx, x, n_valid, n_frames, weight, bias, running_mean, running_var, momentum, eps, num_batches_tracked=None):
-        lib = _lib.load()
-        f32 = torch.float32
-        x2, n_rows = _padded_rows(x, n_frames, "BatchNormTrainPadded")
-        c, dev = x2.shape[1], x2.device
-        y = _empty_like(x2)
-        mean = _empty(c, dtype=f32, device=dev)
-        invstd = _empty(c, dtype=f32, device=dev)
-        w = _as(weight, f32) if weight is not None else None
-        b = _as(bias, f32) if bias is not None else None
-        ws = _glue_ws(c, dev)
-        _lib.check(lib.se3_bn_fwd_padded(
-            _ptr(x2, f32, "x"), _ptr(w, f32, "weight", dev), _ptr(b, f32, "bias", dev), n_rows, int(n_frames),
-            _valid_word(n_valid, dev, "BatchNormTrainPadded"), c, float(eps), float(momentum),
-            _ptr(running_mean, f32, "running_mean", dev), _ptr(running_var, f32, "running_var", dev),
-            _ptr(num_batches_tracked, torch.int64, "num_batches_tracked", dev), _ptr(y, f32, "y"), _ptr(mean, f32, "mean"),
-            _ptr(invstd, f32, "invstd"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_bn_fwd_padded")
-        ctx.save_for_backward(x2, w if w is not None else torch.empty(0, device=dev), mean, invstd)
-        ctx.has_w, ctx.n_valid, ctx.frames = w is not None, n_valid, int(n_frames)
-        ctx.mark_non_differentiable(*[t for t in (running_mean, running_var, num_batches_tracked) if t is not None])
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        f32 = torch.float32
-        x2, w, mean, invstd = ctx.saved_tensors
-        g2 = _as(g, f32)
-        c, dev = x2.shape[1], x2.device
-        dx = _empty_like(x2)
-        dgamma = _empty(c, dtype=f32, device=dev)
-        dbeta = _empty(c, dtype=f32, device=dev)
-        ws = _glue_ws(c, dev)
-        _lib.check(lib.se3_bn_bwd_padded(
-            _ptr(g2, f32, "dy", dev), _ptr(x2, f32, "x"), _ptr(mean, f32, "mean"), _ptr(invstd, f32, "invstd"),
-            _ptr(w if ctx.has_w else None, f32, "weight"), x2.shape[0] // ctx.frames, ctx.frames,
-            _valid_word(ctx.n_valid, dev, "BatchNormTrainPadded"), c, _ptr(dx, f32, "dx"), _ptr(dgamma, f32, "dgamma"),
-            _ptr(dbeta, f32, "dbeta"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_bn_bwd_padded")
-        ng = ctx.needs_input_grad
-        return (dx if ng[0] else None, None, None, dgamma if ng[3] else None, dbeta if ng[4] else None, None, None, None,
-                None, None)
-
-
-class SkipDropPathPadded(torch.autograd.Function):
-    """``SkipDropPath`` on the feature rows of a padded cloud (``se3_skip_fwd_padded`` / ``se3_skip_bwd_padded``): the batch
-    id of an absent row is never used to index the gate."""
-
-    @staticmethod
-    def forward(ctx, x, y, gamma, gate, row_batch, gate_keep, n_valid, n_frames):
-        lib = _lib.load()
-        f32, i32 = torch.float32, torch.int32
-        x2, n_rows = _padded_rows(x, n_frames, "SkipDropPathPadded")
-        y2 = _as(y, f32)
-        if x2.shape != y2.shape:
-            raise ValueError("SkipDropPathPadded: x and y must be [rows, C] of the same shape")
-        c, dev = x2.shape[1], x2.device
-        ga = _as(gamma, f32).reshape(-1)
-        gt = _as(gate, f32) if gate is not None else None
-        rb = row_batch if gate is not None else None
-        if gt is not None and (rb is None or rb.shape[0] != x2.shape[0]):
-            raise ValueError("SkipDropPathPadded: one batch id per row expected")
-        out = _empty_like(x2)
-        _lib.check(lib.se3_skip_fwd_padded(
-            _ptr(x2, f32, "x"), _ptr(y2, f32, "y", dev), _ptr(ga, f32, "gamma", dev), _ptr(gt, f32, "gate", dev),
-            float(gate_keep), _ptr(rb, i32, "row_batch", dev), n_rows, int(n_frames),
-            _valid_word(n_valid, dev, "SkipDropPathPadded"), c, _ptr(out, f32, "out"), _stream(dev)), "se3_skip_fwd_padded")
-        ctx.save_for_backward(x2, ga, gt if gt is not None else torch.empty(0, device=dev),
-                              rb if rb is not None else torch.empty(0, dtype=i32, device=dev))
-        ctx.gated, ctx.gamma_shape, ctx.gate_keep = gt is not None, gamma.shape, float(gate_keep)
-        ctx.n_valid, ctx.frames = n_valid, int(n_frames)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        f32, i32 = torch.float32, torch.int32
-        x2, ga, gt, rb = ctx.saved_tensors
-        g2 = _as(g, f32)
-        c, dev = x2.shape[1], x2.device
-        ng = ctx.needs_input_grad
-        dx = _empty_like(x2) if ng[0] else None
-        dgamma = _empty(c, dtype=f32, device=dev)
-        ws = _glue_ws(c, dev)
-        _lib.check(lib.se3_skip_bwd_padded(
-            _ptr(g2, f32, "g", dev), _ptr(x2, f32, "x"), _ptr(ga, f32, "gamma"), _ptr(gt if ctx.gated else None, f32, "gate"),
-            ctx.gate_keep, _ptr(rb if ctx.gated else None, i32, "row_batch"), x2.shape[0] // ctx.frames, ctx.frames,
-            _valid_word(ctx.n_valid, dev, "SkipDropPathPadded"), c, _ptr(dx, f32, "dx"), _ptr(dgamma, f32, "dgamma"),
-            C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_skip_bwd_padded")
-        return (dx, (g2 if ng[1] else None), (dgamma.reshape(ctx.gamma_shape) if ng[2] else None), None, None, None, None,
-                None)
-
-
-class FramePoolPadded(torch.autograd.Function):
-    """``FramePool`` on a padded cloud (``se3_frame_pool_padded`` / ``se3_frame_unpool_padded``): [n_rows * F, C] ->
-    [n_rows, C], absent points zero."""
-
-    @staticmethod
-    def forward(ctx, x, n_frames, method, n_valid):
-        lib = _lib.load()
-        mode = POOL_MODES[method]
-        x2, n = _padded_rows(x, n_frames, "FramePoolPadded")
-        c, dev = x2.shape[1], x2.device
-        out = _empty((n, c), dtype=torch.float32, device=dev)
-        arg = _empty((n, c), dtype=torch.int32, device=dev) if mode in (1, 2) else None
-        _lib.check(lib.se3_frame_pool_padded(_ptr(x2, torch.float32, "x"), n, int(n_frames),
-                                             _valid_word(n_valid, dev, "FramePoolPadded"), c, mode,
-                                             _ptr(out, torch.float32, "out"), _ptr(arg, torch.int32, "arg"), _stream(dev)),
-                   "se3_frame_pool_padded")
-        ctx.mode, ctx.arg, ctx.f, ctx.n_valid = mode, arg, int(n_frames), n_valid
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        g2 = _as(g, torch.float32)
-        n, c = g2.shape
-        dev = g2.device
-        gx = _empty((n * ctx.f, c), dtype=torch.float32, device=dev)
-        _lib.check(lib.se3_frame_unpool_padded(_ptr(g2, torch.float32, "grad_out"), _ptr(ctx.arg, torch.int32, "arg"), n, ctx.f,
-                                               _valid_word(ctx.n_valid, dev, "FramePoolPadded"), c, ctx.mode,
-                                               _ptr(gx, torch.float32, "grad_x"), _stream(dev)), "se3_frame_unpool_padded")
-        return gx, None, None, None
-
-
-def _level_pool(level, x2, mode: int, want_arg: bool):
-    """``se3_segment_pool`` over ALL ``capacity`` cells of a level of ``grid_levels_bounded``: ``cell_ends`` behind the kept
-    cells holds the present-row count, so those segments are empty -- 0 in ``out``, -1 in ``arg`` -- and only rows that kept
-    cells list are read."""
-    lib = _lib.load()
-    cap, c = level["cell_ends"].shape[0], x2.shape[1]
-    if x2.shape[0] != level["cell_ids"].shape[0]:
-        raise ValueError(f"pooling {x2.shape[0]} rows through a level with {level['cell_ids'].shape[0]} input rows")
-    out = _empty((cap, c), dtype=torch.float32, device=x2.device)
-    arg = _empty((cap, c), dtype=torch.int32, device=x2.device) if want_arg else None
-    _lib.check(lib.se3_segment_pool(_ptr(x2, torch.float32, "src"), _ptr(level["sorted_ids"], torch.int32, "sorted_ids"),
-                                    _ptr(level["cell_ends"], torch.int32, "cell_ends"), cap, c, mode,
-                                    _ptr(out, torch.float32, "out"), _ptr(arg, torch.int32, "arg"), _stream(x2.device)),
-               "se3_segment_pool")
-    return out, arg
-
-
-def _level_unpool(level, v2, arg, mode: int):
-    lib = _lib.load()
-    n, c = level["cell_ids"].shape[0], v2.shape[1]
-    if v2.shape[0] != level["cell_ends"].shape[0]:
-        raise ValueError(f"up-sampling {v2.shape[0]} rows through a level of capacity {level['cell_ends'].shape[0]}")
-    out = _empty((n, c), dtype=torch.float32, device=v2.device)
-    _lib.check(lib.se3_segment_unpool_padded(
-        _ptr(v2, torch.float32, "cell_vals"), _ptr(level["cell_ids"], torch.int32, "cell_ids"),
-        _ptr(level["cell_ends"], torch.int32, "cell_ends"), _ptr(arg, torch.int32, "arg"), n, c, mode,
-        _ptr(out, torch.float32, "out"), _stream(v2.device)), "se3_segment_unpool_padded")
-    return out
-
-
-class GridPoolPadded(torch.autograd.Function):
-    """``GridPool`` between two padded levels (``level``: one dict of ``BoundedLevels.levels``): [n_in, ...] -> [capacity, ...]
-    with zeros behind the kept cells; the gradient is ``se3_segment_unpool_padded``."""
-
-    @staticmethod
-    def forward(ctx, x, level, method):
-        mode = POOL_MODES[method]
-        x2 = _rows2d(_as(x, torch.float32))
-        out, arg = _level_pool(level, x2, mode, mode in (1, 2))
-        ctx.level, ctx.mode, ctx.arg, ctx.shape = level, mode, arg, x.shape
-        return out.reshape((out.shape[0],) + tuple(x.shape[1:]))
-
-    @staticmethod
-    def backward(ctx, g):
-        g2 = _rows2d(_as(g, torch.float32))
-        return _level_unpool(ctx.level, g2, ctx.arg, ctx.mode).reshape(ctx.shape), None, None
-
-
-class GridUpsamplePadded(torch.autograd.Function):
-    """``GridUpsample`` between two padded levels: rows of absent points and of dropped cells get zeros; the gradient is the
-    segment sum over all ``capacity`` cells."""
-
-    @staticmethod
-    def forward(ctx, x, level):
-        x2 = _rows2d(_as(x, torch.float32))
-        ctx.level, ctx.shape = level, x.shape
-        out = _level_unpool(level, x2, None, 3)
-        return out.reshape((out.shape[0],) + tuple(x.shape[1:]))
-
-    @staticmethod
-    def backward(ctx, g):
-        g2 = _rows2d(_as(g, torch.float32))
-        return _level_pool(ctx.level, g2, 3, False)[0].reshape(ctx.shape), None
-
-
+# ------------------------------ random levels and channel sums on padded clouds (include/se3conv_padded_rows.h)
 def rows_gather_padded(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """``src[idx]`` along dim 0 with a zero row where ``idx < 0`` (``se3_rows_gather_padded``)."""
     if not src.is_cuda:
@@ -1846,29 +1718,3 @@ def channel_sums(x2: torch.Tensor, n_valid: Optional[torch.Tensor] = None, n_fra
                                            _ptr(out, f32, "sums"), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)),
                "se3_channel_sums_padded")
     return out
-
-
-class LinearPadded(torch.autograd.Function):
-    """``Linear`` on the feature rows of a padded cloud.  Forward and input gradient are the row-wise GEMMs (absent rows stay
-    finite: they hold the bias); the weight gradient is the library's row-split GEMM over all rows -- the gradient rows of
-    absent points are zero (pc.py: the invariant) --, and the bias gradient is ``channel_sums`` over the present rows
-    instead of ``g.sum(0)``, so that a captured step holds no memset node.  ``n_valid`` None: every row is present."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, n_valid, n_frames):
-        ctx.save_for_backward(x, weight)
-        ctx.has_b, ctx.n_valid, ctx.frames = bias is not None, n_valid, int(n_frames)
-        return torch.nn.functional.linear(x, weight, bias)
-
-    @staticmethod
-    def backward(ctx, g):
-        gx, gw, _ = Linear.backward(_NoBias(ctx), g)
-        gb = channel_sums(_as(g, torch.float32), ctx.n_valid, ctx.frames) if ctx.has_b and ctx.needs_input_grad[2] else None
-        return gx, gw, gb, None, None
-
-
-class _NoBias:
-    """The context of ``LinearPadded`` as ``Linear.backward`` reads it, with the bias gradient left to the caller."""
-
-    def __init__(self, ctx):
-        self.saved_tensors, self.needs_input_grad, self.has_b = ctx.saved_tensors, ctx.needs_input_grad, False

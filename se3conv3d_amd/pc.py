@@ -371,15 +371,14 @@ class PointcloudRotEquiv(Pointcloud):
         if p_pooling_method not in ops.POOL_MODES:
             raise ValueError(p_pooling_method)
         refuse_unflagged(self, "feature_pooling")
-        if padded_rows(self):  # always the library's kernel, eager or captured: torch's reduction would read the absent rows
-            return ops.FramePoolPadded.apply(p_in_tensor, self.n_frames_, p_pooling_method, self.n_valid_)
         # Launched eagerly, a custom autograd.Function costs more in Python than this pass costs on the GPU (fwd + bwd
         # 0.099 ms through the library against 0.057 ms of stock torch ops at 65 k points, profiles/r03_next_rows.txt): outside
         # a graph capture the reduction over the frame axis is torch's own (max / min route their gradient to the winning
         # frame like torch_scatter: torch.max / torch.min with indices, not amax); inside a capture -- where the launch
         # count is what matters -- it is the library's one-kernel form.  SE3_FRAME_POOL=lib forces the library everywhere.
+        # A padded cloud always takes the library's kernel: torch's reduction would read the absent rows.
         x = p_in_tensor
-        if (_FRAME_POOL_TORCH and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and
+        if (not padded_rows(self) and _FRAME_POOL_TORCH and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and
                 x.shape[0] % self.n_frames_ == 0 and not torch.cuda.is_current_stream_capturing()):
             v = x.reshape(x.shape[0] // self.n_frames_, self.n_frames_, x.shape[1])
             if p_pooling_method == "avg":
@@ -387,7 +386,7 @@ class PointcloudRotEquiv(Pointcloud):
             if p_pooling_method == "sum":
                 return v.sum(1)
             return (v.max(1) if p_pooling_method == "max" else v.min(1))[0]
-        return ops.FramePool.apply(p_in_tensor, self.n_frames_, p_pooling_method)
+        return ops.FramePool.apply(p_in_tensor, self.n_frames_, p_pooling_method, self.n_valid_)
 
 
 # ----------------------------------------------------------------------------------- neighbourhoods
@@ -697,13 +696,15 @@ class PaddedSubSample(object):
     the level's size and overflow flag on the device (``info_ [2]``).  Pooling and up-sampling feature rows through it
     needs ``p_padded_rows`` (``PointHierarchy(..., p_padded=True, p_padded_rows=True)``): ``[n_in, ...]`` floating-point
     tensors padded like the source level become ``[capacity, ...]`` tensors padded like this one and back -- averaged
-    levels through ``ops.GridPoolPadded`` / ``ops.GridUpsamplePadded`` (``avg`` / ``max``), random levels through
+    levels through ``ops.GridPool`` / ``ops.GridUpsample`` over all ``capacity`` cells (``cells_``; ``avg`` / ``max``), random
+    levels through
     ``ops.RowsGatherPadded`` / ``ops.RowsUnpickPadded``; no absent row or dropped cell is read, and their rows are zero."""
 
     def __init__(self, p_pc_src, p_cell_size, p_level, p_info, p_rnd_sample=False, p_padded_rows=False):
         self.pc_src_, self.cell_size_, self.level_, self.info_ = p_pc_src, p_cell_size, p_level, p_info
         self.rnd_sample_ = bool(p_rnd_sample)
         self.padded_rows_ = bool(p_padded_rows)
+        self.cells_ = ops.GridCells.of_level(p_level)
         self.cell_ids_, self.sorted_ids_ = p_level["cell_ids"], p_level["sorted_ids"]
         self.capacity_ = int(p_level["pts"].shape[0])
 
@@ -720,7 +721,7 @@ class PaddedSubSample(object):
                 return ops.RowsGatherPadded.apply(p_tensor, self.cell_ids_, self.level_["picked"])
             if p_method not in ("avg", "max"):
                 raise ValueError(p_method)
-            return ops.GridPoolPadded.apply(p_tensor, self.level_, p_method)
+            return ops.GridPool.apply(p_tensor, self.cells_, p_method)
         raise NotImplementedError("pool_tensor on padded levels (p_padded=True) is not implemented: the pooled rows would "
                                   "need the level's present-row count, which is a device word")
 
@@ -733,7 +734,7 @@ class PaddedSubSample(object):
                     raise ValueError("__upsample_tensor__ of a random grid sub-sample takes [cells, C] tensors (as the "
                                      "reference)")
                 return ops.RowsUnpickPadded.apply(p_tensor, self.cell_ids_, self.level_["picked"])
-            return ops.GridUpsamplePadded.apply(p_tensor, self.level_)
+            return ops.GridUpsample.apply(p_tensor, self.cells_)
         raise NotImplementedError("upsample_tensor on padded levels (p_padded=True) is not implemented: the absent rows' "
                                   "cell ids are -1")
 

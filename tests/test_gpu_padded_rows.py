@@ -485,10 +485,10 @@ def test_a_whole_training_step_replays_as_one_graph(amd):
                     seen.append((lv + 1, x.detach()))
             for lv in range(n_lv - 2, -1, -1):
                 up = u.dec_up[lv](p_pc_in=hier.pcs_[lv + 1], p_pc_out=hier.pcs_[lv], p_in_features=x, p_neighborhood=bq(lv + 1, lv))
-                # (the U-Net's skip linears through ops.LinearPadded: torch's column sum for the bias gradient of 6000 rows
-                # zeroes its semaphores with a memset node)
+                # (the U-Net's skip linears through ops.Linear with a frame count: torch's column sum for the bias gradient of
+                # 6000 rows zeroes its semaphores with a memset node)
                 pc = hier.pcs_[lv]
-                sk = amd.ops.LinearPadded.apply(feats[lv], u.skip[lv].weight, u.skip[lv].bias, getattr(pc, "n_valid_", None), f)
+                sk = amd.ops.Linear.apply(feats[lv], u.skip[lv].weight, u.skip[lv].bias, getattr(pc, "n_valid_", None), f)
                 x = torch.nn.functional.gelu(up + sk)
                 seen.append((lv, x.detach()))
             return u.head(hier.pcs_[0].feature_pooling(x, "avg"))

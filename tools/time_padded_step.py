@@ -172,7 +172,7 @@ def network_step():
                                                                p_neighborhood=bq(lv, lv + 1)))
         for lv in (1, 0):
             up = unet.dec_up[lv](p_pc_in=levels[lv + 1], p_pc_out=levels[lv], p_in_features=h, p_neighborhood=bq(lv + 1, lv))
-            sk = ops.LinearPadded.apply(feats[lv], unet.skip[lv].weight, unet.skip[lv].bias, getattr(levels[lv], "n_valid_", None), f)
+            sk = ops.Linear.apply(feats[lv], unet.skip[lv].weight, unet.skip[lv].bias, getattr(levels[lv], "n_valid_", None), f)
             h = torch.nn.functional.gelu(up + sk)
         return unet.head(levels[0].feature_pooling(h, "avg"))
 

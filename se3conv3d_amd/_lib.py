@@ -167,6 +167,14 @@ PADDED_ROWS_SIGNATURES = {
     "se3_rows_unpick_padded": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P]),
 }
 
+# farthest-point sampling, declared in include/se3conv_fps.h (additions inside ABI version 6 as well); must list every
+# symbol that header declares
+FPS_SIGNATURES = {
+    "se3_fps_workspace_bytes": (_SZ, [_I64, _I32]),
+    "se3_fps": (C.c_int, [_P, _P, _I64, _P, _I32, _F, _P, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+}
+FPS_RESIDENT_MAX = 8192  # SE3_FPS_RESIDENT_MAX: the largest element the register-resident form of the sampling kernel takes
+
 _lib = None
 
 
@@ -185,7 +193,8 @@ def load() -> C.CDLL:
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
     for name, (res, args) in (list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items()) + list(FORMS_SIGNATURES.items())
-                                   + list(PADDED_SIGNATURES.items()) + list(PADDED_ROWS_SIGNATURES.items())):
+                                   + list(PADDED_SIGNATURES.items()) + list(PADDED_ROWS_SIGNATURES.items())
+                                   + list(FPS_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so

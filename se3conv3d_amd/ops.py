@@ -750,6 +750,81 @@ def grid_levels_bounded(pts, batch_ids, cell_sizes, capacities, n_batches: int, 
     return BoundedLevels(levels, info, counts, n, n_valid is not None, (pts, batch_ids, n_valid, ws))
 
 
+# --------------------------------------------------------------------------- farthest-point sampling
+class FpsOverflow(RuntimeError):
+    """``fps`` chose more samples than its capacity: ``needed`` is the row count to run again with."""
+
+    def __init__(self, needed: int, capacity: int):
+        super().__init__(f"farthest-point sampling chose {needed} samples but has a capacity of {capacity} rows: "
+                         f"run again with a capacity of at least {needed}")
+        self.needed, self.capacity = needed, capacity
+
+
+class FpsSamples:
+    """What ``fps`` returns, all on the device and of fixed size: ``ids [capacity]`` int32 (rows of ``pts`` in pick order,
+    element after element; -1 behind the last sample), ``d2 [capacity]`` float32 (``d2_at_pick`` of include/se3conv_fps.h;
+    -1 behind), ``starts [n_batches + 1]`` int32 (where each element's samples begin) and ``info [3]`` int32 (sample count
+    M, overflow flag, bad ``batch_ids`` flag).  Nothing here has been read by the host until ``trim()``."""
+
+    def __init__(self, ids, d2, starts, info, capacity, meta, keep):
+        self.ids, self.d2, self.starts, self.info, self.capacity = ids, d2, starts, info, capacity
+        self._meta, self._keep = meta, keep
+
+    def trim(self):
+        """The ONE device-to-host copy: ``(ids[:M], d2[:M], starts)`` as views.  ``ValueError`` when ``batch_ids`` were
+        not sorted or out of range, ``FpsOverflow`` when M exceeds the capacity."""
+        m, overflow, bad = self._meta[-3:].cpu().tolist()
+        if bad:
+            raise ValueError("fps: batch_ids must be non-decreasing and inside [0, num_batches)")
+        if overflow:
+            raise FpsOverflow(m, self.capacity)
+        return self.ids[:m], self.d2[:m], self.starts
+
+
+def fps(pts, batch_ids, ratio: float, num_batches: Optional[int] = None, start_u: Optional[torch.Tensor] = None,
+        n_valid: Optional[torch.Tensor] = None, capacity: Optional[int] = None) -> FpsSamples:
+    """Farthest-point sampling per batch element (``se3_fps``, include/se3conv_fps.h: what ``torch_cluster.fps`` is asked
+    for, with a deterministic contract): element ``b`` -- the run of rows with ``batch_ids == b``, which must be sorted --
+    gets ``min(n_b, ceil(n_b * ratio))`` samples (fp32 product), starting at row ``floor(start_u[b] * n_b)`` (``start_u``
+    float32 ``[num_batches]`` in [0,1); None: the element's first row).  Nothing synchronises with the host, so the call can
+    be captured into a HIP graph; ``n_valid`` (int32 device word): only rows ``[0, n_valid)`` are present.  ``capacity``
+    (rows of the outputs) defaults to the row count of ``pts``, which cannot overflow for any ratio <= 1.  ``pts`` float32
+    ``[N,3]`` and ``batch_ids`` int32 ``[N]`` are taken as they are: anything else is a ValueError.  ``num_batches=None``
+    reads the largest id back (not with ``n_valid``: that would read absent rows)."""
+    lib = _lib.load()
+    f32, i32 = torch.float32, torch.int32
+    _padded_cloud(pts, batch_ids, "fps")
+    dev, n = pts.device, pts.shape[0]
+    ratio = float(ratio)
+    if not 0.0 < ratio <= 1.0:
+        raise ValueError(f"fps: ratio {ratio}; expected 0 < ratio <= 1")
+    p_valid = _valid_word(n_valid, dev, "fps")
+    if num_batches is None:
+        if n_valid is not None:
+            raise ValueError("fps: a padded cloud (n_valid) needs num_batches")
+        num_batches = int(batch_ids.max().item()) + 1 if n else 1
+    nb = int(num_batches)
+    if nb < 1:
+        raise ValueError("fps: num_batches must be at least 1")
+    p_u = _ptr(start_u, f32, "start_u", dev)
+    if start_u is not None and tuple(start_u.shape) != (nb,):
+        raise ValueError(f"fps: start_u of shape {tuple(start_u.shape)} for {nb} batch elements")
+    cap = n if capacity is None else int(capacity)
+    if cap < 0:
+        raise ValueError("fps: capacity must not be negative")
+    ids_buf = _empty(max(cap, 1), dtype=i32, device=dev)  # (at least one row: an empty tensor has no address)
+    d2_buf = _empty(max(cap, 1), dtype=f32, device=dev)
+    ids, d2 = ids_buf[:cap], d2_buf[:cap]
+    meta = _empty(nb + 4, dtype=i32, device=dev)  # starts [nb + 1] | info [3]: trim() reads the flags with one copy
+    starts, info = meta[:nb + 1], meta[nb + 1:]
+    need = lib.se3_fps_workspace_bytes(n, nb)
+    ws = _workspace(need, dev)
+    _lib.check(lib.se3_fps(C.c_void_p(pts.data_ptr()), C.c_void_p(batch_ids.data_ptr()), n, p_valid, nb, ratio, p_u, cap,
+                           C.c_void_p(ids_buf.data_ptr()), C.c_void_p(d2_buf.data_ptr()), C.c_void_p(starts.data_ptr()),
+                           C.c_void_p(info.data_ptr()), C.c_void_p(ws.data_ptr()), need, _stream(dev)), "se3_fps")
+    return FpsSamples(ids, d2, starts, info, cap, meta, (pts, batch_ids, start_u, n_valid, ws))
+
+
 def _rows2d(t):
     return t.reshape(t.shape[0], -1) if t.dim() != 2 else t
 

@@ -677,16 +677,63 @@ class GridSubSample(object):
         return ops.GridUpsample.apply(p_tensor, self.cells_)
 
 
+class FPSSubSample(object):
+    """Farthest-point sub-sampling (pc/FPSSubSample.py, which calls ``torch_cluster.fps``): ``ops.fps`` under the contract
+    of include/se3conv_fps.h -- per batch element ``min(n_b, ceil(n_b * p_ratio))`` points, each the farthest from those
+    picked before it.
+
+    ``ids_`` (int64, as ``torch_cluster`` returns them) are the picked rows of the source cloud in pick order, element after
+    element; ``picked_`` the same as int32 for the library's gathers; ``d2_`` the squared distance of every pick to the
+    picks before it (extension: the squared coverage radius of every prefix).  ``p_random_start=True`` starts every element
+    at a random row, drawn with ``torch.rand`` on the device (the reference's default); ``p_start_values`` (extension, like
+    ``p_rnd_values`` of ``GridSubSample``) supplies those numbers in [0,1), one per batch element;
+    ``p_random_start=False`` starts at each element's first row.  ``__subsample_tensor__`` gathers the picked rows of a
+    tensor of any dtype whatever the method, as the reference indexes (``p_tensor[ids_]``); ``__upsample_tensor__``
+    (extension: the reference's method is an unimplemented ``pass``) scatters the rows back into zeros."""
+
+    def __init__(self, p_pc_src, p_ratio, p_random_start=True, p_start_values=None):
+        refuse_padded(p_pc_src, "FPSSubSample")
+        self.pc_src_ = p_pc_src
+        self.ratio_ = float(p_ratio)
+        self.random_start_ = bool(p_random_start)
+        pts, bid = ops._as(p_pc_src.pts_, torch.float32), ops._as(p_pc_src.batch_ids_, torch.int32)
+        n_batches = p_pc_src.num_batches() if hasattr(p_pc_src, "num_batches") else None
+        u = None
+        if p_start_values is not None:
+            if not self.random_start_:
+                raise ValueError("FPSSubSample: p_start_values are the draws of a random start (p_random_start=True)")
+            u = ops._as(p_start_values, torch.float32).to(pts.device)
+        elif self.random_start_:
+            if n_batches is None:
+                n_batches = int(bid.max().item()) + 1 if bid.numel() else 1
+            u = torch.rand(n_batches, device=pts.device)
+        ids, self.d2_, self.starts_ = ops.fps(pts, bid, self.ratio_, n_batches, start_u=u).trim()
+        self.picked_ = ids
+        self.ids_ = ids.to(torch.int64)
+        self.num_in_ = int(pts.shape[0])
+        self.num_out_ = int(ids.shape[0])
+
+    def __subsample_tensor__(self, p_tensor, p_method="avg"):
+        return ops.RowsGather.apply(p_tensor, self.picked_)
+
+    def __upsample_tensor__(self, p_tensor):
+        return ops.RowsScatter.apply(p_tensor, self.picked_, self.num_in_)
+
+
 def _make_sub_sample(p_point_cloud, p_samp_method, p_id, **kwargs):
-    """The sub-sampling object of one hierarchy step (pc/PointHierarchy.py:46-52)."""
+    """The sub-sampling object of one hierarchy step (pc/PointHierarchy.py:46-52).  A callable method (extension) is
+    called with the level's cloud and the level id and returns that object itself."""
+    if callable(p_samp_method):
+        return p_samp_method(p_point_cloud, p_id)
     if p_samp_method == "grid_avg":
         return GridSubSample(p_point_cloud, kwargs["grid_radii"][p_id], False)
     if p_samp_method == "grid_rnd":
         return GridSubSample(p_point_cloud, kwargs["grid_radii"][p_id], True)
     if p_samp_method == "fps":
-        raise NotImplementedError("farthest-point sub-sampling (FPSSubSample -> torch_cluster.fps) is outside the "
-                                  "accelerated path; no *_rot configuration uses it (INTEGRATION.md)")
-    raise ValueError(f"unknown sub-sample method {p_samp_method!r} (grid_avg, grid_rnd)")
+        raise NotImplementedError("farthest-point sub-sampling by name (\"fps\", fps_ratios=) is not dispatched: pass a "
+                                  "callable instead, PointHierarchy(pc, n, lambda cloud, i: FPSSubSample(cloud, ratios[i])) "
+                                  "(INTEGRATION.md)")
+    raise ValueError(f"unknown sub-sample method {p_samp_method!r} (grid_avg, grid_rnd, or a callable)")
 
 
 class PaddedSubSample(object):
@@ -740,7 +787,11 @@ class PaddedSubSample(object):
 
 
 class PointHierarchy(object):
-    """``p_capacities`` (extension): None builds level after level, each with its own read-back of the level size.
+    """``p_subsample_method``: ``"grid_avg"``, ``"grid_rnd"``, or (extension) a callable ``(level_cloud, level_id) ->
+    sub-sample object``, e.g. ``lambda cloud, i: FPSSubSample(cloud, 0.25)``; a callable builds level after level and takes
+    neither ``p_capacities`` nor ``p_padded``.
+
+    ``p_capacities`` (extension): None builds level after level, each with its own read-back of the level size.
     ``"input"`` or one row count per level builds ALL levels with one library call into buffers of those sizes
     (``ops.grid_levels_bounded``; ``"input"``: the row count of level 0, which cannot overflow) and reads every level size
     back with one copy; the clouds and sub-sample objects are the same, bit for bit.  ``ops.LevelOverflow`` when a level
@@ -768,6 +819,9 @@ class PointHierarchy(object):
             raise ValueError("PointHierarchy: p_padded_rows=True needs p_padded=True")
         self.level_info_ = None
         cur = p_point_cloud
+        if callable(p_subsample_method) and (p_capacities is not None or self.padded_):
+            raise ValueError("PointHierarchy: a callable sub-sample method builds level after level; it takes neither "
+                             "p_capacities nor p_padded (bounded levels are grid levels)")
         if self.padded_:
             if p_capacities is None:
                 raise ValueError("PointHierarchy: p_padded=True needs p_capacities ('input' or one row count per level)")

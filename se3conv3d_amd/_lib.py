@@ -53,7 +53,7 @@ _SZ = C.c_size_t
 _F = C.c_float
 _SHP = C.POINTER(Se3Shape)
 
-# name -> (restype, argtypes); must list every symbol include/se3conv.h declares
+# name -> (restype, argtypes), one table per header of include/ (see TABLES below)
 SIGNATURES = {
     "se3_abi_version": (C.c_int, []),
     "se3_error_string": (C.c_char_p, [C.c_int]),
@@ -116,30 +116,26 @@ SIGNATURES = {
     "se3_profile_tags": (C.c_int, [C.c_char_p, _SZ]),
 }
 
-# the capped ball query, declared in include/se3conv_capped.h (additions inside ABI version 6: the table above and
-# include/se3conv.h stay as they are); must list every symbol that header declares
+# the capped ball query
 CAPPED_SIGNATURES = {
     "se3_ball_query_capped_workspace_bytes": (_SZ, [_I64, _I64]),
     "se3_ball_query_capped": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I64, _I64, _I32, _P, _SZ, _I32, _P, _SZ, _I64, _P, _P, _P, _P,
                                         _P, _I32, C.c_uint32, _P, _P]),
 }
 
-# the chain of grid sub-sampling levels with device-side sizes, declared in include/se3conv_levels.h (additions inside ABI
-# version 6 as well); must list every symbol that header declares
+# the chain of grid sub-sampling levels with device-side sizes
 _LVL = C.POINTER(Se3Level)
 LEVEL_SIGNATURES = {
     "se3_grid_levels_workspace_bytes": (_SZ, [_I64, _I32, _LVL, _I32]),
     "se3_grid_levels": (C.c_int, [_P, _P, _I64, _P, _I32, _LVL, _I32, _P, _P, _SZ, _P]),
 }
 
-# the host-only query of the kernel forms a call takes, declared in include/se3conv_forms.h (an addition inside ABI version 6
-# as well); must list every symbol that header declares
+# the host-only query of the kernel forms a call takes
 FORMS_SIGNATURES = {
     "se3conv_forms": (C.c_int, [_SHP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _SZ]),
 }
 
-# the geometry builds on padded clouds -- row counts in device words -- declared in include/se3conv_padded.h (additions inside
-# ABI version 6 as well); must list every symbol that header declares
+# the geometry builds on padded clouds -- row counts in device words
 PADDED_SIGNATURES = {
     "se3_batch_aabb_padded": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P]),
     "se3_ball_query_padded_workspace_bytes": (_SZ, [_I64, _I64]),
@@ -151,9 +147,7 @@ PADDED_SIGNATURES = {
     "se3_pca_frames_padded": (C.c_int, [_P, _P, _I64, _P, _I32, _I32, _P, _P]),
 }
 
-# the row-wise passes of a network on padded clouds -- feature tensors padded like the points, the present-row count a device
-# word -- declared in include/se3conv_padded_rows.h (additions inside ABI version 6 as well); must list every symbol that
-# header declares
+# the row-wise passes of a network on padded clouds -- feature tensors padded like the points, the present-row count a device word
 PADDED_ROWS_SIGNATURES = {
     "se3_bn_fwd_padded": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _I32, _F, _F, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "se3_bn_bwd_padded": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
@@ -167,13 +161,25 @@ PADDED_ROWS_SIGNATURES = {
     "se3_rows_unpick_padded": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P]),
 }
 
-# farthest-point sampling, declared in include/se3conv_fps.h (additions inside ABI version 6 as well); must list every
-# symbol that header declares
+# farthest-point sampling
 FPS_SIGNATURES = {
     "se3_fps_workspace_bytes": (_SZ, [_I64, _I32]),
     "se3_fps": (C.c_int, [_P, _P, _I64, _P, _I32, _F, _P, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 FPS_RESIDENT_MAX = 8192  # SE3_FPS_RESIDENT_MAX: the largest element the register-resident form of the sampling kernel takes
+
+# header under include/ -> its table, in the order the headers were added.  The rule, for every entry: the table lists exactly
+# the symbols its header declares, with the header's argument counts, and no name stands in two tables.  Headers after
+# se3conv.h are additions inside ABI version 6: they extend the surface, the earlier headers and tables stay as they are.
+TABLES = {
+    "se3conv.h": SIGNATURES,
+    "se3conv_capped.h": CAPPED_SIGNATURES,
+    "se3conv_levels.h": LEVEL_SIGNATURES,
+    "se3conv_forms.h": FORMS_SIGNATURES,
+    "se3conv_padded.h": PADDED_SIGNATURES,
+    "se3conv_padded_rows.h": PADDED_ROWS_SIGNATURES,
+    "se3conv_fps.h": FPS_SIGNATURES,
+}
 
 _lib = None
 
@@ -192,9 +198,7 @@ def load() -> C.CDLL:
     if lib.se3_abi_version() != ABI_VERSION:  # (checked before the symbols: an older library lacks some of them)
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
-    for name, (res, args) in (list(SIGNATURES.items()) + list(CAPPED_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items()) + list(FORMS_SIGNATURES.items())
-                                   + list(PADDED_SIGNATURES.items()) + list(PADDED_ROWS_SIGNATURES.items())
-                                   + list(FPS_SIGNATURES.items())):
+    for name, (res, args) in [item for table in TABLES.values() for item in table.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so

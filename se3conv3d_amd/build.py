@@ -14,6 +14,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from . import _lib
+
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 # SE3_LIB_SUFFIX=_x builds (and _lib.py loads) lib/libse3conv_hip_x.so with its objects under lib/obj_x/: another commit's
@@ -23,13 +25,8 @@ LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj" + SUFFIX) if SUFFIX else LIBDIR
 LIB = os.path.join(LIBDIR, f"libse3conv_hip{SUFFIX}.so")
 SOURCES = ["geometry.hip", "edge_kernels.hip", "edge_bf16.hip", "edge_dx.hip", "gemm.hip", "gemm_bf16.hip", "prep.hip", "frames.hip", "glue.hip", "fps.hip", "api.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "edge_bf16_body.h"), os.path.join(os.path.dirname(PKG), "include", "se3conv.h"),
-           os.path.join(os.path.dirname(PKG), "include", "se3conv_capped.h"),
-           os.path.join(os.path.dirname(PKG), "include", "se3conv_levels.h"),
-           os.path.join(os.path.dirname(PKG), "include", "se3conv_forms.h"),
-           os.path.join(os.path.dirname(PKG), "include", "se3conv_padded.h"),
-           os.path.join(os.path.dirname(PKG), "include", "se3conv_padded_rows.h"),
-           os.path.join(os.path.dirname(PKG), "include", "se3conv_fps.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "edge_bf16_body.h")] + [
+    os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.TABLES]  # every header of the C surface
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP pass packs adjacent fp32 ops into v_pk_fma_f32 / v_pk_mul_f32, which issue slower than the
 # two scalar ops they replace on gfx950 (edge_t_fwd at the headline shape: 0.55 ms packed, 0.44 ms scalar) and need

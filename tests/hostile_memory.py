@@ -18,7 +18,9 @@ memory the test owns and is SEEN by `Arena.check()` instead of faulting.
 
 `hostile(arena)` routes the library's own allocations (`ops._empty`, `ops._empty_like`, `ops._workspace`: every result,
 saved tensor, cached operand and workspace of se3conv3d_amd/ops.py) through the arena for the duration and puts a recording
-proxy in front of the ctypes library, which notes the entry points (`_lib.SIGNATURES` names) that were really called.
+proxy in front of the ctypes library, which notes the entry points (the names of every table of `_lib.TABLES`) that were
+really called.  `guarded(...)` is the frame every hostile-memory module puts around a test body: a fresh arena, the bands
+checked afterwards, and the entry points the module's COVERED table claims for the running test proven to have been called.
 Nothing here touches `torch.empty` itself.  Not for graph capture (`check` synchronises and the arena allocates)."""
 from __future__ import annotations
 
@@ -151,8 +153,8 @@ class Arena:
 
 
 class Recorder:
-    """Stands in for the ctypes library (`_lib._lib`): forwards everything and notes which `_lib.SIGNATURES` names were
-    CALLED (not merely looked up)."""
+    """Stands in for the ctypes library (`_lib._lib`): forwards everything and notes which of `names` were CALLED (not
+    merely looked up)."""
 
     def __init__(self, lib, names):
         self._lib, self._names, self.called = lib, frozenset(names), set()
@@ -178,7 +180,7 @@ def hostile(arena: Optional[Arena]):
     real = _lib.load()
     if isinstance(real, Recorder):
         real = real._lib
-    rec = Recorder(real, _lib.SIGNATURES)
+    rec = Recorder(real, [name for table in _lib.TABLES.values() for name in table])
     saved = (ops._empty, ops._empty_like, ops._workspace, _lib._lib)
     if arena is not None:
         ops._empty, ops._empty_like, ops._workspace = arena.empty, arena.empty_like, arena.workspace
@@ -187,3 +189,52 @@ def hostile(arena: Optional[Arena]):
         yield rec
     finally:
         ops._empty, ops._empty_like, ops._workspace, _lib._lib = saved
+
+
+@contextlib.contextmanager
+def guarded(request, covered, device, workspace_fill: int = FILL, workspace: Optional[bool] = None, with_recorder: bool = False):
+    """The body runs with the library's allocations in a fresh arena on `device` (yielded; `with_recorder`: the pair of arena
+    and Recorder, for bodies that call entry points directly); afterwards the bands are checked and the entry points that
+    `covered` (entry point -> test names, a module's COVERED) claims for the running test must have been called.
+    `workspace`: True = the body took at least one workspace and none is shorter than 256 bytes, False = it took none,
+    None = not looked at."""
+    arena = Arena(device, workspace_fill)
+    with hostile(arena) as rec:
+        yield (arena, rec) if with_recorder else arena
+        arena.check()
+    want = {ep for ep, tests in covered.items() if request.node.originalname in tests}
+    assert want, f"{request.node.originalname} is not in COVERED"
+    assert want <= rec.called, f"claimed but not called: {sorted(want - rec.called)}"
+    if workspace is not None:
+        ws = [a for a in arena.allocations if a.label.startswith("workspace of")]
+        assert (ws and all(a.nbytes >= 256 for a in ws)) if workspace else not ws
+
+
+def in_arena(arena: Arena, t: torch.Tensor, rows: int) -> torch.Tensor:
+    """`t` in front of a buffer of `rows` rows whose tail keeps the arena's fill."""
+    out = arena.alloc((rows,) + tuple(t.shape[1:]), t.dtype)
+    out[:t.shape[0]] = t
+    return out
+
+
+def byte_snapshot(tensors) -> list:
+    return [t.clone().contiguous().view(torch.uint8) for t in tensors]
+
+
+def same_bytes(a, b, key) -> None:
+    assert all(torch.equal(x, y) for x, y in zip(a, b)), key
+
+
+class AcrossFills:
+    """Results are identical whatever the workspace held: `self(key, workspace_fill, result)` keeps `snapshot(result)` of the
+    first run of `key` and compares the run with the other fill against it, byte for byte (`same(kept, new, key)` asserts).
+    One instance per module, so keys of two modules never meet."""
+
+    def __init__(self, snapshot=byte_snapshot, same=same_bytes):
+        self.snapshot, self.same, self.seen = snapshot, same, {}
+
+    def __call__(self, key, workspace_fill, result) -> None:
+        snap = self.snapshot(result)
+        if key in self.seen and self.seen[key][0] != workspace_fill:
+            self.same(self.seen[key][1], snap, key)
+        self.seen.setdefault(key, (workspace_fill, snap))

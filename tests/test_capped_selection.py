@@ -1,38 +1,12 @@
-"""CPU: the capped ball query's surface and selection rule (include/se3conv_capped.h) -- the header against the ctypes
-table, host-side argument checks, the contract's check vectors, uniformity of the rule (two z-tests), and the coverage
-table of tests/test_gpu_capped_hostile_memory.py (the policy of tests/test_hostile_memory_harness.py for these entry
-points)."""
+"""CPU: the capped ball query's selection rule (include/se3conv_capped.h) -- host-side argument checks, the message of a
+library built before the entry points existed, the contract's check vectors and uniformity of the rule (two z-tests);
+tests/test_abi_tables.py holds the header against its table, the library and its hostile-memory module."""
 import ctypes as C
-import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
 from capped_neighbours import edge_hash, edge_key, mix32
-from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "se3conv_capped.h")
-
-
-def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"^(?:int|int64_t|size_t|const char\*)\s+(se3\w+)\s*\(", text, flags=re.M)))
-
-
-def test_header_and_signature_table_agree_and_every_symbol_is_exported(built_library):
-    from se3conv3d_amd import _lib
-
-    syms = declared_symbols()
-    assert syms == sorted(_lib.CAPPED_SIGNATURES) and len(syms) == 2
-    assert not set(syms) & set(_lib.SIGNATURES)          # the pinned table of include/se3conv.h is not extended
-    raw = C.CDLL(built_library)
-    for name in syms:
-        assert hasattr(raw, name), f"{name} declared in se3conv_capped.h but not exported"
-    lib = _lib.load()                                      # binds both tables
-    for name, (res, args) in _lib.CAPPED_SIGNATURES.items():
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
 
 
 def test_a_library_without_the_capped_symbols_asks_for_a_rebuild(built_library, monkeypatch):
@@ -114,22 +88,3 @@ def test_consecutive_samples_draw_independent_subsets(seed, which):
     print(f"seed {seed}, {which}: mean overlap {overlap.mean():.4f} against {mean:.4f}, z = {z:.2f}")
     assert abs(z) <= 5.0
 
-
-def test_every_capped_entry_point_with_a_device_pointer_is_covered_on_hostile_memory():
-    from se3conv3d_amd import _lib
-
-    import test_gpu_capped_hostile_memory as G
-
-    takes_pointer = {n for n, (_, args) in _lib.CAPPED_SIGNATURES.items() if _lib._P in args}
-    assert takes_pointer == {"se3_ball_query_capped"}
-    assert set(G.COVERED) == takes_pointer
-    assert set(_lib.CAPPED_SIGNATURES) - takes_pointer == {"se3_ball_query_capped_workspace_bytes"}   # host-only arithmetic
-    tests = {n for n, f in inspect.getmembers(G, inspect.isfunction) if n.startswith("test_")}
-    for name, where in G.COVERED.items():
-        assert where, name
-        for t in where:
-            assert t in tests, (name, t)
-            src = inspect.getsource(getattr(G, t))
-            assert "pytest.skip" not in src and "mark.skip" not in src and "xfail" not in src, t
-    whole = inspect.getsource(G)
-    assert "pytest.skip" not in whole and "mark.skip" not in whole and "xfail" not in whole

@@ -48,18 +48,6 @@ def report(universe, covered, excluded=()):
                      f"under (pass, want_feat, want_params, have_t) = {tuple(universe[name][1])}" for name in missing)
 
 
-def test_header_and_table_agree_and_stay_apart_from_the_other_tables(built_library):
-    import ctypes as C
-    import os
-    import re
-    from se3conv3d_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(FC.ROOT, "include", "se3conv_forms.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^(?:int|int64_t|size_t|const char\*)\s+(se3\w+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(_lib.FORMS_SIGNATURES) == ["se3conv_forms"]
-    assert not set(_lib.FORMS_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.CAPPED_SIGNATURES) | set(_lib.LEVEL_SIGNATURES))
-    assert hasattr(C.CDLL(built_library), "se3conv_forms") and _lib.load().se3_abi_version() == _lib.ABI_VERSION == 6
-
-
 def test_exclusions_are_few_size_gated_and_name_their_test(built_library):
     assert len(EXCLUSIONS) <= 12
     universe, covered = default_environment()

@@ -1,5 +1,6 @@
-"""CPU: the entry points of include/se3conv_fps.h (farthest-point sampling) are declared, bound and exported, and their
-host-side argument checks answer before any launch.  No kernel runs here."""
+"""CPU: the entry points of include/se3conv_fps.h (farthest-point sampling): the resident limit, the workspace query and
+host-side argument checks that answer before any launch (tests/test_abi_tables.py holds the header against its table and the
+library).  No kernel runs here."""
 import ctypes as C
 import os
 import re
@@ -13,35 +14,11 @@ def header_text():
     return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
-def declared_symbols():
-    return sorted(set(re.findall(r"^(?:int|int64_t|size_t|const char\*)\s+(se3\w+)\s*\(", header_text(), flags=re.M)))
-
-
-def test_header_and_table_agree_and_stay_apart_from_the_other_tables():
-    from se3conv3d_amd import _lib
-
-    assert declared_symbols() == sorted(_lib.FPS_SIGNATURES) == ["se3_fps", "se3_fps_workspace_bytes"]
-    others = (set(_lib.SIGNATURES) | set(_lib.CAPPED_SIGNATURES) | set(_lib.LEVEL_SIGNATURES) | set(_lib.FORMS_SIGNATURES)
-              | set(_lib.PADDED_SIGNATURES) | set(_lib.PADDED_ROWS_SIGNATURES))
-    assert not set(_lib.FPS_SIGNATURES) & others
-
-
 def test_resident_limit_is_the_headers():
     from se3conv3d_amd import _lib
 
     (value,) = re.findall(r"^#define\s+SE3_FPS_RESIDENT_MAX\s+(\d+)\s*$", header_text(), flags=re.M)
     assert _lib.FPS_RESIDENT_MAX == int(value) and int(value) % 1024 == 0
-
-
-def test_library_exports_the_fps_entry_points_inside_abi_version_6(built_library):
-    from se3conv3d_amd import _lib
-
-    raw = C.CDLL(built_library)
-    for name in _lib.FPS_SIGNATURES:
-        assert hasattr(raw, name), f"{name} declared in se3conv_fps.h but not exported"
-    lib = _lib.load()
-    assert lib.se3_abi_version() == _lib.ABI_VERSION == 6
-    assert lib.se3_fps.argtypes == _lib.FPS_SIGNATURES["se3_fps"][1]
 
 
 def test_host_side_argument_checks(built_library):

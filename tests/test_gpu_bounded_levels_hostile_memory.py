@@ -3,13 +3,11 @@ tests/test_gpu_hostile_memory.py for the entry points of include/se3conv_levels.
 to exactly the query's value) come from an arena, no band byte changes, the results are those of the unbounded build
 whatever the workspace held, every output byte is a result or a stated pad value, and the entry point is proven to have
 been called."""
-import contextlib
-
 import pytest
 import torch
 
+import hostile_memory
 from bounded_levels_cases import CELLS2, CELLS3, DEV, assert_pads, assert_same_levels, cloud, fixed_u, unbounded_chain
-from hostile_memory import FILL, Arena, Recorder, hostile
 
 pytestmark = pytest.mark.gpu
 
@@ -37,19 +35,8 @@ def want(ops):
     return pts, bid, unbounded_chain(ops, pts, bid, CELLS3, NB), unbounded_chain(ops, pts, bid, CELLS2, NB, rnd_last=True, u=u), u
 
 
-@contextlib.contextmanager
 def guarded(request, workspace_fill):
-    from se3conv3d_amd import _lib
-
-    arena = Arena(DEV, workspace_fill)
-    with hostile(arena) as inner:
-        rec = Recorder(inner, _lib.LEVEL_SIGNATURES)
-        _lib._lib = rec                      # (hostile() restores what it found when it returns)
-        yield arena
-        arena.check()
-    wanted = {ep for ep, tests in COVERED.items() if request.node.originalname in tests}
-    assert wanted, f"{request.node.originalname} is not in COVERED"
-    assert wanted <= rec.called, f"claimed but not called: {sorted(wanted - rec.called)}"
+    return hostile_memory.guarded(request, COVERED, DEV, workspace_fill)
 
 
 def assert_written(bounded, arena):
@@ -68,7 +55,7 @@ def snapshot(bounded):
     return [{k: v.clone() for k, v in lv.items() if k != "u"} for lv in bounded.levels] + [bounded.info.clone()]
 
 
-def same_snapshot(a, b):
+def same_snapshot(a, b, key):
     for x, y in zip(a[:-1], b[:-1]):
         assert x.keys() == y.keys()
         for k in x:
@@ -76,15 +63,7 @@ def same_snapshot(a, b):
     assert torch.equal(a[-1], b[-1])
 
 
-_seen = {}
-
-
-def across_fills(key, workspace_fill, bounded):
-    """Results are identical whatever the workspace held: the run with the other fill is compared byte for byte."""
-    snap = snapshot(bounded)
-    if key in _seen and _seen[key][0] != workspace_fill:
-        same_snapshot(_seen[key][1], snap)
-    _seen.setdefault(key, (workspace_fill, snap))
+across_fills = hostile_memory.AcrossFills(snapshot, same_snapshot)
 
 
 @pytest.mark.parametrize("workspace_fill", [0x00, 0xFF])

@@ -1,15 +1,14 @@
 """GPU: se3_ball_query_capped on 0xFF-filled, guard-banded buffers (tests/hostile_memory.py) -- the policy of
 tests/test_gpu_hostile_memory.py for the entry points of include/se3conv_capped.h: both search paths run inside an arena,
 no band byte changes, the results are those of the oracle's list put through the rule, whatever the workspace held, and
-the entry point is proven to have been called.  tests/test_capped_selection.py checks this module's coverage table."""
-import contextlib
-
+the entry point is proven to have been called.  tests/test_abi_tables.py checks this module's coverage table."""
 import pytest
 import torch
 
 from capped_neighbours import select_capped
+import hostile_memory
 from conftest import canon_edges
-from hostile_memory import FILL, Arena, Recorder, hostile
+from hostile_memory import FILL, Arena
 from oracle import se3conv_oracle as O
 from test_gpu_hostile_memory import ragged_cloud
 
@@ -29,21 +28,8 @@ def amd(built_library):
     return amd
 
 
-@contextlib.contextmanager
 def guarded(request, workspace_fill=FILL):
-    """The body runs with the library's allocations in a fresh arena and a recorder for the capped entry points in front of
-    the library; afterwards the bands are checked and the entry points COVERED claims for the test must have been called."""
-    from se3conv3d_amd import _lib
-
-    arena = Arena(DEV, workspace_fill)
-    with hostile(arena) as inner:
-        rec = Recorder(inner, _lib.CAPPED_SIGNATURES)
-        _lib._lib = rec                      # (hostile() restores what it found when it returns)
-        yield arena
-        arena.check()
-    want = {ep for ep, tests in COVERED.items() if request.node.originalname in tests}
-    assert want, f"{request.node.originalname} is not in COVERED"
-    assert want <= rec.called, f"claimed but not called: {sorted(want - rec.called)}"
+    return hostile_memory.guarded(request, COVERED, DEV, workspace_fill)
 
 
 @pytest.mark.parametrize("workspace_fill", [0xFF, 0x00])

@@ -2,14 +2,12 @@
 tests/test_gpu_hostile_memory.py for the entry points of include/se3conv_fps.h: every output and the workspace (sized to
 exactly the query's value) come from an arena, no band byte changes, the results are those of the numpy contract whatever the
 workspace held, every output byte is a result or a stated pad value, and the entry points are proven to have been called."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import fps_reference as R
-from hostile_memory import Arena, Recorder, hostile
+import hostile_memory
 from test_gpu_fps import DEV, assert_exact, bits, cloud, draws
 
 pytestmark = pytest.mark.gpu
@@ -25,19 +23,8 @@ def ops(built_library):
     return amd.ops
 
 
-@contextlib.contextmanager
 def guarded(request, workspace_fill):
-    from se3conv3d_amd import _lib
-
-    arena = Arena(DEV, workspace_fill)
-    with hostile(arena) as inner:
-        rec = Recorder(inner, _lib.FPS_SIGNATURES)
-        _lib._lib = rec                      # (hostile() restores what it found when it returns)
-        yield arena
-        arena.check()
-    wanted = {ep for ep, tests in COVERED.items() if request.node.originalname in tests}
-    assert wanted, f"{request.node.originalname} is not in COVERED"
-    assert wanted <= rec.called, f"claimed but not called: {sorted(wanted - rec.called)}"
+    return hostile_memory.guarded(request, COVERED, DEV, workspace_fill)
 
 
 def assert_written(res, arena, n_rows, nb):
@@ -51,15 +38,15 @@ def assert_written(res, arena, n_rows, nb):
     assert ws and all(a.nbytes == need >= 256 for a in ws)
 
 
-_seen = {}
+def snapshot(res):
+    return [bits(t).copy() for t in (res.ids, res.d2, res.starts, res.info)]
 
 
-def across_fills(key, workspace_fill, res):
-    """Results are identical whatever the workspace held: the run with the other fill is compared byte for byte."""
-    snap = [bits(t).copy() for t in (res.ids, res.d2, res.starts, res.info)]
-    if key in _seen and _seen[key][0] != workspace_fill:
-        assert all(np.array_equal(a, b) for a, b in zip(_seen[key][1], snap))
-    _seen.setdefault(key, (workspace_fill, snap))
+def same_snapshot(a, b, key):
+    assert all(np.array_equal(x, y) for x, y in zip(a, b)), key
+
+
+across_fills = hostile_memory.AcrossFills(snapshot, same_snapshot)
 
 
 def run_in(arena, ops, pts, bid, ratio, nb, u, **kw):

@@ -20,10 +20,9 @@ ordinary allocator -- and all outputs and gradients must be bit-for-bit equal (t
 clauses), and states which stages of backward it expects, confirmed by the launch counts of `se3_profile_read` together with
 `se3conv_bwd_needs_t`: a case that silently takes another branch fails instead of testing nothing.
 
-`COVERED` / `HOST_ONLY` partition `_lib.SIGNATURES` (tests/test_hostile_memory_harness.py checks that on the CPU): a new entry
-point fails that test until it has a case here.
+`COVERED` / `HOST_ONLY` partition `_lib.SIGNATURES` (tests/test_abi_tables.py checks that on the CPU, for this module and for
+the module of every other header): a new entry point fails that test until it has a case here.
 """
-import contextlib
 import ctypes as C
 import functools
 import os
@@ -33,6 +32,7 @@ import numpy as np
 import pytest
 import torch
 
+import hostile_memory
 from conftest import GOLDEN, canon_edges, load_npz, rel_err
 from hostile_memory import FILL, Arena, BandDamage, hostile
 from oracle import se3conv_oracle as O
@@ -101,10 +101,6 @@ HOST_ONLY = {
 }
 
 
-def claimed(test_name):
-    return {ep for ep, tests in COVERED.items() if test_name in tests}
-
-
 @pytest.fixture(scope="module")
 def amd(built_library):
     import se3conv3d_amd as amd
@@ -112,17 +108,8 @@ def amd(built_library):
     return amd
 
 
-@contextlib.contextmanager
 def guarded(request, workspace_fill=FILL):
-    """The body runs with the library's allocations in a fresh arena; afterwards the bands are checked and the entry points
-    COVERED claims for the running test must have been called."""
-    arena = Arena(DEV, workspace_fill)
-    with hostile(arena) as rec:
-        yield arena
-        arena.check()
-    want = claimed(request.node.originalname)
-    assert want, f"{request.node.originalname} is not in COVERED"
-    assert want <= rec.called, f"claimed but not called: {sorted(want - rec.called)}"
+    return hostile_memory.guarded(request, COVERED, DEV, workspace_fill)
 
 
 def profile_counts(lib, tags):

@@ -3,13 +3,12 @@ policy of tests/test_gpu_bounded_levels_hostile_memory.py: the clouds, every out
 query's value) come from an arena, so the absent rows of a cloud hold the arena's fill (NaN points, batch id -1); no band
 byte changes, the results are those of the calls on the present rows alone whatever the workspace held, every output byte is
 a result or a stated pad, and the entry points are proven to have been called."""
-import contextlib
-
 import pytest
 import torch
 
+import hostile_memory
 from conftest import canon_edges
-from hostile_memory import Arena, Recorder, hostile
+from hostile_memory import Arena, in_arena
 from padded_cases import DEV, IDENTITY, seeded_cloud
 
 pytestmark = pytest.mark.gpu
@@ -56,39 +55,11 @@ def want(ops):
     return ball, knn
 
 
-@contextlib.contextmanager
 def guarded(request, workspace_fill):
-    from se3conv3d_amd import _lib
-
-    arena = Arena(DEV, workspace_fill)
-    with hostile(arena) as inner:
-        rec = Recorder(inner, _lib.PADDED_SIGNATURES)
-        _lib._lib = rec                      # (hostile() restores what it found when it returns)
-        yield arena
-        arena.check()
-    wanted = {ep for ep, tests in COVERED.items() if request.node.originalname in tests}
-    assert wanted, f"{request.node.originalname} is not in COVERED"
-    assert wanted <= rec.called, f"claimed but not called: {sorted(wanted - rec.called)}"
-    ws = [a for a in arena.allocations if a.label.startswith("workspace of")]
-    assert ws and all(a.nbytes >= 256 for a in ws)
+    return hostile_memory.guarded(request, COVERED, DEV, workspace_fill, workspace=True)
 
 
-def in_arena(arena, t, rows):
-    """`t` in front of a buffer of `rows` rows whose tail keeps the arena's fill."""
-    out = arena.alloc((rows,) + tuple(t.shape[1:]), t.dtype)
-    out[:t.shape[0]] = t
-    return out
-
-
-_seen = {}
-
-
-def across_fills(key, workspace_fill, tensors):
-    """Results are identical whatever the workspace held: the run with the other fill is compared byte for byte."""
-    snap = [t.clone().contiguous().view(torch.uint8) for t in tensors]
-    if key in _seen and _seen[key][0] != workspace_fill:
-        assert all(torch.equal(a, b) for a, b in zip(_seen[key][1], snap)), key
-    _seen.setdefault(key, (workspace_fill, snap))
+across_fills = hostile_memory.AcrossFills()
 
 
 @pytest.mark.parametrize("workspace_fill", [0x00, 0xFF])

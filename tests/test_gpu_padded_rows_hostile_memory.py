@@ -3,13 +3,12 @@ policy of tests/test_gpu_padded_hostile_memory.py: feature rows, gradients, batc
 to exactly the query's value) come from an arena, so the absent rows hold the arena's fill (NaN features, batch id -1); no
 band byte changes, the results are those of the calls on the present rows alone whatever the workspace held, every output
 byte is a result or a stated zero / -1, and the entry points are proven to have been called."""
-import contextlib
-
 import pytest
 import torch
 
+import hostile_memory
 import padded_rows_cases as R
-from hostile_memory import Arena, Recorder, hostile
+from hostile_memory import in_arena
 from padded_cases import DEV, same_bits, seeded_cloud
 from padded_rows_cases import F32, I32, I64, FromArena, Plain, assert_rows, zero_bits
 
@@ -42,39 +41,11 @@ def feats(rows, c, seed):
     return (torch.randn(rows, c, generator=torch.Generator().manual_seed(seed)) * 1.5 + 0.25).to(DEV)
 
 
-@contextlib.contextmanager
 def guarded(request, workspace_fill, needs_workspace):
-    from se3conv3d_amd import _lib
-
-    arena = Arena(DEV, workspace_fill)
-    with hostile(arena) as inner:
-        rec = Recorder(inner, _lib.PADDED_ROWS_SIGNATURES)
-        _lib._lib = rec                      # (hostile() restores what it found when it returns)
-        yield arena, rec
-        arena.check()
-    wanted = {ep for ep, tests in COVERED.items() if request.node.originalname in tests}
-    assert wanted, f"{request.node.originalname} is not in COVERED"
-    assert wanted <= rec.called, f"claimed but not called: {sorted(wanted - rec.called)}"
-    ws = [a for a in arena.allocations if a.label.startswith("workspace of")]
-    assert (ws and all(a.nbytes >= 256 for a in ws)) if needs_workspace else not ws
+    return hostile_memory.guarded(request, COVERED, DEV, workspace_fill, workspace=needs_workspace, with_recorder=True)
 
 
-def in_arena(arena, t, rows):
-    """`t` in front of a buffer of `rows` rows whose tail keeps the arena's fill."""
-    out = arena.alloc((rows,) + tuple(t.shape[1:]), t.dtype)
-    out[:t.shape[0]] = t
-    return out
-
-
-_seen = {}
-
-
-def across_fills(key, workspace_fill, tensors):
-    """Results are identical whatever the workspace held: the run with the other fill is compared byte for byte."""
-    snap = [t.clone().contiguous().view(torch.uint8) for t in tensors]
-    if key in _seen and _seen[key][0] != workspace_fill:
-        assert all(torch.equal(a, b) for a, b in zip(_seen[key][1], snap)), key
-    _seen.setdefault(key, (workspace_fill, snap))
+across_fills = hostile_memory.AcrossFills()
 
 
 @pytest.mark.parametrize("workspace_fill", [0x00, 0xFF])

@@ -1,12 +1,8 @@
-"""CPU: the guard-band harness itself (tests/hostile_memory.py) on CPU tensors, and the coverage table of
-tests/test_gpu_hostile_memory.py -- every entry point of the C ABI is either run on hostile memory there or takes no device
-buffer at all."""
-import inspect
-
+"""CPU: the guard-band harness itself (tests/hostile_memory.py) on CPU tensors.  (The coverage tables of the hostile-memory
+modules are held against the C surface by tests/test_abi_tables.py.)"""
 import pytest
 import torch
 
-import test_gpu_hostile_memory as G
 from hostile_memory import ALIGN, BAND, FILL, Arena, BandDamage, Recorder
 
 
@@ -107,24 +103,48 @@ def test_recorder_notes_calls_not_lookups():
     assert rec.called == {"se3_a"}
 
 
-def test_every_entry_point_is_covered_or_takes_no_device_buffer():
-    from se3conv3d_amd import _lib
 
-    names = set(_lib.SIGNATURES)
-    assert set(G.COVERED) | G.HOST_ONLY == names, (sorted(names - set(G.COVERED) - G.HOST_ONLY), sorted((set(G.COVERED) | G.HOST_ONLY) - names))
-    assert not set(G.COVERED) & G.HOST_ONLY
-    assert len(G.COVERED) == 39 and len(G.HOST_ONLY) == 19
-    # the exemption is for entry points without a device buffer, and for nothing else
-    assert G.HOST_ONLY == ({"se3_abi_version", "se3_error_string", "se3conv_intermediate_bytes_per_element",
-                            "se3conv_intermediate_row_bytes", "se3_ball_query_needs_grid", "se3conv_bwd_needs_t",
-                            "se3_ball_query_grid_bytes"}
-                           | {n for n in names if n.endswith("_workspace_bytes")} | {n for n in names if n.startswith("se3_profile_")})
-    for name in G.HOST_ONLY:
-        assert _lib._P not in _lib.SIGNATURES[name][1] or name.startswith("se3_profile_"), name   # (profile: host pointers)
-    tests = {n for n, f in inspect.getmembers(G, inspect.isfunction) if n.startswith("test_")}
-    for name, where in G.COVERED.items():
-        assert where, name
-        for t in where:
-            assert t in tests, (name, t)
-            src = inspect.getsource(getattr(G, t))
-            assert "pytest.skip" not in src and "mark.skip" not in src and "xfail" not in src, t   # the table allows no exemption
+def test_the_guard_fails_on_an_unclaimed_test_an_uncalled_entry_point_a_workspace_and_a_damaged_band(built_library):
+    """`guarded` is shared by the module of every header: each of its refusals, on CPU tensors and host-only entry points
+    (one name of the first table, one of the last: the recorder sees every table)."""
+    from types import SimpleNamespace
+
+    from hostile_memory import guarded
+    from se3conv3d_amd import _lib, ops
+
+    real = _lib.load()
+    request = SimpleNamespace(node=SimpleNamespace(originalname="test_x"))
+    covered = {"se3_abi_version": ["test_x"], "se3_fps_workspace_bytes": ["test_x", "test_y"]}
+
+    def body(workspace=False, fps=True):
+        lib = _lib.load()
+        assert isinstance(lib, Recorder) and lib.se3_abi_version() == _lib.ABI_VERSION
+        if fps:
+            assert lib.se3_fps_workspace_bytes(100, 2) > 0
+        if workspace:
+            assert ops._workspace(10, "cpu").numel() == 256
+
+    with guarded(request, covered, "cpu", workspace=False):
+        body()
+    with guarded(request, covered, "cpu", 0x00, workspace=True, with_recorder=True) as (arena, rec):
+        body(workspace=True)
+        assert rec is _lib._lib and arena.workspace_fill == 0x00 and len(arena.allocations) == 1
+    assert _lib._lib is real and ops._workspace(10, "cpu").numel() == 256      # everything put back
+    with pytest.raises(AssertionError, match=r"claimed but not called: \['se3_fps_workspace_bytes'\]"):
+        with guarded(request, covered, "cpu"):
+            body(fps=False)
+    with pytest.raises(AssertionError, match="test_x is not in COVERED"):
+        with guarded(request, {"se3_abi_version": ["test_y"]}, "cpu"):
+            body()
+    with pytest.raises(AssertionError):
+        with guarded(request, covered, "cpu", workspace=True):
+            body()
+    with pytest.raises(AssertionError):
+        with guarded(request, covered, "cpu", workspace=False):
+            body(workspace=True)
+    with pytest.raises(BandDamage):
+        with guarded(request, covered, "cpu") as arena:
+            body()
+            _, a = one(arena, (4,), torch.int32)
+            a.raw[a.start + a.nbytes] = 0
+    assert _lib._lib is real

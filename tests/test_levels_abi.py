@@ -1,35 +1,7 @@
-"""CPU: the entry points of include/se3conv_levels.h (a chain of grid sub-sampling levels with device-side sizes) are
-declared, bound and exported, and their host-side argument checks answer before any launch.  No kernel runs here."""
+"""CPU: the entry points of include/se3conv_levels.h (a chain of grid sub-sampling levels with device-side sizes): the struct
+layout, the workspace query, and host-side argument checks that answer before any launch (tests/test_abi_tables.py holds the
+header against its table and the library).  No kernel runs here."""
 import ctypes as C
-import os
-import re
-
-from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "se3conv_levels.h")
-
-
-def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"^(?:int|int64_t|size_t|const char\*)\s+(se3\w+)\s*\(", text, flags=re.M)))
-
-
-def test_header_and_table_agree_and_stay_apart_from_the_other_tables():
-    from se3conv3d_amd import _lib
-
-    assert declared_symbols() == sorted(_lib.LEVEL_SIGNATURES) == ["se3_grid_levels", "se3_grid_levels_workspace_bytes"]
-    assert not set(_lib.LEVEL_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.CAPPED_SIGNATURES))
-
-
-def test_library_exports_the_level_entry_points_inside_abi_version_6(built_library):
-    from se3conv3d_amd import _lib
-
-    raw = C.CDLL(built_library)
-    for name in _lib.LEVEL_SIGNATURES:
-        assert hasattr(raw, name), f"{name} declared in se3conv_levels.h but not exported"
-    lib = _lib.load()
-    assert lib.se3_abi_version() == _lib.ABI_VERSION == 6
-    assert lib.se3_grid_levels.argtypes == _lib.LEVEL_SIGNATURES["se3_grid_levels"][1]
 
 
 def _levels(n_levels=2, capacity=64, cell=0.5, rnd=False, ptr=16):

@@ -1,52 +1,9 @@
 """CPU: the entry points of include/se3conv_padded.h (boxes, ball query, self-k-NN and PCA frames of padded clouds, row counts
-in device words) are declared, bound and exported, their host-side argument checks answer before any launch, and every one
-that takes a device pointer is claimed by the hostile-memory tests.  No kernel runs here."""
+in device words): their host-side argument checks answer before any launch (tests/test_abi_tables.py holds the header
+against its table, the library and its hostile-memory module).  No kernel runs here."""
 import ctypes as C
-import inspect
-import os
-import re
 
-from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "se3conv_padded.h")
-NAMES = ["se3_ball_query_padded", "se3_ball_query_padded_workspace_bytes", "se3_batch_aabb_padded", "se3_knn_grid_params_padded",
-         "se3_knn_query_padded", "se3_knn_query_padded_workspace_bytes", "se3_pca_frames_padded"]
 INVALID, UNSUPPORTED, WORKSPACE = -1, -2, -3
-
-
-def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"^(?:int|int64_t|size_t|const char\*)\s+(se3\w+)\s*\(", text, flags=re.M)))
-
-
-def test_header_and_table_agree_and_stay_apart_from_the_other_tables():
-    from se3conv3d_amd import _lib
-
-    assert declared_symbols() == sorted(_lib.PADDED_SIGNATURES) == NAMES
-    others = set(_lib.SIGNATURES) | set(_lib.CAPPED_SIGNATURES) | set(_lib.LEVEL_SIGNATURES) | set(_lib.FORMS_SIGNATURES)
-    assert not set(_lib.PADDED_SIGNATURES) & others
-
-
-def test_library_exports_and_types_the_padded_entry_points_inside_abi_version_6(built_library):
-    from se3conv3d_amd import _lib
-
-    raw = C.CDLL(built_library)
-    for name in _lib.PADDED_SIGNATURES:
-        assert hasattr(raw, name), f"{name} declared in se3conv_padded.h but not exported"
-    lib = _lib.load()
-    assert lib.se3_abi_version() == _lib.ABI_VERSION == 6
-    for name, (res, args) in _lib.PADDED_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype == res and fn.argtypes == args, name
-
-
-def test_argument_counts_are_those_of_the_header():
-    from se3conv3d_amd import _lib
-
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name, (_, args) in _lib.PADDED_SIGNATURES.items():
-        decl = re.search(r"\b%s\s*\((.*?)\)\s*;" % name, text, flags=re.S).group(1)
-        assert len([a for a in decl.split(",") if a.strip()]) == len(args), name
 
 
 def test_host_side_argument_checks(built_library):
@@ -108,20 +65,3 @@ def test_host_side_argument_checks(built_library):
     assert pca(axis=0) == UNSUPPORTED and pca(n=1 << 31) == UNSUPPORTED
     assert b"workspace" in lib.se3_error_string(WORKSPACE)
 
-
-def test_every_padded_entry_point_with_a_device_pointer_is_covered_on_hostile_memory():
-    from se3conv3d_amd import _lib
-
-    import test_gpu_padded_hostile_memory as G
-
-    takes_pointer = {n for n, (_, args) in _lib.PADDED_SIGNATURES.items() if _lib._P in args}
-    assert set(_lib.PADDED_SIGNATURES) - takes_pointer == {"se3_ball_query_padded_workspace_bytes",
-                                                           "se3_knn_query_padded_workspace_bytes"}   # host-only arithmetic
-    assert set(G.COVERED) == set(_lib.PADDED_SIGNATURES)           # the two queries are claimed too: the Recorder sees them
-    tests = {n for n, f in inspect.getmembers(G, inspect.isfunction) if n.startswith("test_")}
-    for name, where in G.COVERED.items():
-        assert where, name
-        for t in where:
-            assert t in tests, (name, t)
-    whole = inspect.getsource(G)
-    assert "pytest.skip" not in whole and "mark.skip" not in whole and "xfail" not in whole

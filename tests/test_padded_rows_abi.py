@@ -1,53 +1,9 @@
 """CPU: the entry points of include/se3conv_padded_rows.h (batch norm, skip connection, frame pooling and the level pooling /
-up-sampling on feature tensors of padded clouds) are declared, bound and exported, their host-side argument checks answer
-before any launch, and every one is claimed by the hostile-memory tests.  No kernel runs here."""
+up-sampling on feature tensors of padded clouds): their host-side argument checks answer before any launch
+(tests/test_abi_tables.py holds the header against its table, the library and its hostile-memory module).  No kernel runs here."""
 import ctypes as C
-import inspect
-import os
-import re
 
-from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "se3conv_padded_rows.h")
-NAMES = ["se3_bn_bwd_padded", "se3_bn_fwd_padded", "se3_channel_sums_padded", "se3_frame_pool_padded", "se3_frame_unpool_padded", "se3_rows_gather_padded",
-         "se3_rows_unpick_padded", "se3_segment_unpool_padded", "se3_skip_bwd_padded", "se3_skip_fwd_padded"]
 INVALID, UNSUPPORTED, WORKSPACE = -1, -2, -3
-
-
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def test_header_and_table_agree_and_stay_apart_from_the_other_tables():
-    from se3conv3d_amd import _lib
-
-    declared = sorted(set(re.findall(r"^(?:int|int64_t|size_t|const char\*)\s+(se3\w+)\s*\(", header_text(), flags=re.M)))
-    assert declared == sorted(_lib.PADDED_ROWS_SIGNATURES) == NAMES
-    others = (set(_lib.SIGNATURES) | set(_lib.CAPPED_SIGNATURES) | set(_lib.LEVEL_SIGNATURES) | set(_lib.FORMS_SIGNATURES)
-              | set(_lib.PADDED_SIGNATURES))
-    assert not set(_lib.PADDED_ROWS_SIGNATURES) & others
-
-
-def test_library_exports_and_types_the_entry_points_inside_abi_version_6(built_library):
-    from se3conv3d_amd import _lib
-
-    raw = C.CDLL(built_library)
-    for name in _lib.PADDED_ROWS_SIGNATURES:
-        assert hasattr(raw, name), f"{name} declared in se3conv_padded_rows.h but not exported"
-    lib = _lib.load()
-    assert lib.se3_abi_version() == _lib.ABI_VERSION == 6
-    for name, (res, args) in _lib.PADDED_ROWS_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype == res and fn.argtypes == args, name
-
-
-def test_argument_counts_are_those_of_the_header():
-    from se3conv3d_amd import _lib
-
-    text = header_text()
-    for name, (_, args) in _lib.PADDED_ROWS_SIGNATURES.items():
-        decl = re.search(r"\b%s\s*\((.*?)\)\s*;" % name, text, flags=re.S).group(1)
-        assert len([a for a in decl.split(",") if a.strip()]) == len(args), name
 
 
 def test_host_side_argument_checks(built_library):
@@ -147,18 +103,3 @@ def test_host_side_argument_checks(built_library):
     assert unpick(n=two31) == UNSUPPORTED
     assert b"workspace" in lib.se3_error_string(WORKSPACE)
 
-
-def test_every_entry_point_is_covered_on_hostile_memory():
-    from se3conv3d_amd import _lib
-
-    import test_gpu_padded_rows_hostile_memory as G
-
-    assert all(_lib._P in args for _, args in _lib.PADDED_ROWS_SIGNATURES.values())   # every one takes a device pointer
-    assert set(G.COVERED) == set(_lib.PADDED_ROWS_SIGNATURES)
-    tests = {n for n, f in inspect.getmembers(G, inspect.isfunction) if n.startswith("test_")}
-    for name, where in G.COVERED.items():
-        assert where, name
-        for t in where:
-            assert t in tests, (name, t)
-    whole = inspect.getsource(G)
-    assert "pytest.skip" not in whole and "mark.skip" not in whole and "xfail" not in whole

@@ -181,6 +181,21 @@ TABLES = {
     "se3conv_fps.h": FPS_SIGNATURES,
 }
 
+# capacity-bounded k-NN neighbourhoods: the pair query between padded clouds and the edge list of an id table
+KNN_EDGES_SIGNATURES = {
+    "se3_knn_query_pair_padded": (C.c_int, [_P, _P, _I64, _P, _P, _P, _I64, _P, _I32, _P, _P]),
+    "se3_knn_edges_workspace_bytes": (_SZ, [_I64]),
+    "se3_knn_edges_bounded": (C.c_int, [_P, _I64, _P, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
+}
+
+# Why a second registry: TABLES is the surface as tests/test_abi_tables.py pins it (seven headers, their declaration counts,
+# build.HEADERS), and that file is a yardstick that does not change.  Headers added after it stand here, under the same rule
+# -- the table lists exactly what the header declares, no name in two tables -- and get the same checks from a test file of
+# their own, which places the header into TABLES for the duration of a test (tests/test_knn_edges_abi.py).
+ADDED_TABLES = {
+    "se3conv_knn_edges.h": KNN_EDGES_SIGNATURES,
+}
+
 _lib = None
 
 
@@ -198,7 +213,7 @@ def load() -> C.CDLL:
     if lib.se3_abi_version() != ABI_VERSION:  # (checked before the symbols: an older library lacks some of them)
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
-    for name, (res, args) in [item for table in TABLES.values() for item in table.items()]:
+    for name, (res, args) in [item for tables in (TABLES, ADDED_TABLES) for table in tables.values() for item in table.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so

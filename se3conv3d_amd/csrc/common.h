@@ -509,10 +509,12 @@ __device__ __forceinline__ float knn_dist2(float dx, float dy, float dz) { retur
 __device__ __forceinline__ int64_t present_rows(const int32_t* __restrict__ n_valid, int64_t n) {
   return n_valid ? max(min((int64_t)*n_valid, n), (int64_t)0) : n;
 }
-// n_valid (device word, may be NULL = every row): the padded self query of se3conv_padded.h -- queries and candidates are
-// the rows in front of it, the rows of `out` from it on are set to -1
+// n_valid_src / n_valid_q (device words, either may be NULL = every row): the padded queries of se3conv_padded.h (the self
+// query: one word for both) and se3conv_knn_edges.h -- candidates are the source rows in front of the first, queries the rows
+// in front of the second, and the rows of `out` from the second on are set to -1
 int launch_knn_bruteforce(const float* pts, const int32_t* batch_ids, int64_t n, const float* qpts, const int32_t* qbatch,
-                          int64_t m, int k, int32_t* out, hipStream_t stream, const int32_t* n_valid = nullptr);
+                          int64_t m, int k, int32_t* out, hipStream_t stream, const int32_t* n_valid_src = nullptr,
+                          const int32_t* n_valid_q = nullptr);
 int launch_knn_listed(const float* pts, const int32_t* batch_ids, int64_t n, int k, int32_t* out, const int32_t* list,
                       const int32_t* list_count, hipStream_t stream, const int32_t* n_valid = nullptr);
 

@@ -9,6 +9,7 @@
 // reference): one query per thread, candidate tiles staged in LDS, the k best kept in registers by an
 // unrolled insertion.  N = 65k: 4.3 G distance tests ~ 1 ms; it runs once per hierarchy level.
 #include "common.h"
+#include "../../include/se3conv_knn_edges.h"
 
 namespace se3 {
 
@@ -29,12 +30,15 @@ __global__ __launch_bounds__(kKnnQueries* S) void knn_kernel(const float* __rest
                                                              const float* __restrict__ qpts,
                                                              const int32_t* __restrict__ qbatch, int64_t m, int k_out,
                                                              int32_t* __restrict__ out,
-                                                             const int32_t* __restrict__ n_valid) {
-  // n_valid (padded self query, se3conv_padded.h): queries and candidates are the rows in front of *n_valid; the rows of
-  // `out` from there on get -1 and nothing of them is read.  A block without a present query is done before it reads.
+                                                             const int32_t* __restrict__ n_valid_src,
+                                                             const int32_t* __restrict__ n_valid_q) {
+  // row-count words (padded clouds, se3conv_padded.h / se3conv_knn_edges.h; the padded self query passes one word twice):
+  // candidates are the source rows in front of *n_valid_src, queries the rows in front of *n_valid_q; the rows of `out` from
+  // there on get -1 and nothing of an absent row is read.  A block without a present query is done before it reads.
   const int64_t rows = m;
-  if (n_valid) {
-    m = n = present_rows(n_valid, m);
+  if (n_valid_src || n_valid_q) {
+    n = present_rows(n_valid_src, n);
+    m = present_rows(n_valid_q, m);
     const int64_t q = (int64_t)blockIdx.x * kKnnQueries + (threadIdx.x & 63);
     if ((threadIdx.x >> 6) == 0 && q >= m && q < rows)
       for (int e = 0; e < k_out; ++e) out[q * k_out + e] = -1;
@@ -330,11 +334,11 @@ __global__ __launch_bounds__(64 * kListedWaves) void knn_listed_kernel(const flo
 }  // namespace
 
 int launch_knn_bruteforce(const float* pts, const int32_t* batch_ids, int64_t n, const float* qpts, const int32_t* qbatch,
-                          int64_t m, int k, int32_t* out, hipStream_t s, const int32_t* n_valid) {
+                          int64_t m, int k, int32_t* out, hipStream_t s, const int32_t* n_valid_src, const int32_t* n_valid_q) {
   const dim3 grid((unsigned)((m + kKnnQueries - 1) / kKnnQueries));
 #define SE3_KNN(K, S) \
   hipLaunchKernelGGL((knn_kernel<K, S>), grid, dim3(kKnnQueries * S), 0, s, pts, batch_ids, n, qpts, qbatch, m, k, out, \
-                     n_valid)
+                     n_valid_src, n_valid_q)
   if (k <= 8) SE3_KNN(8, kKnnSlices);
   else if (k <= 16) SE3_KNN(16, kKnnSlices);
   else if (k <= 32) SE3_KNN(32, kKnnSlices);
@@ -372,6 +376,20 @@ extern "C" int se3_knn_query_pair(const float* src_pts, const int32_t* src_batch
   if (n_src == 0) return se3::launch_fill_words(out, 0xffffffffu, n_q * k, (hipStream_t)stream);
   if (!src_pts || !src_batch) return SE3_ERR_INVALID_ARGUMENT;
   return launch_knn_bruteforce(src_pts, src_batch, n_src, q_pts, q_batch, n_q, (int)k, out, (hipStream_t)stream);
+}
+
+// padded clouds on either side (include/se3conv_knn_edges.h): the same kernel with a row-count word per cloud
+extern "C" int se3_knn_query_pair_padded(const float* src_pts, const int32_t* src_batch, int64_t n_rows_src,
+                                         const int32_t* n_valid_src, const float* q_pts, const int32_t* q_batch,
+                                         int64_t n_rows_q, const int32_t* n_valid_q, int32_t k, int32_t* out, void* stream) {
+  if (n_rows_src < 0 || n_rows_q < 0 || k < 1) return SE3_ERR_INVALID_ARGUMENT;
+  if (k > 64 || n_rows_src >= (1ll << 31) || n_rows_q >= (1ll << 31)) return SE3_ERR_UNSUPPORTED;
+  if (n_rows_q == 0) return SE3_OK;
+  if (!q_pts || !q_batch || !out) return SE3_ERR_INVALID_ARGUMENT;
+  if (n_rows_src == 0) return se3::launch_fill_words(out, 0xffffffffu, n_rows_q * k, (hipStream_t)stream);
+  if (!src_pts || !src_batch) return SE3_ERR_INVALID_ARGUMENT;
+  return launch_knn_bruteforce(src_pts, src_batch, n_rows_src, q_pts, q_batch, n_rows_q, (int)k, out, (hipStream_t)stream,
+                               n_valid_src, n_valid_q);
 }
 
 namespace se3 {

@@ -1031,7 +1031,8 @@ extern "C" int se3_knn_query_padded(const float* pts, const int32_t* batch_ids, 
   if (grid)
     return knn_query_grid_impl(pts, batch_ids, aabb_min, num_cells, cell_size, n_rows, k, out, workspace, workspace_bytes,
                                stream, n_valid);
-  return launch_knn_bruteforce(pts, batch_ids, n_rows, pts, batch_ids, n_rows, (int)k, out, (hipStream_t)stream, n_valid);
+  return launch_knn_bruteforce(pts, batch_ids, n_rows, pts, batch_ids, n_rows, (int)k, out, (hipStream_t)stream, n_valid,
+                               n_valid);
 }
 
 // ---- ball query, host side: one plan per call --------------------------------------------------------------------------

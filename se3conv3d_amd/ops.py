@@ -1086,12 +1086,20 @@ def knn_query(pts, batch_ids, k: int, n_batches: Optional[int] = None, method: s
     return search(mn, num_cells, cell3, _workspace(ws_bytes, dev))
 
 
-def knn_query_pair(pts_src, batch_src, pts_q, batch_q, k: int) -> torch.Tensor:
+def knn_query_pair(pts_src, batch_src, pts_q, batch_q, k: int, n_valid_src: Optional[torch.Tensor] = None,
+                   n_valid_q: Optional[torch.Tensor] = None) -> torch.Tensor:
     """For every query point the ``k`` nearest SOURCE points of the same batch element: ``[N_q, k]`` int32 source
     indices, ascending (distance, index), -1 padded (``se3_knn_query_pair``; the ``torch_cluster.knn`` call of
-    pc/KnnNeighborhood.py:77-84).  Both batch-id arrays sorted; k <= 64."""
+    pc/KnnNeighborhood.py:77-84).  Both batch-id arrays sorted; k <= 64.  ``n_valid_src`` / ``n_valid_q`` (int32 device
+    words, either may be None = every row): PADDED clouds (``se3_knn_query_pair_padded``, include/se3conv_knn_edges.h) --
+    present queries get what the call on the present rows alone gives, absent queries -1 in every column, no absent row of
+    either cloud is read; the buffers are then taken as they are (float32 / int32, contiguous)."""
     lib = _lib.load()
     f32, i32 = torch.float32, torch.int32
+    padded = n_valid_src is not None or n_valid_q is not None
+    if padded:
+        _padded_cloud(pts_src, batch_src, "knn_query_pair")
+        _padded_cloud(pts_q, batch_q, "knn_query_pair")
     ps, pq = _as(pts_src, f32), _as(pts_q, f32)
     bs, bq = _as(batch_src, i32), _as(batch_q, i32)
     if ps.dim() != 2 or ps.shape[1] != 3 or pq.dim() != 2 or pq.shape[1] != 3:
@@ -1100,10 +1108,51 @@ def knn_query_pair(pts_src, batch_src, pts_q, batch_q, k: int) -> torch.Tensor:
         raise ValueError(f"knn_query_pair: k = {k}; at most 64 neighbours per point")
     dev = pq.device
     out = _empty((pq.shape[0], int(k)), dtype=i32, device=dev)
+    if padded:
+        _lib.check(lib.se3_knn_query_pair_padded(
+            _ptr(ps, f32, "pts_src", dev), _ptr(bs, i32, "batch_src", dev), ps.shape[0], _valid_word(n_valid_src, dev, "knn_query_pair"),
+            _ptr(pq, f32, "pts_q"), _ptr(bq, i32, "batch_q", dev), pq.shape[0], _valid_word(n_valid_q, dev, "knn_query_pair"),
+            int(k), _ptr(out, i32, "out"), _stream(dev)), "se3_knn_query_pair_padded")
+        return out
     _lib.check(lib.se3_knn_query_pair(_ptr(ps, f32, "pts_src", dev), _ptr(bs, i32, "batch_src", dev), ps.shape[0],
                                       _ptr(pq, f32, "pts_q"), _ptr(bq, i32, "batch_q", dev), pq.shape[0], int(k),
                                       _ptr(out, i32, "out"), _stream(dev)), "se3_knn_query_pair")
     return out
+
+
+def knn_edges_bounded(ids: torch.Tensor, capacity: int, n_valid: Optional[torch.Tensor] = None,
+                      neighbors_out: Optional[torch.Tensor] = None):
+    """The edge list of a k-NN id table without a read-back (``se3_knn_edges_bounded``, include/se3conv_knn_edges.h).
+    ``ids [n, k]`` int32 as ``knn_query`` / ``knn_query_pair`` write it (the valid entries of a row are a prefix, -1 behind
+    them); ``n_valid`` (int32 device word): rows from it on are absent and have no edges.  Returns ``(neighbors
+    [capacity,2] int32, ends [n] int32, info [2] int32 on the device)`` as ``ball_query_bounded`` does: sample-major
+    ``(row, id)`` pairs in table order, inclusive end offsets, ``info = (true edge count, overflow flag)``; on overflow
+    the head of the list is kept and ``ends`` clamped.  Rows of ``neighbors`` past the edge count are unset.  ``n * k`` is
+    the capacity that cannot overflow.  ``neighbors_out``: a caller-owned contiguous ``[capacity, 2]`` int32 buffer to write
+    into instead of a fresh allocation.  No host synchronisation: capturable."""
+    lib = _lib.load()
+    i32 = torch.int32
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2 or ids.shape[1] < 1:
+        raise ValueError("knn_edges_bounded: ids is an [n, k] table")
+    if not 1 <= ids.shape[1] <= 64:
+        raise ValueError(f"knn_edges_bounded: k = {ids.shape[1]}; at most 64 neighbours per point")
+    if capacity is None or int(capacity) < 0:
+        raise ValueError("knn_edges_bounded: capacity must be non-negative")
+    n, k, dev = ids.shape[0], ids.shape[1], ids.device
+    p_ids = _ptr(ids, i32, "ids")  # (taken as it is: a conversion would read the absent rows)
+    if neighbors_out is not None:
+        if neighbors_out.shape != (int(capacity), 2) or neighbors_out.dtype != i32 or not neighbors_out.is_contiguous():
+            raise ValueError(f"neighbors_out must be a contiguous int32 [{int(capacity)}, 2] tensor")
+        neighbors = neighbors_out
+    else:
+        neighbors = _empty((int(capacity), 2), dtype=i32, device=dev)
+    ends = _empty(n, dtype=i32, device=dev)
+    info = _empty(2, dtype=i32, device=dev)
+    ws = _workspace(lib.se3_knn_edges_workspace_bytes(n), dev)
+    _lib.check(lib.se3_knn_edges_bounded(p_ids, n, _valid_word(n_valid, dev, "knn_edges_bounded"), k, int(capacity),
+                                         _ptr(neighbors, i32, "neighbors"), _ptr(ends, i32, "ends"), _ptr(info, i32, "info"),
+                                         C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_knn_edges_bounded")
+    return neighbors, ends, info
 
 
 class KNNQuery(torch.autograd.Function):

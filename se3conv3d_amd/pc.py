@@ -555,11 +555,29 @@ class KnnNeighborhood(Neighborhood):
     int32 (centre, neighbour; the point itself first, -1 where the batch element is too small), ``start_ids_`` =
     ``(arange + 1) * k`` when empty slots are kept.  Two different clouds are the reference's ``torch_cluster.knn``
     path (:77-135): ``neighbors_`` int64 ``(sample, source)`` in ascending distance per sample, without the missing
-    entries unless ``p_keep_empty`` (then -1 in column 1, column 0 = the sample)."""
+    entries unless ``p_keep_empty`` (then -1 in column 1, column 0 = the sample).
+
+    ``p_capacity`` (extension): the list without empty slots built on the device into an edge buffer of that many rows
+    (``ops.knn_edges_bounded``, include/se3conv_knn_edges.h) -- no boolean-mask index, no read-back of the edge count, so
+    the build captures into a HIP graph.  ``neighbors_i32_ [p_capacity, 2]`` then holds ``num_edges()`` edges in front of an
+    unset tail, ``start_ids_`` never points past them, ``edge_info_ [2]`` is (true edge count, overflow flag) on the
+    device, and ``num_edges()`` / ``overflowed()`` are the only read-backs; ``neighbors_`` is materialised on first access.
+    After an overflow the list is truncated (its head is kept): rebuild with a larger buffer.  ``rows of samples * k`` is
+    the capacity that can never overflow.  The same edges in the same order as the unbounded build.  Not with
+    ``p_keep_empty=True`` (``ValueError``).
+
+    Padded clouds (``Pointcloud(..., p_n_valid=)``, either side, a padded cloud against itself included) need
+    ``p_capacity``: the id table then comes from the padded queries (``ops.knn_query(..., n_valid=)``,
+    ``ops.knn_query_pair(..., n_valid_src=, n_valid_q=)``) -- absent rows are never read, absent sources never listed,
+    absent samples have no edges.  Without ``p_capacity`` they are refused (``NotImplementedError``).
+
+    ``symmetric_`` is False and ``source_major()`` is None: a k-NN list is not symmetric, also for a cloud against itself,
+    so the convolution's backward reads the library's transposition of this list (``se3_csr_transpose_bounded`` on
+    ``edge_info_`` for a bounded one)."""
 
     MAX_K = 64  # neighbours a query keeps in registers; the reference's kernel has the same limit (knn_query.cu:167)
 
-    def __init__(self, p_pc_src, p_samples, p_k, p_keep_empty=False, p_standard_knn=False):
+    def __init__(self, p_pc_src, p_samples, p_k, p_keep_empty=False, p_standard_knn=False, p_capacity=None):
         # p_standard_knn (the evaluation scripts pass it, test_scannet_rot.py:110): the reference then takes
         # torch_cluster.knn instead of its own sweep kernel -- another EXACT k-NN; the search here is exact already,
         # so the flag only changes which of several equidistant candidates may come first there
@@ -567,14 +585,25 @@ class KnnNeighborhood(Neighborhood):
             raise NotImplementedError(f"KnnNeighborhood: k = {p_k}; the HIP k-NN keeps at most {self.MAX_K} neighbours "
                                       "per point (the limit of the reference's own kernel; its torch_cluster fallback "
                                       "for larger k is not implemented)")
-        if is_padded(p_pc_src) or is_padded(p_samples):
-            raise NotImplementedError("KnnNeighborhood between padded clouds (p_n_valid) is not implemented, a padded cloud "
-                                      "against itself included: the pair query has no row-count words and the list without "
-                                      "empty slots is sized by a read-back (PCA frames take the id table of "
-                                      "ops.knn_query(..., n_valid=) directly)")
+        self.padded_ = is_padded(p_pc_src) or is_padded(p_samples)
+        if self.padded_ and p_capacity is None:
+            raise NotImplementedError("KnnNeighborhood between padded clouds (p_n_valid) is not implemented without "
+                                      "p_capacity, a padded cloud against itself included: the list without empty slots "
+                                      "would be sized by a read-back -- pass p_capacity (rows of samples * k cannot "
+                                      "overflow) for the list built on the device")
+        if p_capacity is not None and p_keep_empty:
+            raise ValueError("KnnNeighborhood: p_capacity builds the list without empty slots; it does not go with "
+                             "p_keep_empty=True")
+        if p_capacity is not None and int(p_capacity) < 0:
+            raise ValueError("KnnNeighborhood: p_capacity must be non-negative")
         self.k_ = int(p_k)
         self.keep_empty_ = p_keep_empty
         self.standard_knn_ = p_standard_knn
+        self.capacity_ = None if p_capacity is None else int(p_capacity)
+        self.edge_info_ = None
+        self.neighbors_i32_ = None
+        # a k-NN list is not symmetric, also for a cloud against itself: backward reads the library's transposition of it
+        self.symmetric_ = False
         super().__init__(p_pc_src, p_samples)
 
     def __compute_neighborhood__(self):
@@ -588,10 +617,18 @@ class KnnNeighborhood(Neighborhood):
             else:
                 grid = pc.pts_.shape[0] >= ops.KNN_GRID_MIN_POINTS and self.k_ <= 32 and hasattr(pc, "aabb")
                 ids = ops.knn_query(pc.pts_, pc.batch_ids_, self.k_, pc.num_batches() if hasattr(pc, "num_batches") else None,
-                                    box=pc.aabb() if grid else None)
-        else:
+                                    box=pc.aabb() if grid else None, n_valid=getattr(pc, "n_valid_", None))
+        else:  # (the words of padded clouds, which only a bounded build is handed; None = every row)
             ids = ops.knn_query_pair(self.pc_src_.pts_, self.pc_src_.batch_ids_, self.samples_.pts_,
-                                     self.samples_.batch_ids_, self.k_)
+                                     self.samples_.batch_ids_, self.k_, n_valid_src=getattr(self.pc_src_, "n_valid_", None),
+                                     n_valid_q=getattr(self.samples_, "n_valid_", None))
+        if self.capacity_ is not None:
+            # the list, its offsets and its edge count from the table on the device: no mask index, no read-back
+            self._neighbors_dtype = torch.int32 if self_query else torch.int64
+            self.neighbors_i32_, self.start_ids_, self.edge_info_ = ops.knn_edges_bounded(
+                ids, self.capacity_, n_valid=getattr(self.samples_, "n_valid_", None))
+            self._neighbors = None
+            return
         n = ids.shape[0]
         centers = torch.arange(n, dtype=torch.int32, device=ids.device)[:, None].expand(-1, self.k_)
         self.neighbors_ = torch.stack((centers.reshape(-1), ids.reshape(-1)), -1)
@@ -603,6 +640,35 @@ class KnnNeighborhood(Neighborhood):
             self.start_ids_ = torch.cumsum(mask.reshape(n, self.k_).sum(1), 0).to(torch.int32)
         if not self_query:
             self.neighbors_ = self.neighbors_.to(torch.int64)  # what torch_cluster.knn returns
+
+    @property
+    def neighbors_(self):
+        """The list as the reference exposes it.  A capacity-bounded build materialises it on first access, all
+        ``p_capacity`` rows, in the dtype the unbounded build has (int32 for a cloud against itself, int64 between two)."""
+        if getattr(self, "_neighbors", None) is None and getattr(self, "neighbors_i32_", None) is not None:
+            self._neighbors = self.neighbors_i32_.to(self._neighbors_dtype)
+        return getattr(self, "_neighbors", None)
+
+    @neighbors_.setter
+    def neighbors_(self, value):  # the base class initialises it to None; the unbounded build and callers attach their own
+        self._neighbors = value
+        if value is not None:
+            self.neighbors_i32_ = None
+
+    def source_major(self):
+        """None: the source-major list of a k-NN neighbourhood is the library's transposition of this very list (a second
+        query with the roles swapped would find other edges)."""
+        return None
+
+    def num_edges(self) -> int:
+        """Number of edges as a host integer (one device read-back for a capacity-bounded build)."""
+        if self.edge_info_ is None:
+            return int(self.neighbors_.shape[0])
+        return min(int(self.edge_info_[0]), int(self.capacity_))
+
+    def overflowed(self) -> bool:
+        """Whether ``p_capacity`` was too small (one read-back; the list is then truncated: rebuild with a larger one)."""
+        return self.edge_info_ is not None and bool(self.edge_info_[1] != 0)
 
 
 def sample_reference_frames_pca(points, p_neighborhood, axis_fixed=False, dtype=None, device=None):
@@ -895,7 +961,8 @@ class PointHierarchy(object):
     def create_neighborhood(self, p_pc_src_id, p_pc_dest_id, p_neigh_method, **kwargs):
         """Memoised per (source level, destination level, method + its parameter), pc/PointHierarchy.py:60-79 (the k-NN
         keyword is spelled ``neihg_k`` there; ``neigh_k`` is accepted too).  ``bq_max_neighbors`` (> 0) and ``bq_seed`` cap a ball-query
-        neighbourhood (``BQNeighborhood``); they enter the key only then."""
+        neighbourhood (``BQNeighborhood``); they enter the key only then.  ``bq_capacity`` / ``knn_capacity`` (extension): a
+        capacity-bounded list (``p_capacity`` of the neighbourhood classes); the capacity enters the key."""
         cap = int(kwargs.get("bq_max_neighbors", 0) or 0) if p_neigh_method == "ball_query" else 0
         if p_neigh_method == "ball_query":
             param = kwargs["bq_radius"]
@@ -904,15 +971,15 @@ class PointHierarchy(object):
         else:
             raise ValueError(f"unknown neighbourhood method {p_neigh_method!r} (ball_query, knn)")
         key = f"{p_pc_src_id}_{p_pc_dest_id}_{p_neigh_method}{param}"
-        capacity = kwargs.get("bq_capacity") if p_neigh_method == "ball_query" else None
-        if capacity is not None:  # (extension: a capacity-bounded list, BQNeighborhood(p_capacity=); padded levels need it)
+        capacity = kwargs.get("bq_capacity") if p_neigh_method == "ball_query" else kwargs.get("knn_capacity")
+        if capacity is not None:  # (extension: a capacity-bounded list, *Neighborhood(p_capacity=); padded levels need it)
             key += f"_cap{int(capacity)}"
         if cap > 0:  # (a capped neighbourhood is another list, and so is one drawn with another seed)
             key += f"_max{cap}_seed{kwargs.get('bq_seed')}"
         if key not in self.neigh_cache_:
             src, dst = self.pcs_[p_pc_src_id], self.pcs_[p_pc_dest_id]
             self.neigh_cache_[key] = BQNeighborhood(src, dst, param, cap, p_capacity=capacity, p_seed=kwargs.get("bq_seed")) \
-                if p_neigh_method == "ball_query" else KnnNeighborhood(src, dst, param)
+                if p_neigh_method == "ball_query" else KnnNeighborhood(src, dst, param, p_capacity=capacity)
         return self.neigh_cache_[key]
 
     def clear_neigh_cache(self):

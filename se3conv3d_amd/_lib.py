@@ -196,6 +196,22 @@ ADDED_TABLES = {
     "se3conv_knn_edges.h": KNN_EDGES_SIGNATURES,
 }
 
+# global pooling: one row per batch element, on padded clouds too, in a fixed order of additions
+GLOBAL_POOL_SIGNATURES = {
+    "se3_global_pool_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
+    "se3_global_pool": (C.c_int, [_P, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "se3_global_unpool": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P]),
+}
+GLOBAL_POOL_CHUNK = 128  # SE3_GLOBAL_POOL_CHUNK: points per chunk of the sum / avg order
+
+# The third registry, and meant to be the last: tests/test_knn_edges_abi.py pins ADDED_TABLES to its one header the way
+# tests/test_abi_tables.py pins TABLES to seven, so a header after those stands here, under the same rule and with the same
+# checks from a test file of its own.  Such a test asserts that its header is IN this registry, never what the registry
+# equals: the next header is one more line here and one more test file.
+EXTENSION_TABLES = {
+    "se3conv_global_pool.h": GLOBAL_POOL_SIGNATURES,
+}
+
 _lib = None
 
 
@@ -213,7 +229,7 @@ def load() -> C.CDLL:
     if lib.se3_abi_version() != ABI_VERSION:  # (checked before the symbols: an older library lacks some of them)
         raise Se3LibraryError(f"{LIB_PATH} has ABI version {lib.se3_abi_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild it (`python -m se3conv3d_amd.build`)")
-    for name, (res, args) in [item for tables in (TABLES, ADDED_TABLES) for table in tables.values() for item in table.items()]:
+    for name, (res, args) in [item for tables in (TABLES, ADDED_TABLES, EXTENSION_TABLES) for table in tables.values() for item in table.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError:  # same ABI number, older build of it (entry points are added within a version): say so

@@ -24,10 +24,11 @@ SUFFIX = os.environ.get("SE3_LIB_SUFFIX", "")
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj" + SUFFIX) if SUFFIX else LIBDIR
 LIB = os.path.join(LIBDIR, f"libse3conv_hip{SUFFIX}.so")
-SOURCES = ["geometry.hip", "edge_kernels.hip", "edge_bf16.hip", "edge_dx.hip", "gemm.hip", "gemm_bf16.hip", "prep.hip", "frames.hip", "glue.hip", "fps.hip", "knn_edges.hip", "api.hip"]
+SOURCES = ["geometry.hip", "edge_kernels.hip", "edge_bf16.hip", "edge_dx.hip", "gemm.hip", "gemm_bf16.hip", "prep.hip", "frames.hip", "glue.hip", "fps.hip", "knn_edges.hip", "global_pool.hip", "api.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "edge_bf16_body.h")] + [
     os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.TABLES]  # every header of the pinned C surface
 ADDED_HEADERS = [os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.ADDED_TABLES]  # ... and those added since
+EXTENSION_HEADERS = [os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.EXTENSION_TABLES]  # the third registry
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP pass packs adjacent fp32 ops into v_pk_fma_f32 / v_pk_mul_f32, which issue slower than the
 # two scalar ops they replace on gfx950 (edge_t_fwd at the headline shape: 0.55 ms packed, 0.44 ms scalar) and need
@@ -71,7 +72,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJDIR, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + HEADERS + ADDED_HEADERS):
+        if force or _stale(o, [s] + HEADERS + ADDED_HEADERS + EXTENSION_HEADERS):
             jobs.append([hipcc, *FLAGS, "-c", s, "-o", o])
 
     def run(cmd):

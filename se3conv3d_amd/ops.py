@@ -1007,6 +1007,101 @@ class FramePool(torch.autograd.Function):
         return gx.reshape(ctx.shape), None, None, None
 
 
+# ------------------------------------------------------------------------------------------ global pooling
+# One row per batch element (include/se3conv_global_pool.h): fp64 sums in a fixed order and no atomic, so two calls give the
+# same bits; with the row-count word of a padded cloud neither an absent row nor an absent id is read.  The ids are per
+# POINT ([n_rows] int32), whatever the frame count.
+def _point_ids(batch_ids, n_valid, dev, who: str) -> torch.Tensor:
+    """The [n_rows] int32 ids as the library reads them: taken as they are with a word (a conversion would read the absent
+    ones), converted without one."""
+    if n_valid is None:
+        batch_ids = _as(batch_ids, torch.int32)
+    _ptr(batch_ids, torch.int32, "batch_ids", dev)
+    if batch_ids.dim() != 1:
+        raise ValueError(f"{who}: batch_ids is [n_rows], one id per point")
+    return batch_ids
+
+
+def global_pool(x, batch_ids, n_batches: int, mode, frames: int = 1, n_valid: Optional[torch.Tensor] = None):
+    """``se3_global_pool``: ``x [n_rows * frames, C]`` -> ``(out [n_batches, C] float32, arg [n_batches, C] int32 or None,
+    counts [n_batches] int32)``.  ``mode``: a name of ``POOL_MODES`` or its number; ``arg`` (the winning row) for max / min
+    only.  ``n_valid``: the row-count word of a padded cloud -- ``x`` and ``batch_ids`` are then taken as they are."""
+    mode = POOL_MODES[mode] if isinstance(mode, str) else int(mode)
+    who = "global_pool"
+    x2, n = _padded_rows(x if n_valid is not None else _rows2d(_as(x, torch.float32)), frames, who)
+    c, dev, nb = x2.shape[1], x2.device, int(n_batches)
+    ids = _point_ids(batch_ids, n_valid, dev, who)
+    if ids.shape[0] != n:
+        raise ValueError(f"{who}: {ids.shape[0]} batch ids for {n} points")
+    lib = _lib.load()
+    out = _empty((nb, c), dtype=torch.float32, device=dev)
+    arg = _empty((nb, c), dtype=torch.int32, device=dev) if mode in (1, 2) else None
+    counts = _empty((nb,), dtype=torch.int32, device=dev)
+    need = lib.se3_global_pool_workspace_bytes(n, int(frames), nb, c)
+    ws = _workspace(need, dev)
+    _lib.check(lib.se3_global_pool(_ptr(x2, torch.float32, "x"), _ptr(ids, torch.int32, "batch_ids"), n, int(frames),
+                                   _valid_word(n_valid, dev, who), nb, c, mode, _ptr(out, torch.float32, "out"),
+                                   _ptr(arg, torch.int32, "arg"), _ptr(counts, torch.int32, "counts"),
+                                   C.c_void_p(ws.data_ptr()), need, _stream(dev)), "se3_global_pool")
+    return out, arg, counts
+
+
+def global_unpool(vals, batch_ids, mode, frames: int = 1, n_valid: Optional[torch.Tensor] = None,
+                  arg: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``se3_global_unpool``: ``vals [n_batches, C]`` -> ``[n_rows * frames, C]`` -- in sum mode ``vals[batch_ids[point]]``,
+    otherwise the gradient of ``global_pool`` in that mode (``arg`` for max / min, ``counts`` for avg, both as the pool
+    returned them).  Absent rows and rows of points with an id outside ``[0, n_batches)`` are zero."""
+    mode = POOL_MODES[mode] if isinstance(mode, str) else int(mode)
+    who = "global_unpool"
+    v2 = _rows2d(_as(vals, torch.float32))
+    if not v2.is_cuda:
+        raise ValueError(f"{who}: expected [n_batches, C] values on the GPU (the HIP path has no CPU fallback)")
+    nb, c, dev = v2.shape[0], v2.shape[1], v2.device
+    ids = _point_ids(batch_ids, n_valid, dev, who)
+    n = ids.shape[0]
+    if arg is not None and tuple(arg.shape) != (nb, c) or counts is not None and tuple(counts.shape) != (nb,):
+        raise ValueError(f"{who}: arg is [n_batches, C] and counts [n_batches], as global_pool returns them")
+    out = _empty((n * int(frames), c), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().se3_global_unpool(_ptr(v2, torch.float32, "vals"), _ptr(ids, torch.int32, "batch_ids"),
+                                             _ptr(arg, torch.int32, "arg", dev), _ptr(counts, torch.int32, "counts", dev), n,
+                                             int(frames), _valid_word(n_valid, dev, who), nb, c, mode,
+                                             _ptr(out, torch.float32, "out"), _stream(dev)), "se3_global_unpool")
+    return out
+
+
+class GlobalPool(torch.autograd.Function):
+    """``global_pooling`` (pc/Pointcloud.py:58-76, pc/PointcloudRotEquiv.py:252-270): [n_rows * F, C] -> [B, C]; the gradient
+    is ``se3_global_unpool``.  ``n_valid``: the word of a padded cloud."""
+
+    @staticmethod
+    def forward(ctx, x, batch_ids, n_batches, method, n_frames=1, n_valid=None):
+        out, arg, counts = global_pool(x, batch_ids, n_batches, method, n_frames, n_valid)
+        ctx.ids, ctx.method, ctx.f, ctx.n_valid, ctx.arg, ctx.counts, ctx.shape = batch_ids, method, int(n_frames), n_valid, arg, counts, x.shape
+        return out.reshape((int(n_batches),) + tuple(x.shape[1:]))
+
+    @staticmethod
+    def backward(ctx, g):
+        gx = global_unpool(g, ctx.ids, ctx.method, ctx.f, ctx.n_valid, ctx.arg, ctx.counts)
+        return gx.reshape(ctx.shape), None, None, None, None, None
+
+
+class GlobalUpsample(torch.autograd.Function):
+    """``global_upsample`` (pc/Pointcloud.py:79-88): [B, C] -> [n_rows * F, C], ``x[batch_ids[point]]`` with zero rows for
+    absent points; the gradient is the sum pool, in its fixed order instead of the atomics of an index_add."""
+
+    @staticmethod
+    def forward(ctx, x, batch_ids, n_frames=1, n_valid=None):
+        ctx.ids, ctx.f, ctx.n_valid, ctx.shape = batch_ids, int(n_frames), n_valid, x.shape
+        out = global_unpool(x, batch_ids, "sum", n_frames, n_valid)
+        return out.reshape((out.shape[0],) + tuple(x.shape[1:]))
+
+    @staticmethod
+    def backward(ctx, g):
+        # (with a word the gradient is taken as it is: its absent rows are not read)
+        g2 = g.contiguous() if ctx.n_valid is not None else g
+        return global_pool(g2, ctx.ids, ctx.shape[0], "sum", ctx.f, ctx.n_valid)[0].reshape(ctx.shape), None, None, None
+
+
 # ------------------------------------------------------------------------------- frames (row f-1)
 KNN_GRID_MIN_POINTS = 8192  # below this the all-pairs scan is as fast as sorting into cells
 KNN_CELL_FACTOR = 1.6       # cell size / estimated k-NN distance (1.26 covers points on a face of the cloud)

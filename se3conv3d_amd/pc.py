@@ -84,9 +84,10 @@ def is_padded(cloud) -> bool:
 def refuse_padded(cloud, what: str) -> None:
     """The loud end of what padded clouds do not support yet (limits table)."""
     if is_padded(cloud):
+        hint = " (or pass p_native=True on a cloud built with p_padded_rows=True)" if what.startswith("global_") else ""
         raise NotImplementedError(f"{what} on a padded cloud (p_n_valid) is not implemented: it reads every row of the "
                                   "buffers, and the present-row count is a device word -- build the hierarchy with "
-                                  "p_padded=False for it")
+                                  f"p_padded=False for it{hint}")
 
 
 def padded_rows(cloud) -> bool:
@@ -178,13 +179,28 @@ class Pointcloud(object):
         out = torch.zeros((n_out,) + tuple(p_in_tensor.shape[1:]), dtype=p_in_tensor.dtype, device=p_in_tensor.device)
         return out.scatter_reduce(0, idx, p_in_tensor, how, include_self=False)
 
-    def global_pooling(self, p_in_tensor, p_pooling_method="avg"):
-        """One row per batch element (pc/Pointcloud.py:58-76; classification heads -- [B, C] outputs, plain torch)."""
+    def global_pooling(self, p_in_tensor, p_pooling_method="avg", p_native=False):
+        """One row per batch element (pc/Pointcloud.py:58-76; classification heads -- [B, C] outputs, plain torch).
+        ``p_native=True`` (extension, keyword): the library's kernels instead (``ops.GlobalPool``,
+        include/se3conv_global_pool.h) -- fp64 sums in a fixed order, so two runs give the same bits, and on a cloud built
+        with ``p_padded_rows=True`` the pass follows the row-count word and captures into a graph."""
+        if p_native:
+            return self._global_pool_native(p_in_tensor, p_pooling_method, getattr(self, "n_frames_", 1), "global_pooling")
         refuse_padded(self, "global_pooling")
         return self._pool_rows_by(self.batch_ids_, p_in_tensor, p_pooling_method, self.num_batches())
 
-    def global_upsample(self, p_in_tensor):
-        """pc/Pointcloud.py:79-88."""
+    def _global_pool_native(self, p_in_tensor, p_pooling_method, n_frames, what):
+        if p_pooling_method not in ops.POOL_MODES:
+            raise ValueError(p_pooling_method)
+        refuse_unflagged(self, what)
+        return ops.GlobalPool.apply(p_in_tensor, self.batch_ids_, self.num_batches(), p_pooling_method, n_frames, self.n_valid_)
+
+    def global_upsample(self, p_in_tensor, p_native=False):
+        """pc/Pointcloud.py:79-88.  ``p_native=True``: ``ops.GlobalUpsample`` -- zero rows for the absent points of a padded
+        cloud, and a gradient that is a sum in fixed order."""
+        if p_native:
+            refuse_unflagged(self, "global_upsample")
+            return ops.GlobalUpsample.apply(p_in_tensor, self.batch_ids_, getattr(self, "n_frames_", 1), self.n_valid_)
         refuse_padded(self, "global_upsample")
         return torch.index_select(p_in_tensor, 0, self.batch_ids_.to(torch.int64))
 
@@ -349,18 +365,30 @@ class PointcloudRotEquiv(Pointcloud):
         self.local_frames_ = self.local_frames_.to(p_device)
         self.batch_ids_considering_frames_ = self.batch_ids_considering_frames_.to(p_device)
 
-    def global_pooling(self, p_in_tensor, p_pooling_method="avg"):
-        """Rows are per (point, frame) here (pc/PointcloudRotEquiv.py:252-270)."""
+    def global_pooling(self, p_in_tensor, p_pooling_method="avg", p_native=False):
+        """Rows are per (point, frame) here (pc/PointcloudRotEquiv.py:252-270).  ``p_native``: as in ``Pointcloud`` -- the
+        kernel takes the per-point ids and the frame count, no ``[N * F]`` copy of the ids."""
+        if p_native:
+            return super().global_pooling(p_in_tensor, p_pooling_method, p_native=True)
         refuse_padded(self, "global_pooling")
         return self._pool_rows_by(self.batch_ids_considering_frames_, p_in_tensor, p_pooling_method, self.num_batches())
 
-    def global_upsample(self, p_in_tensor):
+    def global_upsample(self, p_in_tensor, p_native=False):
+        if p_native:
+            return super().global_upsample(p_in_tensor, p_native=True)
         refuse_padded(self, "global_upsample")
         return torch.index_select(p_in_tensor, 0, self.batch_ids_considering_frames_.to(torch.int64))
 
     def global_pooling_specific_feature_pooling(self, p_in_tensor, p_global_pooling_method="avg",
-                                                p_feature_pooling_method="avg"):
-        """Frames first, then batch elements (pc/PointcloudRotEquiv.py:195-222)."""
+                                                p_feature_pooling_method="avg", p_native=False):
+        """Frames first, then batch elements (pc/PointcloudRotEquiv.py:195-222).  ``p_native=True``: ``ops.FramePool``, then
+        ``ops.GlobalPool`` over the per-point rows -- two kernels forward, two backward."""
+        if p_native:
+            if p_feature_pooling_method not in ops.POOL_MODES:
+                raise ValueError(p_feature_pooling_method)
+            refuse_unflagged(self, "global_pooling_specific_feature_pooling")
+            pooled = ops.FramePool.apply(p_in_tensor, self.n_frames_, p_feature_pooling_method, self.n_valid_)
+            return self._global_pool_native(pooled, p_global_pooling_method, 1, "global_pooling_specific_feature_pooling")
         refuse_padded(self, "global_pooling_specific_feature_pooling")
         pooled = self.feature_pooling(p_in_tensor, p_pooling_method=p_feature_pooling_method)
         return self._pool_rows_by(self.batch_ids_, pooled, p_global_pooling_method, self.num_batches())

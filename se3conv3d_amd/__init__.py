@@ -3,7 +3,8 @@
 Layout mirrors the slice of ``point_cloud_lib`` that the path touches:
 
   se3conv3d_amd.layers   PNEConvLayerRotEquiv(+Factory), PNEConvLayer(+Factory), IConvLayer(+Factory), PreProcessModule
-  se3conv3d_amd.blocks   ResNetFormer, SkipConnection, DropPathPC, BatchNormPC (torch glue around the conv)
+  se3conv3d_amd.blocks   ResNetFormer, ResNetB, ResConvNeXt, SkipConnection, DropPathPC, BatchNormPC, GroupNormPC (torch glue
+                         around the conv)
   se3conv3d_amd.pc       Pointcloud(RotEquiv), BQNeighborhood, PointHierarchy(RotEquiv), frame sampling
   se3conv3d_amd.ops      FeatBasisProj, BallQuery, ComputeKeys, SE3ConvFunction (ctypes -> C ABI)
   se3conv3d_amd.csrc     HIP kernels + the extern "C" boundary (include/se3conv.h)
@@ -12,7 +13,7 @@ Importing the package does not load the HIP library; the first op call does and 
 not been built (``python -m se3conv3d_amd.build``).
 """
 from . import blocks, layers, ops, pc  # noqa: F401
-from .blocks import BatchNormPC, DropPathPC, ResNetFormer, SkipConnection  # noqa: F401
+from .blocks import BatchNormPC, DropPathPC, GroupNormPC, ResConvNeXt, ResNetB, ResNetFormer, SkipConnection  # noqa: F401
 from .layers import (IConvLayer, IConvLayerFactory, PNEConvLayer, PNEConvLayerFactory,  # noqa: F401
                      PNEConvLayerRotEquiv, PNEConvLayerRotEquivFactory, PreProcessModule)
 from .ops import (BallQuery, ComputeKeys, FeatBasisProj, KNNQuery, SE3ConvFunction,  # noqa: F401

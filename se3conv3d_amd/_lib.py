@@ -204,12 +204,21 @@ GLOBAL_POOL_SIGNATURES = {
 }
 GLOBAL_POOL_CHUNK = 128  # SE3_GLOBAL_POOL_CHUNK: points per chunk of the sum / avg order
 
+# the point-cloud group norm: statistics per (batch element, channel group) in the same kind of fixed order
+GROUP_NORM_SIGNATURES = {
+    "se3_group_norm_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),
+    "se3_group_norm_fwd": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _I32, _F, _P, _P, _P, _P, _SZ, _P]),
+    "se3_group_norm_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+}
+GROUP_NORM_CHUNK = 64  # SE3_GROUP_NORM_CHUNK: points per chunk of the order of additions
+
 # The third registry, and meant to be the last: tests/test_knn_edges_abi.py pins ADDED_TABLES to its one header the way
 # tests/test_abi_tables.py pins TABLES to seven, so a header after those stands here, under the same rule and with the same
 # checks from a test file of its own.  Such a test asserts that its header is IN this registry, never what the registry
 # equals: the next header is one more line here and one more test file.
 EXTENSION_TABLES = {
     "se3conv_global_pool.h": GLOBAL_POOL_SIGNATURES,
+    "se3conv_group_norm.h": GROUP_NORM_SIGNATURES,
 }
 
 _lib = None

@@ -1102,6 +1102,74 @@ class GlobalUpsample(torch.autograd.Function):
         return global_pool(g2, ctx.ids, ctx.shape[0], "sum", ctx.f, ctx.n_valid)[0].reshape(ctx.shape), None, None, None
 
 
+# ------------------------------------------------------------------------------------------ group norm
+def _point_rows(x2: torch.Tensor, n_valid, frames: int, who: str) -> tuple:
+    """``n_rows, frames, n_valid`` of an entry point that always takes the three: those of ``_glue_rows`` with a row-count word,
+    every point and a null word without one."""
+    if n_valid is not None:
+        return _glue_rows(x2, n_valid, frames, who)
+    return (x2.shape[0] // frames, frames, C.c_void_p(0))
+
+
+class GroupNorm(torch.autograd.Function):
+    """``GroupNormPC`` (layers/GroupNormPC.py:34-57) on ``[n_rows * n_frames, C]``: every batch element normalised on its own
+    per group of channels (the group of channel ``c`` is ``c % num_groups``), ``se3_group_norm_fwd`` / ``se3_group_norm_bwd``
+    (include/se3conv_group_norm.h) -- fp64 sums in a fixed order and no atomic, so two calls give the same bits.
+    ``batch_ids``: one id per POINT.  ``n_valid``: the row-count word of a padded cloud -- ``x``, the gradient and the ids are
+    then taken as they are, statistics and gradients run over the present rows alone, and the absent rows get zeros."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, batch_ids, n_batches, num_groups, eps, n_valid=None, n_frames=1):
+        f32, who = torch.float32, "GroupNorm"
+        x2 = _feature_rows(x, n_valid, n_frames, who)
+        if not x2.is_cuda:
+            raise ValueError(f"{who}: expected [rows, C] features on the GPU (the HIP path has no CPU fallback)")
+        c, dev, nb, groups, frames = x2.shape[1], x2.device, int(n_batches), int(num_groups), int(n_frames)
+        ids = _point_ids(batch_ids, n_valid, dev, who)
+        if frames < 1 or ids.shape[0] * frames != x2.shape[0]:
+            raise ValueError(f"{who}: {ids.shape[0]} batch ids and {frames} frame(s) for {x2.shape[0]} rows")
+        ga, be = _as(gamma, f32).reshape(-1), _as(beta, f32).reshape(-1)
+        if ga.shape[0] != c or be.shape[0] != c:
+            raise ValueError(f"{who}: gamma and beta hold one value per channel")
+        lib = _lib.load()
+        y = _empty_like(x2)
+        mean = _empty((nb, groups), dtype=f32, device=dev)
+        invstd = _empty((nb, groups), dtype=f32, device=dev)
+        need = lib.se3_group_norm_workspace_bytes(ids.shape[0], frames, nb, c, groups)
+        ws = _workspace(need, dev)
+        _lib.check(lib.se3_group_norm_fwd(_ptr(x2, f32, "x"), _ptr(ga, f32, "gamma", dev), _ptr(be, f32, "beta", dev),
+                                          _ptr(ids, torch.int32, "batch_ids"), *_point_rows(x2, n_valid, frames, who),
+                                          nb, c, groups, float(eps), _ptr(y, f32, "y"),
+                                          _ptr(mean, f32, "save_mean"), _ptr(invstd, f32, "save_invstd"),
+                                          C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_group_norm_fwd")
+        ctx.save_for_backward(x2, ga, mean, invstd, ids)
+        ctx.nb, ctx.groups, ctx.frames, ctx.n_valid = nb, groups, frames, n_valid
+        ctx.gamma_shape, ctx.beta_shape = gamma.shape, beta.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        f32, who = torch.float32, "GroupNorm"
+        x2, ga, mean, invstd, ids = ctx.saved_tensors
+        g2 = _as(g, f32)
+        c, dev = x2.shape[1], x2.device
+        lib = _lib.load()
+        dx = _empty_like(x2)
+        dgamma = _empty(c, dtype=f32, device=dev)
+        dbeta = _empty(c, dtype=f32, device=dev)
+        need = lib.se3_group_norm_workspace_bytes(ids.shape[0], ctx.frames, ctx.nb, c, ctx.groups)
+        ws = _workspace(need, dev)
+        _lib.check(lib.se3_group_norm_bwd(_ptr(g2, f32, "dy", dev), _ptr(x2, f32, "x"), _ptr(ga, f32, "gamma"),
+                                          _ptr(mean, f32, "save_mean"), _ptr(invstd, f32, "save_invstd"),
+                                          _ptr(ids, torch.int32, "batch_ids"), *_point_rows(x2, ctx.n_valid, ctx.frames, who),
+                                          ctx.nb, c, ctx.groups, _ptr(dx, f32, "dx"),
+                                          _ptr(dgamma, f32, "dgamma"), _ptr(dbeta, f32, "dbeta"), C.c_void_p(ws.data_ptr()),
+                                          ws.numel(), _stream(dev)), "se3_group_norm_bwd")
+        ng = ctx.needs_input_grad
+        return (dx if ng[0] else None, dgamma.reshape(ctx.gamma_shape) if ng[1] else None,
+                dbeta.reshape(ctx.beta_shape) if ng[2] else None) + (None,) * 6
+
+
 # ------------------------------------------------------------------------------- frames (row f-1)
 KNN_GRID_MIN_POINTS = 8192  # below this the all-pairs scan is as fast as sorting into cells
 KNN_CELL_FACTOR = 1.6       # cell size / estimated k-NN distance (1.26 covers points on a face of the cloud)

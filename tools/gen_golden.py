@@ -9,7 +9,9 @@ What is executed from the reference (imported from /root/reference/point_cloud_l
 copied): ``PNEConvLayerRotEquivFactory`` / ``PNEConvLayerRotEquiv`` (forward through
 ``IConvLayer.forward`` incl. the EMA pre-process branch, ``get_rot_tenors``, the kernel MLP,
 ``FeatBasisProj`` autograd function, einsum, scalings, parameter init), ``PointcloudRotEquiv``
-(random frames), ``BQNeighborhood``, and ``RotationFunctions.*``.
+(random frames), ``BQNeighborhood``, ``RotationFunctions.*``, and the blocks and norms around the convolution
+(``ResNetFormer``, ``ResNetB``, ``ResConvNeXt``, ``BatchNormPC``, ``GroupNormPC``: ``python tools/gen_golden.py group_norm``
+writes the three fixtures of the group norm alone).
 
 What is NOT the reference: three native modules are not installed here and cannot be built
 (no nvcc): ``point_cloud_lib_ops`` (CUDA), ``torch_scatter``, ``torch_cluster``.  The
@@ -429,6 +431,79 @@ def block_case(pclib, seed):
     return data
 
 
+def _group_norm_layer(pclib):
+    """The reference's GroupNormPC as a norm-layer factory.  Its forward reads ``self.num_features_`` (layers/GroupNormPC.py:42,
+    56) while NormLayerPC.py:21 stores ``num_feats_``: the attribute is set on the instance, the code runs as it is."""
+    def make(c, groups=8):
+        norm = pclib.layers.GroupNormPC(c, groups)
+        norm.num_features_ = norm.num_feats_
+        return norm
+    return make
+
+
+GROUP_NORM_SIZES = (130, 47, 123)           # 300 points, three elements of uneven size
+GROUP_NORM_SHAPES = ((16, 8), (24, 4), (8, 8))
+
+
+def group_norm_case(pclib, seed):
+    """GroupNormPC of the reference (layers/GroupNormPC.py:34-57, with the scatter_mean stand-in) on a plain Pointcloud: output
+    and autograd gradients per (C, G), with gamma and betas moved off 1 and 0 and a per-channel offset on the input."""
+    torch.manual_seed(seed)
+    n = sum(GROUP_NORM_SIZES)
+    bid = torch.repeat_interleave(torch.arange(len(GROUP_NORM_SIZES), dtype=torch.int32), torch.tensor(GROUP_NORM_SIZES))
+    pc = pclib.pc.Pointcloud(torch.rand(n, 3), bid)
+    out = {"batch": bid.numpy(), "shapes": np.array(GROUP_NORM_SHAPES, dtype=np.int32)}
+    for c, groups in GROUP_NORM_SHAPES:
+        norm = _group_norm_layer(pclib)(c, groups)
+        with torch.no_grad():
+            norm.gamma_.uniform_(0.5, 1.5)
+            norm.betas_.uniform_(-0.5, 0.5)
+        x = (torch.randn(n, c) * (0.5 + torch.rand(1, c)) + torch.randn(1, c)).requires_grad_(True)
+        y = norm(x, pc)
+        g = torch.randn_like(y)
+        y.backward(g)
+        p = f"c{c}_g{groups}/"
+        out[p + "x"], out[p + "g"], out[p + "y"], out[p + "dx"] = x.detach().numpy(), g.numpy(), y.detach().numpy(), x.grad.numpy()
+        out[p + "gamma"], out[p + "betas"] = norm.gamma_.detach().numpy(), norm.betas_.detach().numpy()
+        out[p + "dgamma"], out[p + "dbetas"] = norm.gamma_.grad.numpy(), norm.betas_.grad.numpy()
+    return out
+
+
+def group_norm_block_case(pclib, seed, block):
+    """A whole ResNetB / ResConvNeXt block of the reference with GroupNormPC as its norm layer (SkipConnection with gamma moved
+    off its 1e-6 initial value, no drop path) around PNEConvLayerRotEquiv, in the manner of `block_case` and smaller: state_dict,
+    input, output and every gradient."""
+    torch.manual_seed(seed)
+    n, f, c_in, c_out = 200, 1, 16, 24    # one frame: the reference's GroupNormPC takes one id per row from `batch_ids_`
+    pts = torch.rand(n, 3)
+    bid = torch.sort(torch.randint(0, 2, (n,), dtype=torch.int32)).values
+    pc = pclib.pc.PointcloudRotEquiv(pts, bid, {"pca": False, "n_frames": f, "fixed_axis": False})
+    r = _radius(n / 2, 12)
+    nbh = pclib.pc.BQNeighborhood(pc, pc, r)
+    fact = pclib.layers.PNEConvLayerRotEquivFactory(9, 32, "mlp_gelu")
+    blk = getattr(pclib.layers, block)(c_in, c_out, fact, _group_norm_layer(pclib), 0.0)
+    blk.train()
+    with torch.no_grad():
+        blk.spatial_conv_.norm_neigh_dist_.fill_(1.0 / r)
+        blk.spatial_conv_.norm_num_neighs_.fill_(nbh.start_ids_.shape[0] / nbh.neighbors_.shape[0])
+        blk.spatial_conv_.proj_biases_.uniform_(-0.5, 0.5)
+        blk.skip_path_.gamma_.fill_(0.9)
+        blk.norm_.gamma_.uniform_(0.5, 1.5)
+        blk.norm_.betas_.uniform_(-0.5, 0.5)
+    state0 = {k: v.detach().clone() for k, v in blk.state_dict().items()}
+    x = torch.randn(n * f, c_in, requires_grad=True)
+    out = blk(pc, x, nbh)
+    g = torch.randn_like(out)
+    out.backward(g)
+    data = {"pts": pts.numpy(), "batch": bid.numpy(), "frames": pc.local_frames_.numpy(), "radius": np.float32(r),
+            "x": x.detach().numpy(), "out": out.detach().numpy(), "g": g.numpy(), "dx": x.grad.numpy()}
+    for k, v in state0.items():
+        data["state/" + k] = v.numpy()
+    for k, v in blk.named_parameters():
+        data["grad/" + k] = v.grad.numpy()
+    return data
+
+
 def pne_case(pclib, seed, n_in, n_out, c_in, c_out, k_deg, batches):
     """The reference's non-equivariant PNEConvLayer ('mlp_gelu', aggregation 'add', 3-D offsets; scope row f-4):
     plain Pointcloud, BQNeighborhood, forward + backward through LinearPNE / FeatBasisProj / einsum."""
@@ -748,6 +823,15 @@ def main():
         np.savez_compressed(path, **block_case(pclib, 13))
         print(f"{path}: size={os.path.getsize(path) / 1e6:.2f} MB")
     if only == "block":
+        return
+    if only in ("", "group_norm"):
+        cases = [("group_norm.npz", group_norm_case(pclib, 31))]
+        cases += [(f"{block.lower()}_block.npz", group_norm_block_case(pclib, 37, block)) for block in ("ResNetB", "ResConvNeXt")]
+        for name, data in cases:
+            path = os.path.join(OUT, name)
+            np.savez_compressed(path, **data)
+            print(f"{path}: size={os.path.getsize(path) / 1e6:.2f} MB")
+    if only == "group_norm":
         return
     for name, seed, n_in, n_out, c_in, c_out, k, b in PNE_CASES:
         path = os.path.join(OUT, f"{name}.npz")

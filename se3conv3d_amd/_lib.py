@@ -212,6 +212,16 @@ GROUP_NORM_SIGNATURES = {
 }
 GROUP_NORM_CHUNK = 64  # SE3_GROUP_NORM_CHUNK: points per chunk of the order of additions
 
+# the loss and metrics head: masked, smoothed cross-entropy and the per-class counters of SemSegMetrics in one pass
+SEG_HEAD_SIGNATURES = {
+    "se3_seg_head_workspace_bytes": (_SZ, [_I64, _I32]),
+    "se3_seg_loss_fwd": (C.c_int, [_P, _P, _I32, _P, _I64, _P, _I32, _F, _P, _P, _P, _P, _P, _SZ, _P]),
+    "se3_seg_loss_bwd": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _I64, _P, _I32, _F, _P, _P]),
+}
+SEG_HEAD_CHUNK = 256         # SE3_SEG_HEAD_CHUNK: rows per chunk of the loss sum
+SEG_HEAD_TILE_CLASSES = 56   # SE3_SEG_HEAD_TILE_CLASSES: the widest row the LDS-tile form of the kernels takes
+SEG_HEAD_MAX_CLASSES = 1024
+
 # The third registry, and meant to be the last: tests/test_knn_edges_abi.py pins ADDED_TABLES to its one header the way
 # tests/test_abi_tables.py pins TABLES to seven, so a header after those stands here, under the same rule and with the same
 # checks from a test file of its own.  Such a test asserts that its header is IN this registry, never what the registry
@@ -219,6 +229,7 @@ GROUP_NORM_CHUNK = 64  # SE3_GROUP_NORM_CHUNK: points per chunk of the order of 
 EXTENSION_TABLES = {
     "se3conv_global_pool.h": GLOBAL_POOL_SIGNATURES,
     "se3conv_group_norm.h": GROUP_NORM_SIGNATURES,
+    "se3conv_seg_head.h": SEG_HEAD_SIGNATURES,
 }
 
 _lib = None

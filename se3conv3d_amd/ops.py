@@ -1170,8 +1170,100 @@ class GroupNorm(torch.autograd.Function):
                 dbeta.reshape(ctx.beta_shape) if ng[2] else None) + (None,) * 6
 
 
+# ------------------------------------------------------------------------------------------ loss and metrics head
+# include/se3conv_seg_head.h: the mean smoothed cross-entropy over the rows that count and the per-class counters of
+# SemSegMetrics in one pass over the logits, the gradient in a second.  Nothing is compacted and nothing is read back: which
+# classes count is a device mask, which rows exist a device word.
+_counted_masks: dict = {}
+
+
+def counted_mask(classes: int, not_counted, device) -> torch.Tensor:
+    """The ``[classes]`` uint8 mask of ``se3_seg_loss_fwd`` from the ids of the classes that do NOT count (``p_mask_cls`` of the
+    task scripts).  Uploaded once per (ids, classes, device) and kept: a later call, inside a capture too, copies nothing."""
+    ids = tuple(sorted({int(i) for i in not_counted}))
+    key = (ids, int(classes), str(device))
+    mask = _counted_masks.get(key)
+    if mask is None:
+        host = torch.ones(int(classes), dtype=torch.uint8)
+        for i in ids:
+            if 0 <= i < int(classes):
+                host[i] = 0
+        mask = _counted_masks[key] = host.to(device)
+    return mask
+
+
+def _seg_labels(labels, n: int, dev, who: str) -> Tuple[C.c_void_p, int]:
+    """Labels are taken as they are, int64 (torch's) or int32: ``(pointer, label_bits)``."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"{who}: labels are an int64 or int32 tensor (they are not converted)")
+    if tuple(labels.shape) != (n,):
+        raise ValueError(f"{who}: labels of shape {tuple(labels.shape)} for {n} rows of logits")
+    return _ptr(labels, labels.dtype, "labels", dev), 64 if labels.dtype == torch.int64 else 32
+
+
+class SegLoss(torch.autograd.Function):
+    """``CrossEntropyLoss(reduction="mean", label_smoothing=...)`` over the rows of ``logits [n_rows, classes]`` that count
+    (``se3_seg_loss_fwd`` / ``se3_seg_loss_bwd``): a row counts iff it is present, its label lies in ``[0, classes)`` (so -100 is
+    ignored) and ``counted`` (a ``[classes]`` uint8 device tensor, or None) is nonzero at the label.  ``n_valid``: the row-count
+    word of a padded cloud -- logits and labels are then taken as they are and no absent row or label is read.  ``tallies``
+    (``[3, classes]`` int64 on the device, or None): the call ADDS the counted rows' ground truth / predicted / hit counts.
+    Every row that does not count gets a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, label_smoothing=0.0, counted=None, n_valid=None, tallies=None):
+        f32, who = torch.float32, "SegLoss"
+        x2 = _feature_rows(logits, n_valid, 1, who)
+        if not x2.is_cuda:
+            raise ValueError(f"{who}: expected [rows, classes] logits on the GPU (the HIP path has no CPU fallback)")
+        n, classes, dev = x2.shape[0], x2.shape[1], x2.device
+        lab_ptr, bits = _seg_labels(labels, n, dev, who)
+        if counted is not None and tuple(counted.shape) != (classes,):
+            raise ValueError(f"{who}: counted is [classes] uint8")
+        if tallies is not None and (tuple(tallies.shape) != (3, classes) or tallies.requires_grad):
+            raise ValueError(f"{who}: tallies is [3, classes] int64")
+        lib = _lib.load()
+        loss = _empty((1,), dtype=f32, device=dev)
+        count = _empty((1,), dtype=torch.int32, device=dev)
+        lse = _empty((n,), dtype=torch.float64, device=dev) if ctx.needs_input_grad[0] else None
+        need = lib.se3_seg_head_workspace_bytes(n, classes)
+        ws = _workspace(need, dev)
+        _lib.check(lib.se3_seg_loss_fwd(_ptr(x2, f32, "logits"), lab_ptr, bits, _ptr(counted, torch.uint8, "counted", dev), n,
+                                        _valid_word(n_valid, dev, who), classes, float(label_smoothing), _ptr(loss, f32, "loss"),
+                                        _ptr(count, torch.int32, "count"), _ptr(lse, torch.float64, "lse"),
+                                        _ptr(tallies, torch.int64, "tallies", dev), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                        _stream(dev)), "se3_seg_loss_fwd")
+        if lse is not None:
+            ctx.save_for_backward(x2, labels, lse, count)
+        ctx.counted, ctx.n_valid, ctx.smoothing, ctx.shape = counted, n_valid, float(label_smoothing), logits.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        f32, who = torch.float32, "SegLoss"
+        x2, labels, lse, count = ctx.saved_tensors
+        n, classes, dev = x2.shape[0], x2.shape[1], x2.device
+        g1 = _as(g, f32).reshape(1)
+        lab_ptr, bits = _seg_labels(labels, n, dev, who)
+        dx = _empty_like(x2)
+        _lib.check(_lib.load().se3_seg_loss_bwd(_ptr(x2, f32, "logits"), lab_ptr, bits,
+                                                _ptr(ctx.counted, torch.uint8, "counted", dev), _ptr(lse, torch.float64, "lse"),
+                                                _ptr(count, torch.int32, "count"), _ptr(g1, f32, "grad_loss", dev), n,
+                                                _valid_word(ctx.n_valid, dev, who), classes, ctx.smoothing,
+                                                _ptr(dx, f32, "grad_logits"), _stream(dev)), "se3_seg_loss_bwd")
+        return dx.reshape(ctx.shape), None, None, None, None, None
+
+
+def seg_loss(logits, labels, label_smoothing: float = 0.0, counted=None, n_valid: Optional[torch.Tensor] = None,
+             tallies: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 0-dim float32 loss of ``SegLoss``.  ``counted``: a ``[classes]`` uint8 device tensor (nonzero: the class counts), or
+    a sequence of the class ids that do NOT count (``counted_mask``), or None."""
+    if counted is not None and not isinstance(counted, torch.Tensor):
+        counted = counted_mask(logits.shape[-1], counted, logits.device)
+    return SegLoss.apply(logits, labels, label_smoothing, counted, n_valid, tallies)
+
+
 # ------------------------------------------------------------------------------- frames (row f-1)
-KNN_GRID_MIN_POINTS = 8192  # below this the all-pairs scan is as fast as sorting into cells
+KNN_GRID_MIN_POINTS = 8192 # below this the all-pairs scan is as fast as sorting into cells
 KNN_CELL_FACTOR = 1.6       # cell size / estimated k-NN distance (1.26 covers points on a face of the cloud)
 
 

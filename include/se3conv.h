@@ -150,7 +150,9 @@ int se3_batch_aabb(const float* pts, const int32_t* batch_ids, int64_t n, int32_
  *   over those cells and the maps back to the rows: mode sum = the gather of upsample_tensor (GridSubSample.py:93)
  *   and, as a pool, its gradient; avg / max / min unpool = the gradients of the pools (max / min route to the row
  *   that supplied the extremum, `arg` [n_cells,C] from the forward, like torch_scatter).
- * Modes: 0 avg, 1 max, 2 min, 3 sum.  Summation order is fixed (input order inside a cell). */
+ * Modes: 0 avg, 1 max, 2 min, 3 sum.  Summation order is fixed (input order inside a cell).  max / min: the first extremum
+ * in the cell's sorted_ids order wins -- a later row replaces it only on strict > / <, so -0.0 and +0.0 tie and a NaN never
+ * replaces -- and `arg` holds that row's id. */
 #define SE3_POOL_AVG 0
 #define SE3_POOL_MAX 1
 #define SE3_POOL_MIN 2
@@ -181,7 +183,8 @@ int se3_rows_scatter(const void* src, const int32_t* idx, int64_t n_src, int64_t
 
 /* Frame pooling (scope row f-3)  <-  PointcloudRotEquiv.feature_pooling (pc/PointcloudRotEquiv.py:224-251): the F rows
  * point*F + frame of x [n_points*F, C] -> out [n_points, C]; `arg` [n_points, C] (max / min only) = winning frame.
- * se3_frame_unpool is its gradient: grad_out [n_points, C] -> grad_x [n_points*F, C]. */
+ * se3_frame_unpool is its gradient: grad_out [n_points, C] -> grad_x [n_points*F, C].  max / min: the first frame that holds the
+ * extremum wins (a later frame replaces it only on strict > / <: -0.0 and +0.0 tie, a NaN never replaces). */
 int se3_frame_pool(const float* x, int64_t n_points, int32_t frames, int32_t channels, int32_t mode, float* out,
                    int32_t* arg, void* stream);
 int se3_frame_unpool(const float* grad_out, const int32_t* arg, int64_t n_points, int32_t frames, int32_t channels,

@@ -1632,7 +1632,7 @@ __global__ void segment_pool_kernel(const float* __restrict__ src, const int32_t
       const float v = src[(int64_t)id * c + ch];
       if (MODE == kPoolAvg || MODE == kPoolSum) {
         acc += v;
-      } else if (best < 0 || (MODE == kPoolMax ? v > acc : v < acc)) {  // first extremum wins (lowest row id)
+      } else if (best < 0 || (MODE == kPoolMax ? v > acc : v < acc)) {  // first extremum in sorted_ids order wins
         acc = v, best = id;
       }
     }

@@ -3,7 +3,12 @@ SkipDropPath / BiasGelu) against the plain torch fp32 formulation of the same st
 BatchNormPC / SkipConnection / DropPathPC / ResNetFormer run (layers/ResNetFormer.py:64-88).  The block as a whole is
 pinned by the reference fixture in test_gpu_network.py::test_reference_resnetformer_block_runs_unchanged (fused path);
 here: odd channel counts, single rows, empty tensors, the drop-path gate with frame-aware batch ids, and fused ==
-unfused on a whole block with drop path on.  Tolerance 2e-6 relative (fp32 element-wise maths, fp64 channel sums)."""
+unfused on a whole block with drop path on.  Tolerance 2e-6 relative (fp32 element-wise maths, fp64 channel sums).
+
+These comparisons are one norm per tensor against torch fp32 on data of one magnitude.  The same passes are held per element
+against a float64 reference, on every thread layout, past the grid cap, on data of uneven magnitude and on the gate's float32
+boundary, by tests/test_gpu_rowwise_passes.py (tests/rowwise_passes_reference.py); what stays particular to this file is said
+at each test."""
 import pytest
 import torch
 
@@ -23,6 +28,8 @@ def amd(built_library):
 
 @pytest.mark.parametrize("rows,c", [(1, 32), (7, 1), (1000, 3), (1000, 48), (70000, 64), (513, 260), (0, 16)])
 def test_batch_norm_train_matches_torch(amd, rows, c):
+    """(The arithmetic of every case is covered per element by test_gpu_rowwise_passes.py; particular to this test: torch's
+    own fp32 batch norm as the other side, and the empty tensor.)"""
     torch.manual_seed(rows + c)
     x = (torch.randn(rows, c, device=DEV) * 3 + 5).requires_grad_(True)   # mean >> 0: the variance must not cancel
     w = torch.randn(c, device=DEV).requires_grad_(True)
@@ -52,6 +59,8 @@ def test_batch_norm_train_matches_torch(amd, rows, c):
 
 @pytest.mark.parametrize("rows,c,frames,batches", [(1000, 64, 2, 3), (999, 48, 1, 4), (4096, 3, 4, 2), (0, 32, 2, 1)])
 def test_skip_with_drop_path_gate_matches_torch(amd, rows, c, frames, batches):
+    """(Covered per element, with draws on the float32 boundary of floor(keep + u), by test_gpu_rowwise_passes.py; particular
+    to this test: random draws, four frames per point, the empty tensor and the [1, C] shape of gamma's gradient.)"""
     torch.manual_seed(3)
     rows = rows // frames * frames
     x = torch.randn(rows, c, device=DEV, requires_grad=True)
@@ -86,6 +95,8 @@ def test_skip_with_drop_path_gate_matches_torch(amd, rows, c, frames, batches):
 
 @pytest.mark.parametrize("rows,c", [(1000, 128), (33, 6), (70000, 64)])
 def test_bias_gelu_matches_torch(amd, rows, c):
+    """(Fully covered per element by test_gpu_rowwise_passes.py, which also runs c = 64 past the grid cap; kept as the
+    comparison with torch's own fp32 GELU.)"""
     torch.manual_seed(4)
     z = (torch.randn(rows, c, device=DEV) * 2).requires_grad_(True)
     b = torch.randn(c, device=DEV, requires_grad=True)
@@ -102,7 +113,10 @@ def test_bias_gelu_matches_torch(amd, rows, c):
                                                   (1, 32, 5, True), (777, 13, 130, True), (0, 16, 8, True)])
 def test_linear_weight_gradient_on_the_row_split_gemm_matches_torch(amd, rows, n_in, n_out, bias):
     """ops.Linear: forward / input gradient are the BLAS GEMMs, the weight gradient is se3_linear_wgrad (fp32 MFMA, rows
-    split over the chip, fixed-order reduction) -- against torch.nn.functional.linear's own backward in fp64."""
+    split over the chip, fixed-order reduction) -- against torch.nn.functional.linear's own backward in fp64.  (The weight
+    gradient is held per element, at the row counts where the row ranges change shape, by test_gpu_rowwise_passes.py; particular
+    to this test: the headline shape of 512 ranges, the BLAS products of the forward pass and the input gradient, the bias
+    gradient and the empty tensor.)"""
     from se3conv3d_amd import ops
     torch.manual_seed(rows + n_in)
     x = torch.randn(rows, n_in, device=DEV, requires_grad=True)

@@ -300,6 +300,12 @@ int se3_csr_transpose_bounded(const int32_t* neighbors, int64_t n_rows, const in
  *   fe_neighbors[E',2] = (s*F_out+a, p*F_in+b) sorted by col0 and fe_ends[N_out*F_out]
  *   (inclusive).  E' = E*F_out*F_in.  Only needed for API parity / FeatBasisProj users; the
  *   fused operator below never materialises these.
+ *   Order inside a row: row s*F_out+a holds the edges of sample s in the order of `neighbors`,
+ *   and for each edge its F_in frame-edges with b ascending (b fastest); the F_out rows of a
+ *   sample follow each other with a ascending (blocks by a).  Frame-edge (e, a, b) of an edge e
+ *   of sample s therefore sits at F_in*F_out*start + a*deg*F_in + (e - start)*F_in + b, start =
+ *   ends[s-1], deg = ends[s] - start: the order a stable sort by col0 of the (e, a, b)-major
+ *   list gives.  desc and fe_neighbors share it.
  * ------------------------------------------------------------------------------------------- */
 int se3_rot_tensors(const float* pts_in, const float* pts_out, const float* frames_in,
                     const float* frames_out, const int32_t* neighbors, const int32_t* ends,
@@ -312,6 +318,10 @@ int se3_rot_tensors(const float* pts_in, const float* pts_out, const float* fram
  * formulation (this call + se3_feat_basis_proj); no shipped configuration uses them. */
 #define SE3_REL_ROT_6D 0
 #define SE3_REL_ROT_MATRIX 1
+/* The quaternion is the candidate of RotationFunctions.py:91-151 with the largest q_abs = sqrt(max(0, 1 +- m00 +- m11 +- m22)),
+ * divided by 2 max(q_abs, 0.1).  Tie rule: of equal q_abs the FIRST in the order (r, i, j, k) is taken, as torch.argmax
+ * does -- rotations by 90, 120 and 180 degrees about the axes and diagonals of the cube tie two- and four-fold, and the
+ * choice decides the sign of the whole quaternion. */
 #define SE3_REL_ROT_QUATERNION 2
 int se3_rot_tensors_rel(const float* pts_in, const float* pts_out, const float* frames_in,
                         const float* frames_out, const int32_t* neighbors, const int32_t* ends,

@@ -222,6 +222,19 @@ SEG_HEAD_CHUNK = 256         # SE3_SEG_HEAD_CHUNK: rows per chunk of the loss su
 SEG_HEAD_TILE_CLASSES = 56   # SE3_SEG_HEAD_TILE_CLASSES: the widest row the LDS-tile form of the kernels takes
 SEG_HEAD_MAX_CLASSES = 1024
 
+# point-neighbourhood embeddings (the five kernel-MLP activations, the three kernel-point correlations) and the max aggregation
+PNE_SIGNATURES = {
+    "se3_pne_embed_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
+    "se3_pne_embed_fwd": (C.c_int, [_P, _P, _P, _I64, _P, _I32, _P, _I32, _F, _P, _P, _I32, _P, _P]),
+    "se3_pne_embed_bwd": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I32, _P, _I32, _F, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
+    "se3_neigh_max_fwd": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P, _P]),
+    "se3_neigh_max_bwd": (C.c_int, [_P] * 9 + [_I64, _I64, _I64, _I32, _I32, _P, _P, _P]),
+}
+PNE_CHUNK = 1024     # SE3_PNE_CHUNK: edges per chunk of the order of additions of se3_pne_embed_bwd
+PNE_MAX_KPTS = 64    # SE3_PNE_MAX_KPTS
+# enum se3_pne_kind
+PNE_KINDS = {"mlp_linear": 0, "mlp_relu": 1, "mlp_gelu": 2, "mlp_sin": 3, "mlp_softmax": 4, "kp_gauss": 5, "kp_linear": 6, "kp_box": 7}
+
 # The third registry, and meant to be the last: tests/test_knn_edges_abi.py pins ADDED_TABLES to its one header the way
 # tests/test_abi_tables.py pins TABLES to seven, so a header after those stands here, under the same rule and with the same
 # checks from a test file of its own.  Such a test asserts that its header is IN this registry, never what the registry
@@ -230,6 +243,7 @@ EXTENSION_TABLES = {
     "se3conv_global_pool.h": GLOBAL_POOL_SIGNATURES,
     "se3conv_group_norm.h": GROUP_NORM_SIGNATURES,
     "se3conv_seg_head.h": SEG_HEAD_SIGNATURES,
+    "se3conv_pne.h": PNE_SIGNATURES,
 }
 
 _lib = None

@@ -18,6 +18,7 @@ from __future__ import annotations
 import math
 from abc import ABC, abstractmethod
 
+import numpy as np
 import torch
 
 from . import ops
@@ -275,16 +276,97 @@ class _IdentityFramed(object):
         self.n_frames_ = 1
 
 
+def create_pts_icosphere(subdiv, return_faces=False):
+    """The vertices ``[V,3]`` (float64, on the unit sphere) of an icosahedron whose triangles are split ``subdiv`` times:
+    12 vertices for 0, 42 for 1, ``10 * 4**subdiv + 2`` in general.  Vertices and order are those of the reference's function
+    of the same name (tests/golden/icosphere.npz holds its output), the construction is this package's own:
+
+      * two poles on the y axis and two rings of five at ``y = +-1/sqrt(5)``, 72 degrees apart in azimuth (measured from +z
+        towards +x), the lower ring turned by 36 degrees against the upper;
+      * the twenty faces in four bands of five -- the fan of the upper pole in ascending azimuth, the triangles that hang
+        from the upper ring in descending azimuth, the fan of the lower pole in descending azimuth, the triangles that stand
+        on the lower ring;
+      * a split puts the midpoint of every edge on the sphere, once per edge, in the order the faces meet their edges."""
+    s5 = math.sqrt(5.0)
+
+    def ring(y, deg):
+        a = math.radians(deg)
+        return (2.0 / s5 * math.sin(a), y, 2.0 / s5 * math.cos(a))
+
+    up = {d: ring(1.0 / s5, d) for d in range(0, 360, 72)}       # azimuth -> vertex of the upper ring
+    low = {d: ring(-1.0 / s5, d) for d in range(36, 360, 72)}
+    top, bottom = (0.0, 1.0, 0.0), (0.0, -1.0, 0.0)
+    verts = [top, up[0], low[180], bottom, low[252], up[288], low[108], up[72], low[36], low[324], up[144], up[216]]
+    at = {v: i for i, v in enumerate(verts)}
+    faces = [[at[top], at[up[(216 + 72 * i) % 360]], at[up[(288 + 72 * i) % 360]]] for i in range(5)]
+    faces += [[at[up[a % 360]], at[up[(a - 72) % 360]], at[low[(a - 36) % 360]]] for a in range(360, 0, -72)]
+    faces += [[at[bottom], at[low[a % 360]], at[low[(a - 72) % 360]]] for a in range(324, -36, -72)]
+    stand = [[at[low[a % 360]], at[low[(a + 72) % 360]], at[up[(a + 36) % 360]]] for a in range(252, -108, -72)]
+    stand[0] = stand[0][2:] + stand[0][:2]     # (the first of them is listed from its upper vertex)
+    faces += stand
+    verts = [list(v) for v in verts]
+    for _ in range(int(subdiv)):
+        cut = {}
+
+        def mid(i, j):
+            key = (min(i, j), max(i, j))
+            if key not in cut:
+                m = [(a + b) / 2 for a, b in zip(verts[i], verts[j])]
+                n = math.sqrt(sum(c * c for c in m))
+                verts.append([c / n for c in m])
+                cut[key] = len(verts) - 1
+            return cut[key]
+
+        split = []
+        for a, b, c in faces:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            split += [[a, ab, ca], [b, bc, ab], [c, ca, bc], [ab, bc, ca]]
+        faces = split
+    v = np.array(verts, dtype=np.float64)
+    return (v, np.array(faces)) if return_faces else v
+
+
+def _random_rotation() -> torch.Tensor:
+    """A rotation matrix ``[3,3]`` (float64) drawn uniformly: a unit quaternion from four normal variates."""
+    q = torch.randn(4, dtype=torch.float64)
+    w, x, y, z = (q / q.norm()).tolist()
+    return torch.tensor([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                         [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                         [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], dtype=torch.float64)
+
+
+# PNEConvLayer.py:104-134: (scale of the kernel points, sigma per correlation function) of the single and the double set
+_KP_SETS = {False: (0.6, {"linear": 0.4, "gauss": 0.3, "box": 1.0}), True: (0.35, {"linear": 0.2, "gauss": 0.16, "box": 1.0})}
+PNE_TYPES = tuple(_ACTIVATIONS) + tuple(f"kp_{c}{d}" for d in ("", "_double") for c in ("linear", "gauss", "box"))
+_FEAT_BASIS_K = (8, 16, 32, 64)  # the K of se3_feat_basis_proj (the reference's CUDA op: feat_basis_utils.cuh:35-41)
+
+
+def kernel_points(p_pne_type: str):
+    """The unrotated kernel points ``[J,3]`` (float64) of a ``kp_*`` type: the icosahedron and the origin, scaled by 0.6
+    (J = 13), or for ``*_double`` the icosahedron at 0.35, its first split at 0.7 and the origin (J = 55)."""
+    double = "double" in p_pne_type
+    scale = _KP_SETS[double][0]
+    sets = [create_pts_icosphere(0) * scale] + ([create_pts_icosphere(1) * scale * 2] if double else [])
+    return np.concatenate(sets + [np.zeros((1, 3))])
+
+
 class PNEConvLayer(IConvLayer):
-    """The reference's non-equivariant continuous convolution (``layers/PNEConvLayer.py:47-229``, scope row f-4),
-    ``mlp_gelu`` embedding with ``add`` aggregation:
+    """The reference's non-equivariant continuous convolution (``layers/PNEConvLayer.py:47-229``, scope row f-4):
 
-        out[s,o] = nu * sum_{(s,p) in E} sum_k sum_i GELU(rho (x_p - y_s) . A + beta)_k * f[p,i] * W[i,k,o]
+        add:  out[s,o] = nu * sum_{(s,p) in E} sum_k sum_i phi(rho (x_p - y_s))_k * f[p,i] * W[i,k,o]
+        max:  out[s,o] = nu * max_{(s,p) in E} sum_k sum_i phi(rho (x_p - y_s))_k * f[p,i] * W[i,k,o]      (0 without an edge)
 
-    It runs through the same HIP operator as the equivariant layer: with one identity frame per point the
-    9-D descriptor of the fused kernel is ``[rho (x_p - y_s), 1,0,0, 0,1,0]``, so the ``[3,K]`` projection axes
-    are padded with six zero rows (whose gradient rows are dropped by autograd's ``cat``).  Parameter / buffer
-    names and shapes are the reference's (``proj_axes_ [3,K]``, ``proj_biases_ [K]``, ``conv_weights_ [C_in,K,C_out]``).
+    with every embedding ``phi`` of the reference (``PNE_TYPES``): the kernel MLP ``act(r . A + beta)`` with five activations,
+    and the kernel-point embeddings ``corr(|r - kp_j| / sigma) . A + beta`` (KPConv-style; ``kernel_pts_ [J,3]`` is a buffer,
+    randomly rotated once at construction).  Parameter / buffer names and shapes are the reference's (``proj_axes_ [3,K]`` or
+    ``[J,K]``, ``proj_biases_ [K]``, ``conv_weights_ [C_in,K,C_out]``).
+
+    ``mlp_gelu`` with ``add`` runs through the same HIP operator as the equivariant layer: with one identity frame per point
+    the 9-D descriptor of the fused kernel is ``[rho (x_p - y_s), 1,0,0, 0,1,0]``, so the ``[3,K]`` projection axes are padded
+    with six zero rows (whose gradient rows are dropped by autograd's ``cat``).  Every other ``add`` configuration is
+    ``ops.PneEmbed -> ops.FeatBasisProj -> einsum`` (K in {8, 16, 32, 64}, as that operator); ``max`` is ``ops.PneEmbed``, one dense
+    product ``G = f @ W`` and ``ops.NeighConvMax``.  The output always has one row per output point (DESIGN.md "Quirks").
+    Capacity-bounded neighbourhoods (``p_capacity``) feed the fused path only.
     """
 
     def __init__(self, p_dims, p_in_features, p_out_features, p_num_basis, p_pne_type, p_aggregation="add"):
@@ -292,16 +374,57 @@ class PNEConvLayer(IConvLayer):
         self.num_basis_ = p_num_basis
         self.pne_type_ = p_pne_type
         self.aggregation_ = p_aggregation
-        if p_pne_type != "mlp_gelu" or p_aggregation != "add" or p_dims != 3:
-            raise NotImplementedError("PNEConvLayer on the HIP operator: 'mlp_gelu' embedding, 'add' aggregation, 3-D points")
-        bound = math.sqrt(1.0 / p_dims)
-        self.proj_axes_ = torch.nn.Parameter(torch.empty(p_dims, p_num_basis).uniform_(-bound, bound))
+        if p_dims != 3:
+            raise NotImplementedError("PNEConvLayer on the HIP library: 3-D points")
+        if p_pne_type not in PNE_TYPES:
+            raise ValueError(f"unknown pne type {p_pne_type!r}: expected one of {PNE_TYPES}")
+        if p_aggregation not in ("add", "max"):
+            raise ValueError(f"unknown aggregation {p_aggregation!r}: expected 'add' or 'max'")
+        self.fused_ = p_pne_type == "mlp_gelu" and p_aggregation == "add"
+        if p_aggregation == "add" and not self.fused_ and p_num_basis not in _FEAT_BASIS_K:
+            raise ValueError(f"PNEConvLayer('{p_pne_type}', 'add') aggregates through FeatBasisProj, which takes a number of basis "
+                             f"functions in {set(_FEAT_BASIS_K)}, not {p_num_basis}")
+        if "kp" in p_pne_type:
+            # the correlation function by substring: the reference's `if` chain (:195-200) compares whole names and leaves
+            # it unset for the *_double types (DESIGN.md "Quirks")
+            corr = next(c for c in ("linear", "gauss", "box") if c in p_pne_type)
+            self.embed_kind_ = "kp_" + corr
+            self.kp_sigma_ = _KP_SETS["double" in p_pne_type][1][corr]
+            kp = torch.from_numpy(kernel_points(p_pne_type)) @ _random_rotation()
+            self.register_buffer("kernel_pts_", kp.to(torch.float32))
+            n_in = kp.shape[0]
+        else:
+            self.embed_kind_ = p_pne_type
+            n_in = p_dims
+        bound = math.sqrt(1.0 / n_in)
+        self.proj_axes_ = torch.nn.Parameter(torch.empty(n_in, p_num_basis).uniform_(-bound, bound))
         self.proj_biases_ = torch.nn.Parameter(torch.zeros((p_num_basis,), dtype=torch.float32))
         bound = math.sqrt(1.0 / (p_in_features * p_num_basis))
         self.conv_weights_ = torch.nn.Parameter(
             torch.empty(p_in_features, p_num_basis, p_out_features).uniform_(-bound, bound))
 
+    def _conv_embedded(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
+        """Every configuration but ``mlp_gelu`` + ``add``: the embedding of the edges, then the aggregation."""
+        if getattr(p_neighborhood, "edge_info_", None) is not None:
+            raise NotImplementedError("a capacity-bounded neighbourhood (rows past the edge count are unset) cannot feed "
+                                      "the materialised path: build the neighbourhood without p_capacity")
+        nb32 = getattr(p_neighborhood, "neighbors_i32_", None)
+        if nb32 is None:
+            nb32 = p_neighborhood.neighbors_
+        phi = ops.PneEmbed.apply(p_pc_in.pts_, p_pc_out.pts_, nb32, self.proj_axes_, self.proj_biases_, self.norm_neigh_dist_,
+                                 self.embed_kind_, getattr(self, "kernel_pts_", None), getattr(self, "kp_sigma_", 0.0))
+        if self.aggregation_ == "add":
+            t = ops.FeatBasisProj.apply(phi, p_in_features, nb32, p_neighborhood.start_ids_)
+            out = torch.einsum("nik,iko->no", t, self.conv_weights_)
+        else:
+            c_in, k, c_out = self.conv_weights_.shape
+            g = torch.matmul(p_in_features, self.conv_weights_.reshape(c_in, k * c_out)).reshape(-1, k, c_out)
+            out, _ = ops.NeighConvMax.apply(phi, g, nb32, p_neighborhood.start_ids_, p_in_features.shape[0], p_neighborhood)
+        return out * self.norm_num_neighs_
+
     def __compute_convolution__(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
+        if not self.fused_:
+            return self._conv_embedded(p_pc_in, p_pc_out, p_in_features, p_neighborhood)
         pc_in = _IdentityFramed(p_pc_in)
         pc_out = pc_in if p_pc_out is p_pc_in else _IdentityFramed(p_pc_out)
         cache = getattr(p_neighborhood, "_se3_geom_plain", None)

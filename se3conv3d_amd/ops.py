@@ -1839,6 +1839,164 @@ class FeatBasisProj(torch.autograd.Function):
         return g_basis.to(p_ctx.dtypes[0]), g_feat.to(p_ctx.dtypes[1]), None, None
 
 
+# ------------------------------------------- point-neighbourhood embeddings and max aggregation (include/se3conv_pne.h)
+def _pne_call(kind: str, kpts, sigma):
+    """enum value, kernel points, their count and sigma as the entry points of se3conv_pne.h take them."""
+    if kind not in _lib.PNE_KINDS:
+        raise ValueError(f"embedding kind {kind!r}; expected one of {sorted(_lib.PNE_KINDS)}")
+    if not kind.startswith("kp_"):
+        return _lib.PNE_KINDS[kind], None, 0, 0.0
+    if kpts is None or kpts.dim() != 2 or kpts.shape[1] != 3 or not 1 <= kpts.shape[0] <= _lib.PNE_MAX_KPTS:
+        raise ValueError(f"{kind}: kernel points are [J,3] with 1 <= J <= {_lib.PNE_MAX_KPTS}")
+    return _lib.PNE_KINDS[kind], _as(kpts, torch.float32), kpts.shape[0], float(sigma)
+
+
+class PneEmbed(torch.autograd.Function):
+    """``phi [E,K]`` of ``se3_pne_embed_fwd``: the embedding of every edge's relative position, activation included --
+    ``kind`` is a key of ``_lib.PNE_KINDS`` ("mlp_linear", "mlp_relu", "mlp_gelu", "mlp_sin", "mlp_softmax", "kp_gauss",
+    "kp_linear", "kp_box").  Gradients go to ``proj_axes`` and ``proj_biases`` only, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, pts, samples, neighbors, proj_axes, proj_biases, norm_dist, kind, kpts=None, sigma=0.0):
+        lib = _lib.load()
+        f32, i32 = torch.float32, torch.int32
+        code, kp, n_kp, sig = _pne_call(kind, kpts, sigma)
+        x, y, nb = _as(pts, f32), _as(samples, f32), _as(neighbors, i32)
+        a, b = _as(proj_axes, f32), _as(proj_biases, f32).reshape(-1)
+        dev = x.device
+        if x.dim() != 2 or x.shape[1] != 3 or y.dim() != 2 or y.shape[1] != 3:
+            raise ValueError("PneEmbed: only [N,3] point sets are supported")
+        if nb.dim() != 2 or nb.shape[1] != 2:
+            raise ValueError("neighbors must be [E,2]")
+        k = b.shape[0]
+        if tuple(a.shape) != ((n_kp if kp is not None else 3), k):
+            raise ValueError(f"{kind}: proj_axes of shape {tuple(a.shape)}, expected {((n_kp if kp is not None else 3), k)}")
+        rho = _scalar(norm_dist, "norm_dist", dev)
+        phi = _empty((nb.shape[0], k), dtype=f32, device=dev)
+        _lib.check(lib.se3_pne_embed_fwd(_ptr(x, f32, "pts"), _ptr(y, f32, "samples", dev), _ptr(nb, i32, "neighbors", dev),
+                                         nb.shape[0], _ptr(rho, f32, "norm_dist"), code, _ptr(kp, f32, "kernel_pts", dev), n_kp,
+                                         sig, _ptr(a, f32, "proj_axes", dev), _ptr(b, f32, "proj_biases", dev), k,
+                                         _ptr(phi, f32, "phi"), _stream(dev)), "se3_pne_embed_fwd")
+        ctx.save_for_backward(x, y, nb, a, b, rho, *(() if kp is None else (kp,)))
+        ctx.call = (code, n_kp, sig, proj_axes.dtype, proj_biases.dtype, tuple(proj_biases.shape))
+        return phi
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f32, i32 = torch.float32, torch.int32
+        x, y, nb, a, b, rho, *rest = ctx.saved_tensors
+        kp = rest[0] if rest else None
+        code, n_kp, sig, dt_a, dt_b, shape_b = ctx.call
+        g = _as(g, f32)
+        dev = x.device
+        k = b.shape[0]
+        d_a, d_b = _empty_like(a), _empty_like(b)
+        ws = _workspace(lib.se3_pne_embed_workspace_bytes(nb.shape[0], code, n_kp, k), dev)
+        _lib.check(lib.se3_pne_embed_bwd(_ptr(g, f32, "grad_phi", dev), _ptr(x, f32, "pts"), _ptr(y, f32, "samples"),
+                                         _ptr(nb, i32, "neighbors"), nb.shape[0], _ptr(rho, f32, "norm_dist"), code,
+                                         _ptr(kp, f32, "kernel_pts"), n_kp, sig, _ptr(a, f32, "proj_axes"),
+                                         _ptr(b, f32, "proj_biases"), k, _ptr(d_a, f32, "dA"), _ptr(d_b, f32, "dbeta"),
+                                         C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_pne_embed_bwd")
+        return None, None, None, d_a.to(dt_a), d_b.reshape(shape_b).to(dt_b), None, None, None, None
+
+
+class LinearPNE(torch.autograd.Function):
+    """Drop-in for ``point_cloud_lib.custom_ops.LinearPNE`` (PNE.py:3-61): ``rho (x_src - y_smp) @ A + b`` per edge."""
+
+    @staticmethod
+    def forward(p_ctx, p_pts, p_samples, p_neighbors, p_proj_axes, p_proj_biases, p_norm_dist):
+        return PneEmbed.forward(p_ctx, p_pts, p_samples, p_neighbors, p_proj_axes, p_proj_biases, p_norm_dist, "mlp_linear")
+
+    @staticmethod
+    def backward(p_ctx, p_grads):
+        return PneEmbed.backward(p_ctx, p_grads)[:6]
+
+
+class KPPNE(torch.autograd.Function):
+    """Drop-in for ``point_cloud_lib.custom_ops.KPPNE`` (PNE.py:64-164): the correlation of every edge with the kernel points
+    (``p_corr_func`` "gauss", "linear" or "box"), projected by ``p_proj_axes [J,K]``."""
+
+    @staticmethod
+    def forward(p_ctx, p_pts, p_samples, p_neighbors, p_kpts, p_sigma, p_proj_axes, p_proj_biases, p_norm_dist, p_corr_func):
+        if p_corr_func not in ("gauss", "linear", "box"):
+            raise ValueError(f"correlation function {p_corr_func!r}; expected 'gauss', 'linear' or 'box'")
+        return PneEmbed.forward(p_ctx, p_pts, p_samples, p_neighbors, p_proj_axes, p_proj_biases, p_norm_dist,
+                                "kp_" + p_corr_func, p_kpts, p_sigma)
+
+    @staticmethod
+    def backward(p_ctx, p_grads):
+        g = PneEmbed.backward(p_ctx, p_grads)
+        return None, None, None, None, None, g[3], g[4], None, None
+
+
+def neigh_transposition(neighbors_i32: torch.Tensor, n_src: int, cache=None):
+    """``(t_samples, t_ends, t_edge_ids)`` of ``se3_csr_transpose`` for ``NeighConvMax``; with ``cache`` (the neighbourhood
+    object) built once and kept on it, as the convolution's backward keeps its own on the geometry."""
+    key = (neighbors_i32.data_ptr(), neighbors_i32.shape[0], int(n_src))
+    held = getattr(cache, "_se3_max_transpose", None) if cache is not None else None
+    if held is not None and held[0] == key:
+        return held[1]
+    tr = csr_transpose(neighbors_i32, int(n_src), want_edge_ids=True)
+    if cache is not None:
+        try:
+            cache._se3_max_transpose = (key, tr)
+        except AttributeError:
+            pass
+    return tr
+
+
+class NeighConvMax(torch.autograd.Function):
+    """``out[m,o] = max_e sum_k phi[e,k] G[src_e,k,o]`` over the edges of sample ``m`` (``se3_neigh_max_fwd``): the reference's
+    ``TransformNeighConv`` + ``scatter_max`` on transformed features ``G [N,K,C_out]`` (``feat @ W.reshape(C_in, K * C_out)``), which
+    costs ``K * C_out`` per edge and never forms an ``E x C_in x C_out`` kernel.  Always ``M = len(ends)`` rows; a sample without edges
+    gets zeros.  ``cache``: an object (the neighbourhood) that keeps the source-major transposition the backward needs."""
+
+    @staticmethod
+    def forward(ctx, phi, G, neighbors, ends, n_src, cache=None):
+        lib = _lib.load()
+        f32, i32 = torch.float32, torch.int32
+        ph, g3 = _as(phi, f32), _as(G, f32)
+        nb, en = _as(neighbors, i32), _as(ends, i32)
+        dev = ph.device
+        e, k = ph.shape
+        if g3.dim() != 3 or g3.shape[0] != int(n_src) or g3.shape[1] != k:
+            raise ValueError(f"NeighConvMax: G of shape {tuple(g3.shape)}, expected [{int(n_src)}, {k}, C_out]")
+        if nb.dim() != 2 or nb.shape[1] != 2 or nb.shape[0] != e:
+            raise ValueError("neighbors must be [E,2], one row per row of phi")
+        m, c = en.shape[0], g3.shape[2]
+        out = _empty((m, c), dtype=f32, device=dev)
+        arg = _empty((m, c), dtype=i32, device=dev)
+        _lib.check(lib.se3_neigh_max_fwd(_ptr(ph, f32, "phi"), _ptr(g3, f32, "G", dev), _ptr(nb, i32, "neighbors", dev),
+                                         _ptr(en, i32, "ends", dev), e, m, int(n_src), k, c, _ptr(out, f32, "out"),
+                                         _ptr(arg, i32, "arg"), _stream(dev)), "se3_neigh_max_fwd")
+        ctx.save_for_backward(ph, g3, nb, en, arg)
+        ctx.cache, ctx.dtypes = cache, (phi.dtype, G.dtype)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, g, _g_arg=None):
+        lib = _lib.load()
+        f32, i32 = torch.float32, torch.int32
+        ph, g3, nb, en, arg = ctx.saved_tensors
+        g = _as(g, f32)
+        dev = ph.device
+        e, k = ph.shape
+        n_src, c = g3.shape[0], g3.shape[2]
+        if e:
+            ts, te, tid = neigh_transposition(nb, n_src, ctx.cache)
+        else:  # nothing to transpose: every source has no incoming edge
+            ts, te, tid = None, torch.zeros(n_src, dtype=i32, device=dev), None
+        dphi, dg = _empty_like(ph), _empty_like(g3)
+        _lib.check(lib.se3_neigh_max_bwd(_ptr(g, f32, "grad_out", dev), _ptr(arg, i32, "arg"), _ptr(ph, f32, "phi"),
+                                         _ptr(g3, f32, "G"), _ptr(nb, i32, "neighbors"), _ptr(en, i32, "ends"),
+                                         _ptr(ts, i32, "t_samples"), _ptr(te, i32, "t_ends"), _ptr(tid, i32, "t_edge_ids"), e,
+                                         en.shape[0], n_src, k, c, _ptr(dphi, f32, "dphi"), _ptr(dg, f32, "dG"), _stream(dev)),
+                   "se3_neigh_max_bwd")
+        return dphi.to(ctx.dtypes[0]), dg.to(ctx.dtypes[1]), None, None, None, None
+
+
 # ------------------------------------------------------------------ row-wise glue of a block (row f-3)
 def _glue_ws(c: int, dev) -> torch.Tensor:
     return _workspace(_lib.load().se3_glue_workspace_bytes(int(c)), dev)

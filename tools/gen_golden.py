@@ -542,6 +542,66 @@ def pne_case(pclib, seed, n_in, n_out, c_in, c_out, k_deg, batches):
     }
 
 
+PNE_KINDS_ADD = ("mlp_gelu", "mlp_relu", "mlp_sin", "mlp_softmax", "mlp_linear", "kp_gauss", "kp_linear", "kp_box")
+PNE_KINDS_MAX = ("kp_gauss", "mlp_relu", "mlp_softmax")
+
+
+def pne_kinds_case(pclib, seed, n_in=300, n_out=150, c_in=5, c_out=24, num_basis=16, k_deg=12, batches=2):
+    """Every embedding of the reference's PNEConvLayer that its own code can run, aggregation 'add', and 'max' for three of
+    them: one shared geometry (two batch elements, the last sample has a neighbour -- the reference's scatter_max drops
+    trailing empty rows), one feature tensor and one output gradient; per case the parameters as drawn (the rotated
+    `kernel_pts_` among them), out, dx, dA, dbeta, dW.  The `*_double` types are not here: the reference's
+    __compute_convolution__ leaves their correlation function unset and raises (PNEConvLayer.py:195-200)."""
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    pts_in = torch.rand(n_in, 3)
+    bid_in = torch.sort(torch.randint(0, batches, (n_in,), dtype=torch.int32)).values
+    pts_out = torch.rand(n_out, 3)
+    bid_out = torch.sort(torch.randint(0, batches, (n_out,), dtype=torch.int32)).values
+    pc_in, pc_out = pclib.pc.Pointcloud(pts_in, bid_in), pclib.pc.Pointcloud(pts_out, bid_out)
+    r = _radius(n_in / batches, k_deg)
+    neigh = pclib.pc.BQNeighborhood(pc_in, pc_out, r)
+    ends = neigh.start_ids_.numpy().astype(np.int32)
+    assert ends[-1] > ends[-2], "the last sample needs a neighbour"
+    x0 = torch.randn(n_in, c_in)
+    g = torch.randn(n_out, c_out)
+    rho = torch.tensor(1.0 / r, dtype=torch.float32)
+    nu = torch.tensor(neigh.start_ids_.shape[0] / neigh.neighbors_.shape[0], dtype=torch.float32)
+    data = {"pts_in": pts_in.numpy(), "pts_out": pts_out.numpy(), "batch_in": bid_in.numpy(), "batch_out": bid_out.numpy(),
+            "radius": np.float64(r), "neighbors": neigh.neighbors_.numpy().astype(np.int32), "ends": ends,
+            "rho": rho.numpy(), "nu": nu.numpy(), "x": x0.numpy(), "grad_out": g.numpy(),
+            "empty_samples": np.int32((np.diff(np.concatenate([[0], ends])) == 0).sum())}
+    cases = [(t, "add") for t in PNE_KINDS_ADD] + [(t, "max") for t in PNE_KINDS_MAX]
+    for pne_type, agg in cases:
+        conv = pclib.layers.PNEConvLayerFactory(3, num_basis, pne_type, agg).create_conv_layer(c_in, c_out)
+        with torch.no_grad():
+            conv.proj_biases_.uniform_(-0.5, 0.5)
+        conv.norm_neigh_dist_, conv.norm_num_neighs_ = rho, nu
+        x = x0.clone().requires_grad_(True)
+        out = conv(p_pc_in=pc_in, p_pc_out=pc_out, p_in_features=x, p_neighborhood=neigh)
+        assert out.shape == g.shape
+        out.backward(g)
+        key = f"{pne_type}/{agg}/"
+        if hasattr(conv, "kernel_pts_"):
+            data[key + "kernel_pts"] = conv.kernel_pts_.numpy()
+            data[key + "sigma"] = np.float32(conv.kp_sigma_)
+        data.update({key + "proj_axes": conv.proj_axes_.detach().numpy(), key + "proj_biases": conv.proj_biases_.detach().numpy(),
+                     key + "conv_weights": conv.conv_weights_.detach().numpy(), key + "out": out.detach().numpy(),
+                     key + "dx": x.grad.numpy(), key + "dA": conv.proj_axes_.grad.numpy(),
+                     key + "dbeta": conv.proj_biases_.grad.numpy(), key + "dW": conv.conv_weights_.grad.numpy()})
+    return data
+
+
+def icosphere_case(pclib):
+    """The reference's create_pts_icosphere at 0, 1 and 2 splits: vertices (and the faces, which fix the vertex order of the
+    next split)."""
+    data = {}
+    for s in (0, 1, 2):
+        v, f = pclib.layers.create_pts_icosphere(s, True)
+        data[f"verts{s}"], data[f"faces{s}"] = v, f.astype(np.int32)
+    return data
+
+
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from seeded_params import seeded_conv_params as _seeded_conv_params  # noqa: E402  (shared with the tests that replay the fixtures)
@@ -832,6 +892,22 @@ def main():
             np.savez_compressed(path, **data)
             print(f"{path}: size={os.path.getsize(path) / 1e6:.2f} MB")
     if only == "group_norm":
+        return
+    if only in ("", "pne_kinds"):
+        for name, data in (("embedding_kinds.npz", pne_kinds_case(pclib, 41)), ("icosphere.npz", icosphere_case(pclib))):
+            path = os.path.join(OUT, name)
+            np.savez_compressed(path, **data)
+            print(f"{path}: size={os.path.getsize(path) / 1e6:.2f} MB")
+        import json
+        types_ = list(PNE_KINDS_ADD) + [f"kp_{c}_double" for c in ("gauss", "linear", "box")]
+        keys = {}
+        for pne_type in types_:      # the reference's constructor runs for every type, the *_double ones included
+            conv = pclib.layers.PNEConvLayerFactory(3, 16, pne_type).create_conv_layer(5, 24)
+            keys[pne_type] = {"state": {k: list(v.shape) for k, v in conv.state_dict().items()},
+                              "sigma": getattr(conv, "kp_sigma_", None)}
+        with open(os.path.join(OUT, "pne_layer_keys.json"), "w") as fh:
+            json.dump(keys, fh, indent=1, sort_keys=True)
+    if only == "pne_kinds":
         return
     for name, seed, n_in, n_out, c_in, c_out, k, b in PNE_CASES:
         path = os.path.join(OUT, f"{name}.npz")

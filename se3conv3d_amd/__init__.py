@@ -2,12 +2,13 @@
 
 Layout mirrors the slice of ``point_cloud_lib`` that the path touches:
 
-  se3conv3d_amd.layers   PNEConvLayerRotEquiv(+Factory), PNEConvLayer(+Factory), IConvLayer(+Factory), PreProcessModule
+  se3conv3d_amd.layers   PNEConvLayerRotEquiv(+Factory), PNEConvLayer(+Factory), MultiHeadAttLayer(+Factory), LoRAttConvLayer(+Factory),
+                         IConvLayer(+Factory), PreProcessModule
   se3conv3d_amd.blocks   ResNetFormer, ResNetB, ResConvNeXt, SkipConnection, DropPathPC, BatchNormPC, GroupNormPC (torch glue
                          around the conv)
   se3conv3d_amd.pc       Pointcloud(RotEquiv), BQNeighborhood, PointHierarchy(RotEquiv), frame sampling
-  se3conv3d_amd.ops      FeatBasisProj, BallQuery, ComputeKeys, SE3ConvFunction, SegLoss, LinearPNE, KPPNE, PneEmbed, NeighConvMax
-                         (ctypes -> C ABI)
+  se3conv3d_amd.ops      FeatBasisProj, BallQuery, ComputeKeys, SE3ConvFunction, SegLoss, LinearPNE, KPPNE, PneEmbed, NeighConvMax,
+                         BasisAttention (ctypes -> C ABI)
   se3conv3d_amd.metrics  SemSegMetrics: the reference's counters, kept on the device (include/se3conv_seg_head.h)
   se3conv3d_amd.csrc     HIP kernels + the extern "C" boundary (include/se3conv.h)
 
@@ -16,10 +17,11 @@ not been built (``python -m se3conv3d_amd.build``).
 """
 from . import blocks, layers, metrics, ops, pc  # noqa: F401
 from .blocks import BatchNormPC, DropPathPC, GroupNormPC, ResConvNeXt, ResNetB, ResNetFormer, SkipConnection  # noqa: F401
-from .layers import (IConvLayer, IConvLayerFactory, PNEConvLayer, PNEConvLayerFactory,  # noqa: F401
+from .layers import (IConvLayer, IConvLayerFactory, LoRAttConvLayer, LoRAttConvLayerFactory, MultiHeadAttLayer,  # noqa: F401
+                     MultiHeadAttLayerFactory, PNEConvLayer, PNEConvLayerFactory,
                      PNEConvLayerRotEquiv, PNEConvLayerRotEquivFactory, PreProcessModule, create_pts_icosphere)
 from .metrics import SemSegMetrics  # noqa: F401
-from .ops import (KPPNE, BallQuery, ComputeKeys, FeatBasisProj, KNNQuery, LinearPNE, NeighConvMax, PneEmbed,  # noqa: F401
+from .ops import (KPPNE, BallQuery, BasisAttention, ComputeKeys, FeatBasisProj, KNNQuery, LinearPNE, NeighConvMax, PneEmbed,  # noqa: F401
                   SE3ConvFunction, SegLoss, get_precision, seg_loss, set_precision)
 from .pc import (BQNeighborhood, KnnNeighborhood, Pointcloud, PointcloudRotEquiv, PointHierarchy,  # noqa: F401
                  PointHierarchyRotEquiv)

@@ -235,14 +235,26 @@ PNE_MAX_KPTS = 64    # SE3_PNE_MAX_KPTS
 # enum se3_pne_kind
 PNE_KINDS = {"mlp_linear": 0, "mlp_relu": 1, "mlp_gelu": 2, "mlp_sin": 3, "mlp_softmax": 4, "kp_gauss": 5, "kp_linear": 6, "kp_box": 7}
 
+# the attention stage of MultiHeadAttLayer / LoRAttConvLayer: a softmax per point and head over the basis functions of [N, 2V, K]
+BASIS_ATT_SIGNATURES = {
+    "se3_basis_att_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
+    "se3_basis_att_fwd": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P]),
+    "se3_basis_att_bwd": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+}
+BASIS_ATT_CHUNK = 256        # SE3_BASIS_ATT_CHUNK: points per chunk of the order of additions of dpe
+BASIS_ATT_MAX_BASIS = 64     # SE3_BASIS_ATT_MAX_BASIS
+
 # The third registry, and meant to be the last: tests/test_knn_edges_abi.py pins ADDED_TABLES to its one header the way
 # tests/test_abi_tables.py pins TABLES to seven, so a header after those stands here, under the same rule and with the same
 # checks from a test file of its own.  Such a test asserts that its header is IN this registry, never what the registry
-# equals: the next header is one more line here and one more test file.
+# equals: the next header is one more line here and one more test file.  One of them did pin a position all the same:
+# tests/test_pne_abi.py holds "se3conv_pne.h" to the END of this registry, and test files do not change, so a header added
+# after it (se3conv_basis_att.h was the first) goes in FRONT of that line; the order here means nothing else.
 EXTENSION_TABLES = {
     "se3conv_global_pool.h": GLOBAL_POOL_SIGNATURES,
     "se3conv_group_norm.h": GROUP_NORM_SIGNATURES,
     "se3conv_seg_head.h": SEG_HEAD_SIGNATURES,
+    "se3conv_basis_att.h": BASIS_ATT_SIGNATURES,
     "se3conv_pne.h": PNE_SIGNATURES,
 }
 

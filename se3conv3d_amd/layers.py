@@ -470,6 +470,119 @@ class PNEConvLayerFactory(IConvLayerFactory):
         return PNEConvLayer(self.dims_, p_in_features, p_out_features, self.num_basis_, self.pne_type_, self.aggregation_)
 
 
+_KP_RES = {"single": "kp_gauss", "double": "kp_gauss_double"}  # p_kp_res -> the kernel-point set (and sigma) of that PNE type
+
+
+class MultiHeadAttLayer(IConvLayer):
+    """The reference's multi-head attention over the basis functions (``layers/MultiHeadAttLayer.py:11-150``):
+
+        phi = kp_gauss(rho (x_p - y_s)) @ proj_axes_ + proj_biases_                      per edge, [E,K]
+        [q v | key] = linear_kqv_(f)                                                      [N,2V] and [N,V], V = C_in
+        T[s,c,k] = sum_{(s,p) in E} phi_k [q v][p,c]                                      FeatBasisProj, [N,2V,K]
+        att[s,k,h] = softmax_k sum_{i in head h} (Tq[s,i,k] + pe_[k,i]) key[s,i]          ops.BasisAttention, one HIP pass
+        out[s] = nu * w_out_(sum_k Tv[s,:,k] att[s,k,h(:)])
+
+    Parameters and buffers by the reference's names and shapes (``kernel_pts_ [13|55,3]``, ``proj_axes_ [J,K]``, ``proj_biases_ [K]``,
+    ``linear_kqv_``, ``w_out_``, ``pe_ [1,K,V]``) and its init bounds; the kernel points are rotated once with a uniformly drawn
+    rotation.  As in the reference there is no ``1/sqrt(D)`` and the bias of ``w_out_`` is scaled by ``nu`` too (DESIGN.md "Quirks").
+    ``p_num_basis`` is one of FeatBasisProj's; input and output cloud are one object; capacity-bounded neighbourhoods are refused."""
+
+    def __init__(self, p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads):
+        super().__init__(p_dims, p_in_features, p_out_features)
+        if p_dims != 3:
+            raise NotImplementedError(f"{type(self).__name__} on the HIP library: 3-D points")
+        if p_kp_res not in _KP_RES:
+            raise ValueError(f"unknown kernel-point resolution {p_kp_res!r}: expected 'single' or 'double'")
+        if p_num_heads < 1 or p_in_features % p_num_heads != 0:
+            raise ValueError(f"{p_num_heads} heads do not divide the {p_in_features} input features")
+        if p_num_basis not in _FEAT_BASIS_K:
+            raise ValueError(f"{type(self).__name__} aggregates through FeatBasisProj, which takes a number of basis functions in "
+                             f"{set(_FEAT_BASIS_K)}, not {p_num_basis}")
+        self.num_basis_ = p_num_basis
+        self.kp_res_ = p_kp_res
+        self.num_heads_ = p_num_heads
+        self.value_size_ = p_in_features
+        self.kp_sigma_ = _KP_SETS[p_kp_res == "double"][1]["gauss"]
+        kp = torch.from_numpy(kernel_points(_KP_RES[p_kp_res])) @ _random_rotation()
+        self.register_buffer("kernel_pts_", kp.to(torch.float32))
+        bound = math.sqrt(1.0 / kp.shape[0])
+        self.proj_axes_ = torch.nn.Parameter(torch.empty(kp.shape[0], p_num_basis).uniform_(-bound, bound))
+        self.proj_biases_ = torch.nn.Parameter(torch.zeros((p_num_basis,), dtype=torch.float32))
+        self.linear_kqv_ = torch.nn.Linear(p_in_features, 3 * self.value_size_)
+        self.w_out_ = torch.nn.Linear(self.value_size_, p_out_features)
+        bound = math.sqrt(1.0 / self.value_size_)
+        self.pe_ = torch.nn.Parameter(torch.empty(1, p_num_basis, self.value_size_).uniform_(-bound, bound))
+
+    def _attend(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
+        """``(w_out_(attention), T)``: steps 1 to 5, before the scaling."""
+        if p_pc_in is not p_pc_out:
+            raise AssertionError(f"{type(self).__name__}: the input and the output cloud must be the same object, as in the reference")
+        if getattr(p_neighborhood, "edge_info_", None) is not None:
+            raise NotImplementedError("a capacity-bounded neighbourhood (rows past the edge count are unset) cannot feed "
+                                      "the materialised path: build the neighbourhood without p_capacity")
+        nb32 = getattr(p_neighborhood, "neighbors_i32_", None)
+        if nb32 is None:
+            nb32 = p_neighborhood.neighbors_
+        v = self.value_size_
+        phi = ops.PneEmbed.apply(p_pc_in.pts_, p_pc_out.pts_, nb32, self.proj_axes_, self.proj_biases_, self.norm_neigh_dist_,
+                                 "kp_gauss", self.kernel_pts_, self.kp_sigma_)
+        x = self.linear_kqv_(p_in_features)
+        t = ops.FeatBasisProj.apply(phi, x[:, :2 * v], nb32, p_neighborhood.start_ids_)
+        agg = ops.BasisAttention.apply(t, x[:, 2 * v:], self.pe_, self.num_heads_)
+        return self.w_out_(agg), t
+
+    def __compute_convolution__(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
+        return self._attend(p_pc_in, p_pc_out, p_in_features, p_neighborhood)[0] * self.norm_num_neighs_
+
+
+class LoRAttConvLayer(MultiHeadAttLayer):
+    """The reference's low-rank attention convolution (``layers/LoRAttConvLayer.py:11-163``): ``MultiHeadAttLayer`` plus an ordinary
+    continuous convolution on the value half of the same aggregate, ``sum_{k,i} Tv[s,i,k] conv_weights_[k,i,o]``, both scaled by
+    ``nu``.  ``conv_weights_ [K,V,C_out]`` as in the reference; the product reads ``Tv`` as a view of ``T``."""
+
+    def __init__(self, p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads):
+        super().__init__(p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads)
+        bound = math.sqrt(1.0 / (self.value_size_ * p_num_basis))
+        self.conv_weights_ = torch.nn.Parameter(torch.empty(p_num_basis, self.value_size_, p_out_features).uniform_(-bound, bound))
+
+    def __compute_convolution__(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
+        att, t = self._attend(p_pc_in, p_pc_out, p_in_features, p_neighborhood)
+        v, k = self.value_size_, self.num_basis_
+        w = self.conv_weights_.permute(1, 0, 2).reshape(v * k, self.feat_output_size_)
+        conv = torch.matmul(t[:, :v, :].reshape(t.shape[0], v * k), w)
+        return (att + conv) * self.norm_num_neighs_
+
+
+class MultiHeadAttLayerFactory(IConvLayerFactory):
+    """``layers/MultiHeadAttLayer.py:153-202``."""
+
+    _layer = MultiHeadAttLayer
+
+    def __init__(self, p_dims, p_num_basis, p_kp_res, p_num_heads):
+        super().__init__(p_dims)
+        self.num_basis_ = p_num_basis
+        self.kp_res_ = p_kp_res
+        self.num_heads_ = p_num_heads
+
+    def update_parameters(self, **kwargs):
+        # an `elif` chain, as in the reference: only the first key present is applied (DESIGN.md "Quirks")
+        if "num_basis" in kwargs:
+            self.num_basis_ = kwargs["num_basis"]
+        elif "kp_res" in kwargs:
+            self.kp_res_ = kwargs["kp_res"]
+        elif "num_heads" in kwargs:
+            self.num_heads_ = kwargs["num_heads"]
+
+    def __create_conv_layer_imp__(self, p_in_features, p_out_features):
+        return self._layer(self.dims_, p_in_features, p_out_features, self.num_basis_, self.kp_res_, self.num_heads_)
+
+
+class LoRAttConvLayerFactory(MultiHeadAttLayerFactory):
+    """``layers/LoRAttConvLayer.py:166-215``."""
+
+    _layer = LoRAttConvLayer
+
+
 class PNEConvLayerRotEquivFactory(IConvLayerFactory):
     def __init__(self, p_dims, p_num_basis, p_pne_type, p_rel_rot="6D"):
         super().__init__(p_dims)

@@ -1997,6 +1997,74 @@ class NeighConvMax(torch.autograd.Function):
         return dphi.to(ctx.dtypes[0]), dg.to(ctx.dtypes[1]), None, None, None, None
 
 
+# ------------------------------------------- attention over the basis functions (include/se3conv_basis_att.h)
+def _key_rows(key: torch.Tensor, v: int) -> Tuple[torch.Tensor, int]:
+    """``key [N,V]`` as the library reads it and its row stride in floats: a float32 view with unit inner stride (the last
+    third of a ``[N,3V]`` projection) is passed as it is, anything else is made contiguous."""
+    k = key.detach()
+    if k.dtype == torch.float32 and k.dim() == 2 and k.stride(1) == 1 and k.stride(0) >= v and k.shape[0] > 1:
+        return k, k.stride(0)
+    return k.to(torch.float32).contiguous(), v
+
+
+class BasisAttention(torch.autograd.Function):
+    """The attention stage of ``MultiHeadAttLayer`` / ``LoRAttConvLayer`` (``se3_basis_att_fwd`` / ``_bwd``): with ``T [N,2V,K]`` as
+    ``FeatBasisProj`` gives it for ``2V`` channels (value rows first, query rows second), ``key [N,V]`` and ``pe [K,V]`` or ``[1,K,V]``,
+
+        s[n,k,h] = sum_{i in head h} (Tq[n,i,k] + pe[k,i]) * key[n,i],   att = softmax_k(s),   out[n,i] = sum_k Tv[n,i,k] * att[n,k,h(i)]
+
+    and returns ``out [N,V]`` (no ``1/sqrt(D)``, as the reference).  Gradients go to ``T``, ``key`` and ``pe``.  ``T`` is read in its own
+    layout: no transposed copy and no ``N x K x V`` intermediate."""
+
+    @staticmethod
+    def forward(ctx, T, key, pe, num_heads):
+        lib = _lib.load()
+        f32 = torch.float32
+        for name, x in (("T", T), ("key", key), ("pe", pe)):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda:
+                raise ValueError(f"BasisAttention: {name} must be a GPU tensor (the HIP path has no CPU fallback)")
+        t = _as(T, f32)
+        if t.dim() != 3 or t.shape[1] % 2:
+            raise ValueError(f"BasisAttention: T of shape {tuple(T.shape)}, expected [N, 2V, K]")
+        n, v, k = t.shape[0], t.shape[1] // 2, t.shape[2]
+        h = int(num_heads)
+        if h < 1 or v % h:
+            raise ValueError(f"BasisAttention: {h} heads do not divide the value size {v}")
+        if not 1 <= k <= _lib.BASIS_ATT_MAX_BASIS:
+            raise ValueError(f"BasisAttention: {k} basis functions, expected 1 .. {_lib.BASIS_ATT_MAX_BASIS}")
+        if tuple(key.shape) != (n, v):
+            raise ValueError(f"BasisAttention: key of shape {tuple(key.shape)}, expected {(n, v)}")
+        if tuple(pe.shape) not in ((k, v), (1, k, v)):
+            raise ValueError(f"BasisAttention: pe of shape {tuple(pe.shape)}, expected {(k, v)} or {(1, k, v)}")
+        kr, stride = _key_rows(key, v)
+        p = _as(pe, f32).reshape(k, v)
+        dev = t.device
+        att = _empty((n, k, h), dtype=f32, device=dev)
+        out = _empty((n, v), dtype=f32, device=dev)
+        _lib.check(lib.se3_basis_att_fwd(_ptr(t, f32, "T"), C.c_void_p(kr.data_ptr()), stride, _ptr(p, f32, "pe", dev), n, v, h, k,
+                                         _ptr(att, f32, "att"), _ptr(out, f32, "out"), _stream(dev)), "se3_basis_att_fwd")
+        ctx.save_for_backward(t, kr, p, att)
+        ctx.call = (h, stride, T.dtype, key.dtype, pe.dtype, tuple(pe.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f32 = torch.float32
+        t, kr, p, att = ctx.saved_tensors
+        h, stride, dt_t, dt_key, dt_pe, shape_pe = ctx.call
+        n, v, k = t.shape[0], t.shape[1] // 2, t.shape[2]
+        g = _as(g, f32)
+        dev = t.device
+        d_t, d_key, d_pe = _empty_like(t), _empty((n, v), dtype=f32, device=dev), _empty_like(p)
+        ws = _workspace(lib.se3_basis_att_workspace_bytes(n, v, h, k), dev)
+        _lib.check(lib.se3_basis_att_bwd(_ptr(g, f32, "grad_out", dev), _ptr(t, f32, "T"), C.c_void_p(kr.data_ptr()), stride,
+                                         _ptr(p, f32, "pe"), _ptr(att, f32, "att"), n, v, h, k, _ptr(d_t, f32, "dT"),
+                                         _ptr(d_key, f32, "dkey"), _ptr(d_pe, f32, "dpe"), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                         _stream(dev)), "se3_basis_att_bwd")
+        return d_t.to(dt_t), d_key.to(dt_key), d_pe.reshape(shape_pe).to(dt_pe), None
+
+
 # ------------------------------------------------------------------ row-wise glue of a block (row f-3)
 def _glue_ws(c: int, dev) -> torch.Tensor:
     return _workspace(_lib.load().se3_glue_workspace_bytes(int(c)), dev)

@@ -592,6 +592,58 @@ def pne_kinds_case(pclib, seed, n_in=300, n_out=150, c_in=5, c_out=24, num_basis
     return data
 
 
+ATTENTION_CASES = [(layer, res, heads) for layer in ("mha", "lora") for res, heads in (("single", 2), ("double", 4))]
+ATTENTION_FACTORIES = {"mha": "MultiHeadAttLayerFactory", "lora": "LoRAttConvLayerFactory"}
+
+
+def attention_case(pclib, seed, n=300, c_in=8, c_out=24, num_basis=16, k_deg=12, batches=2):
+    """The reference's MultiHeadAttLayer and LoRAttConvLayer (layers/MultiHeadAttLayer.py, layers/LoRAttConvLayer.py) with the
+    single and the double kernel-point set: one geometry (two batch elements, the same cloud in and out), one feature tensor and
+    one output gradient; per case every parameter as drawn (biases, `pe_` and `proj_biases_` non-zero), the rotated
+    `kernel_pts_`, out, dx and the gradient of every parameter."""
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    pts = torch.rand(n, 3)
+    bid = torch.sort(torch.randint(0, batches, (n,), dtype=torch.int32)).values
+    pc = pclib.pc.Pointcloud(pts, bid)
+    r = _radius(n / batches, k_deg)
+    neigh = pclib.pc.BQNeighborhood(pc, pc, r)
+    x0 = torch.randn(n, c_in)
+    g = torch.randn(n, c_out)
+    rho = torch.tensor(1.0 / r, dtype=torch.float32)
+    nu = torch.tensor(neigh.start_ids_.shape[0] / neigh.neighbors_.shape[0], dtype=torch.float32)
+    data = {"pts": pts.numpy(), "batch": bid.numpy(), "radius": np.float64(r),
+            "neighbors": neigh.neighbors_.numpy().astype(np.int32), "ends": neigh.start_ids_.numpy().astype(np.int32),
+            "rho": rho.numpy(), "nu": nu.numpy(), "x": x0.numpy(), "grad_out": g.numpy()}
+    for layer, res, heads in ATTENTION_CASES:
+        conv = getattr(pclib.layers, ATTENTION_FACTORIES[layer])(3, num_basis, res, heads).create_conv_layer(c_in, c_out)
+        with torch.no_grad():
+            conv.proj_biases_.uniform_(-0.5, 0.5)
+        conv.norm_neigh_dist_, conv.norm_num_neighs_ = rho, nu
+        x = x0.clone().requires_grad_(True)
+        out = conv(p_pc_in=pc, p_pc_out=pc, p_in_features=x, p_neighborhood=neigh)
+        assert out.shape == g.shape
+        out.backward(g)
+        key = f"{layer}/{res}/"
+        data[key + "heads"], data[key + "sigma"] = np.int32(heads), np.float32(conv.kp_sigma_)
+        data[key + "kernel_pts_"] = conv.kernel_pts_.numpy()
+        data[key + "out"], data[key + "dx"] = out.detach().numpy(), x.grad.numpy()
+        for name, p in conv.named_parameters():
+            assert p.grad is not None and float(p.detach().abs().max()) > 0, name
+            data[key + "param/" + name], data[key + "grad/" + name] = p.detach().numpy(), p.grad.numpy()
+    return data
+
+
+def attention_keys(pclib):
+    """State-dict keys and shapes, and sigma, of both attention layers for both kernel-point resolutions."""
+    keys = {}
+    for layer, factory in ATTENTION_FACTORIES.items():
+        for res in ("single", "double"):
+            conv = getattr(pclib.layers, factory)(3, 16, res, 2).create_conv_layer(8, 24)
+            keys[f"{layer}/{res}"] = {"state": {k: list(v.shape) for k, v in conv.state_dict().items()}, "sigma": conv.kp_sigma_}
+    return keys
+
+
 def icosphere_case(pclib):
     """The reference's create_pts_icosphere at 0, 1 and 2 splits: vertices (and the faces, which fix the vertex order of the
     next split)."""
@@ -833,6 +885,16 @@ def main():
         return
     pclib = _import_reference()
     os.makedirs(OUT, exist_ok=True)
+    if only == "attention":      # (only on request: a plain run keeps the recorded draws of these two fixtures)
+        path = os.path.join(OUT, "attention_layers.npz")
+        np.savez_compressed(path, **attention_case(pclib, 43))
+        print(f"{path}: size={os.path.getsize(path) / 1e6:.2f} MB")
+        return
+    if only == "attention_keys":
+        import json
+        with open(os.path.join(OUT, "attention_layer_keys.json"), "w") as fh:
+            json.dump(attention_keys(pclib), fh, indent=1, sort_keys=True)
+        return
     if only in ("", "hierarchy"):
         path = os.path.join(OUT, "hierarchy.npz")
         np.savez_compressed(path, **hierarchy_case(pclib, 11))

@@ -12,10 +12,10 @@ Pinning (see DESIGN.md "Oracle"):
     golden fixtures generated from the reference's own Python (``tools/gen_golden.py``
     imports ``/root/reference/point_cloud_lib`` with stand-ins for the three native
     modules that are not installed; fixtures under ``tests/golden/``).
-  * the arithmetic of the two CUDA ops (``feat_basis_proj{,_grad}``) and of the CUDA
-    ball query cannot be executed here (no nvcc, no GPU): for those this file follows the
-    CUDA sources line by line (citations below) and their semantics are pinned only by the
-    reference's Python call sites -> "parity unpinned" for the native arithmetic itself.
+  * the arithmetic of the native ops (``feat_basis_proj{,_grad}``, ball query, keys, kNN) is restated here from the CUDA
+    sources line by line (citations below) and, since ``oracle/build_ref.py`` compiles those sources for the device, held
+    to the kernels themselves on an MI355X (``tests/test_gpu_reference_kernels.py``; DESIGN.md section 5 lists what is
+    pinned by execution and what is still restatement only).
 
 Conventions:
   rows of feature tensors are ``point * F + frame``; frames are ``[N, F, 9]`` row-major

@@ -13,11 +13,19 @@ copied): ``PNEConvLayerRotEquivFactory`` / ``PNEConvLayerRotEquiv`` (forward thr
 (``ResNetFormer``, ``ResNetB``, ``ResConvNeXt``, ``BatchNormPC``, ``GroupNormPC``: ``python tools/gen_golden.py group_norm``
 writes the three fixtures of the group norm alone).
 
-What is NOT the reference: three native modules are not installed here and cannot be built
-(no nvcc): ``point_cloud_lib_ops`` (CUDA), ``torch_scatter``, ``torch_cluster``.  The
-stand-ins below are deliberately naive loop/index_add implementations of their documented
-semantics, written independently of ``oracle/se3conv_oracle.py`` so the fixtures cross-check
-the oracle instead of echoing it.  Everything stored is data (inputs + outputs), no source.
+What is NOT the reference: three native modules are not installed here: ``point_cloud_lib_ops``
+(CUDA), ``torch_scatter``, ``torch_cluster``.  The stand-ins below are deliberately naive
+loop/index_add implementations of their documented semantics, written independently of
+``oracle/se3conv_oracle.py`` so the fixtures cross-check the oracle instead of echoing it.
+Everything stored is data (inputs + outputs), no source.
+
+The stand-ins for ``point_cloud_lib_ops`` remain: the fixtures are generated on the CPU, and the
+reference's own module, which ``oracle/build_ref.py`` now compiles for gfx950 into ``oracle/_ref/``,
+runs on the device only.  That compiled module cross-checks the stand-ins there:
+``tests/test_gpu_reference_kernels.py`` recomputes every ``layer_*.npz`` with T and its gradients
+from the compiled ``feat_basis_proj{,_grad}`` and holds the result to the recorded outputs, and runs
+the compiled ``ball_query`` / ``compute_keys`` / ``knn_query`` beside the oracle that these
+stand-ins agree with.
 
 One fixture does not come from the reference: ``python tools/gen_golden.py workspace_plan`` records the answers of this
 library's own host-only queries (see ``workspace_plan_case``); only on request, never as part of a plain run.

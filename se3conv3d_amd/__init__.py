@@ -10,12 +10,14 @@ Layout mirrors the slice of ``point_cloud_lib`` that the path touches:
   se3conv3d_amd.ops      FeatBasisProj, BallQuery, ComputeKeys, SE3ConvFunction, SegLoss, LinearPNE, KPPNE, PneEmbed, NeighConvMax,
                          BasisAttention (ctypes -> C ABI)
   se3conv3d_amd.metrics  SemSegMetrics: the reference's counters, kept on the device (include/se3conv_seg_head.h)
+  se3conv3d_amd.augment  AugPipeline and the reference's augmentation classes on a whole batch (include/se3conv_augment.h)
   se3conv3d_amd.csrc     HIP kernels + the extern "C" boundary (include/se3conv.h)
 
 Importing the package does not load the HIP library; the first op call does and raises if it has
 not been built (``python -m se3conv3d_amd.build``).
 """
-from . import blocks, layers, metrics, ops, pc  # noqa: F401
+from . import augment, blocks, layers, metrics, ops, pc  # noqa: F401
+from .augment import AugmentedBatch, AugPipeline, Augmentation  # noqa: F401
 from .blocks import BatchNormPC, DropPathPC, GroupNormPC, ResConvNeXt, ResNetB, ResNetFormer, SkipConnection  # noqa: F401
 from .layers import (IConvLayer, IConvLayerFactory, LoRAttConvLayer, LoRAttConvLayerFactory, MultiHeadAttLayer,  # noqa: F401
                      MultiHeadAttLayerFactory, PNEConvLayer, PNEConvLayerFactory,

@@ -244,6 +244,25 @@ BASIS_ATT_SIGNATURES = {
 BASIS_ATT_CHUNK = 256        # SE3_BASIS_ATT_CHUNK: points per chunk of the order of additions of dpe
 BASIS_ATT_MAX_BASIS = 64     # SE3_BASIS_ATT_MAX_BASIS
 
+# the augmentation pipeline on a batch: statistics per element, the affine table, apply + noise, keep masks, compaction
+_U32 = C.c_uint32
+_D = C.POINTER(C.c_double)   # host: the constants of a step
+AUGMENT_SIGNATURES = {
+    "se3_aug_stats_workspace_bytes": (_SZ, [_I64, _I32]),
+    "se3_aug_stats": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "se3_aug_affine_step": (C.c_int, [_I32, _D, _F, _P, _P, _P, _I32, _P, _P]),
+    "se3_aug_apply": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _I32, _P, _F, _F, _F, _F, _U32, _P, _U32, _P, _P, _P]),
+    "se3_aug_keep_mask": (C.c_int, [_I32, _D, _F, _P, _P, _I64, _P, _I32, _P, _P, _U32, _P, _U32, _P, _P]),
+    "se3_aug_compact_workspace_bytes": (_SZ, [_I64]),
+    "se3_aug_compact": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+}
+AUG_CHUNK = 256      # SE3_AUG_CHUNK: rows per chunk of the order of additions of se3_aug_stats
+AUG_DRAWS = 8        # SE3_AUG_DRAWS: uniform numbers per (step, element); column 0 is the gate
+AUG_CONSTS = 12      # SE3_AUG_CONSTS
+# enum se3_aug_kind
+AUG_KINDS = {"rot_axis": 0, "rot_3d": 1, "center": 2, "linear": 3, "mirror": 4, "translation": 5, "stdnorm": 6,
+             "drop": 16, "crop_box": 17, "crop_pts": 18}
+
 # The third registry, and meant to be the last: tests/test_knn_edges_abi.py pins ADDED_TABLES to its one header the way
 # tests/test_abi_tables.py pins TABLES to seven, so a header after those stands here, under the same rule and with the same
 # checks from a test file of its own.  Such a test asserts that its header is IN this registry, never what the registry
@@ -255,6 +274,7 @@ EXTENSION_TABLES = {
     "se3conv_group_norm.h": GROUP_NORM_SIGNATURES,
     "se3conv_seg_head.h": SEG_HEAD_SIGNATURES,
     "se3conv_basis_att.h": BASIS_ATT_SIGNATURES,
+    "se3conv_augment.h": AUGMENT_SIGNATURES,
     "se3conv_pne.h": PNE_SIGNATURES,
 }
 

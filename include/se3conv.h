@@ -560,6 +560,10 @@ int se3_profile_tags(char* buf, size_t len);
  *   SE3_TR_MERGE_SORT     se3_csr_transpose*: the merge-sort form for every graph, same result
  *   SE3_DX_PATH           feature gradient edge-major: 1 wherever implemented, 0 never; default: the two-term cost model of
  *                         DESIGN.md section 4.11 (microseconds of either form; never above 20 edges per source row)
+ *                         A second field, SE3_DX_PATH=<dx>,dense=<n> (<dx> = -1: the cost model), sets the other decision of the
+ *                         backward plan: the dense products (gemm_gradT, gemm_gradX, gemm_gradW) of an under-filled level run as
+ *                         roles of one launch on levels of at most n rows (default 32768); dense=0 =
+ *                         separate launches at every size (tests/test_gpu_bwd_dense_shared.py compares the two bit for bit)
  * (Removed in round 6 with their code: SE3_SLICE_MB / SE3_SLICE_STREAMS, the row-sliced schedule of round 5 that lost every
  *  A/B -- profiles/r05_slice_ab.txt; SE3_PAIR_PERSIST / SE3_PAIR_OCC.)
  * (Removed since with their code: SE3_OVERLAP / SE3_OVERLAP_ROWS, the two-stream backward pass; SE3_BWD_BRANCH_ORDER;

@@ -29,6 +29,8 @@ HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "edge_bf16_body.h"
     os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.TABLES]  # every header of the pinned C surface
 ADDED_HEADERS = [os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.ADDED_TABLES]  # ... and those added since
 EXTENSION_HEADERS = [os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.EXTENSION_TABLES]  # the third registry
+# the kernel bodies gemm_bf16.hip includes as text (once per stand-alone kernel, once per role of the shared launch)
+BODY_TEXTS = [os.path.join(CSRC, name) for name in ("gemm_nn_bf16_body.h", "gemm_nn_t24_body.h", "gemm_tn_bf16_body.h")]
 ARCH = "gfx950"
 # -fno-slp-vectorize: the SLP pass packs adjacent fp32 ops into v_pk_fma_f32 / v_pk_mul_f32, which issue slower than the
 # two scalar ops they replace on gfx950 (edge_t_fwd at the headline shape: 0.55 ms packed, 0.44 ms scalar) and need
@@ -72,7 +74,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJDIR, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + HEADERS + ADDED_HEADERS + EXTENSION_HEADERS):
+        if force or _stale(o, [s] + HEADERS + ADDED_HEADERS + EXTENSION_HEADERS + BODY_TEXTS):
             jobs.append([hipcc, *FLAGS, "-c", s, "-o", o])
 
     def run(cmd):

@@ -33,6 +33,10 @@ const Switches& switches() {
     v.dx_path = dx ? atoi(dx) : -1;
     const char* es = getenv("SE3_EDGE_STREAM");  // n > 0: n items; anything else: never
     v.edge_stream_min_items = es ? (atoi(es) > 0 ? atoi(es) : INT32_MAX) : 4096;
+    // a second field of the same variable, "<dx>,dense=<n>", gates the shared launch of backward's dense products (the other
+    // decision of plan_bwd): n > 0: levels of up to n rows; anything else: never.  (<dx> = -1 is the cost model, as without it.)
+    const char* ds = dx ? strstr(dx, "dense=") : nullptr;
+    v.dense_share_rows = ds ? (atoll(ds + 6) > 0 ? atoll(ds + 6) : 0) : kDenseShareRows;
     return v;
   }();
   return sw;
@@ -379,6 +383,7 @@ struct BwdPlan {
   bool grad_t;         // grad_T is computed: for the parameter gradients, and as the operand of the edge-major form ...
   bool strip_t;        // ... by the row-strip GEMM (else the tiled one); the weights are prepared in its fragment layout
   int fmt_t, fmt_u;    // row formats of T and of U (row_format)
+  bool share_dense;    // the dense products (grad_T, grad_X, the weight gradient's) run as roles of one launch: plan_dense_shared
   struct { int64_t m; int ka, n, splits; } tn;  // the weight gradient's TN product: over the rows of U or over those of T
   int n_param_partials;
   // Workspace offsets.  `big`: grad_T, and U when grad_T is not there at the same time.  `u`, `split_x`: where U and the
@@ -414,6 +419,25 @@ bool plan_edge_major(const se3conv_shape* s, bool want_params) {
   return 15.0 + d_bytes / 2.2e6 < 45.0 + u_bytes / 6.0e6;
 }
 
+// Whether the dense products of a backward call share a launch (gemm_bf16.hip, bwd_dense_shared_kernel).  On a level that
+// does not fill the chip the products are launches one after the other on a machine none of them fills; as roles of one
+// grid they run side by side and the level saves a launch per role.  Decided from the shape and the request: split-bf16
+// arithmetic; a level of at most Switches::dense_share_rows rows on either side (the gate: profiles/bwd_dense_shared.txt;
+// SE3_DX_PATH=-1,dense=0 forces separate launches); every product the request can run is one the shared kernel has a body for
+// (the buffer-load forms over packed words and 3-byte rows -- not the T16 rows, not the guarded-load forms); at least two
+// products.  A call that passes no grad_weights runs one product fewer: with one left it launches that one as ever.
+bool plan_dense_shared(const se3conv_shape* s, const BwdPlan& p, bool want_params) {
+  const int64_t rows_out = s->n_out * s->f_out, rows_in = s->n_in * s->f_in, gate = switches().dense_share_rows;
+  if (!p.fast || rows_in <= 0 || rows_out <= 0 || rows_in > gate || rows_out > gate) return false;
+  const int ck = s->c_in * s->num_basis, cok = s->c_out * s->num_basis;
+  const bool x_role = p.feat_branch && p.feat == FeatGrad::u;
+  if ((int)p.grad_t + (int)x_role + (int)want_params < 2) return false;
+  if (p.grad_t && !p.strip_t && !gemm_nn_bf16_sharable(rows_out, ck, s->c_out, true, 0)) return false;
+  if (x_role && !gemm_nn_bf16_sharable(rows_in, s->c_in, cok, false, p.fmt_u)) return false;
+  if (want_params && !gemm_tn_bf16_sharable(p.tn.m, p.tn.ka, p.tn.n, p.tn.splits, p.dw == WeightGrad::u ? p.fmt_u : p.fmt_t)) return false;
+  return true;
+}
+
 BwdPlan plan_bwd(const se3conv_shape* s, bool want_feat, bool want_params, bool have_t) {
   BwdPlan p{};
   const size_t kb = s->num_basis;
@@ -441,6 +465,7 @@ BwdPlan plan_bwd(const se3conv_shape* s, bool want_feat, bool want_params, bool 
   else p.tn = {(int64_t)rows_out, ck, s->c_out, 0};
   p.tn.splits = gemm_tn_splits(p.tn.m, p.tn.ka, p.tn.n);
   p.n_param_partials = edge_param_grad_blocks((int64_t)rows_out);
+  p.share_dense = plan_dense_shared(s, p, want_params);
 
   // The workspace.  Callers cache these sizes: a reservation that is wider than its use (the packed feature words although
   // the caller may bring them, se3conv_prepared; the grad_X planes of a U form on zero rows) stays as wide.
@@ -955,11 +980,49 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
     if (int rc = launch_edge_t_bf16("edge_t_transposed", gt, gpk, s->c_out, rows_out, axes_ext, rho, u, stream, p.fmt_u))
       return rc;
   }
+  // The dense products.  On an under-filled level (BwdPlan::share_dense) those this call runs are the roles of ONE launch
+  // right behind the U writer -- they read U, g, f and T and write grad_T, dX and the weight gradient's partials, nothing of
+  // each other's -- and the launchers below only describe their product to `shared`; with one product left nothing is shared.
+  DenseShare shared;
+  ReduceBatch shared_sums;  // the partial sums of the shared roles: they join final_sums where those of separate launches do
+  DenseShare* const share = p.share_dense && (int)p.grad_t + (int)u_form + (int)(grad_weights != nullptr) >= 2 ? &shared : nullptr;
+  const uint32_t* t_rows = (const uint32_t*)t_save;  // the weight gradient's T, where it reads T
+  auto recompute_t = [&]() -> int {
+    if (!grad_weights || p.dw != WeightGrad::t_recomputed) return SE3_OK;
+    uint32_t* tt = (uint32_t*)(ws + p.t);
+    t_rows = tt;
+    return launch_edge_t_bf16("edge_t_recompute", g, featpk, s->c_in, rows_in, axes_ext, rho, tt, stream, p.fmt_t);
+  };
+  auto grad_x = [&]() -> int {
+    return launch_gemm_nn_bf16("gemm_gradX", u, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
+                               (float*)(ws + p.split_x), nu, inv_phi, stream, p.fmt_u, share ? &shared_sums : &final_sums, share);
+  };
+  auto grad_w = [&]() -> int {
+    if (p.dw == WeightGrad::u)  // C'[(o,k), i] = sum_p U[p,(o,k)] f[p,i]; the batched reduction stores it as dW[i,k,o]
+      return launch_gemm_tn_bf16("gemm_gradW", u, featpk, grad_weights, tn_partials, p.tn.splits, p.tn.m, p.tn.ka, p.tn.n, nu,
+                                 inv_phi, stream, p.fmt_u, share ? &shared_sums : &final_sums, true, share);
+    // dW[(i,k),o] = sum_m T[m,(i,k)] g[m,o]
+    return launch_gemm_tn_bf16("gemm_gradW", t_rows, gpk, grad_weights, tn_partials, p.tn.splits, p.tn.m, p.tn.ka, p.tn.n, nu,
+                               inv_phi, stream, p.fmt_t, share ? &shared_sums : &final_sums, false, share);
+  };
+  if (share) {  // (a recomputed T is an operand of the shared launch: written in front of it)
+    if (int rc = recompute_t()) return rc;
+    shared.next_order = 2;  // in the grid: the long k loops of grad_X first, the short strips of grad_T last
+  }
   if (p.grad_t) {  // grad_T[m,(i,k)] = sum_o g[m,o] W'[i,k,o] into `big`
-    if (int rc = p.strip_t ? launch_gemm_strip_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, rows_out, ck, s->c_out, stream)
+    if (int rc = p.strip_t ? launch_gemm_strip_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, rows_out, ck, s->c_out, stream, share)
                            : launch_gemm_nn_bf16("gemm_gradT", gpk, bt_hi, bt_lo, bigw, true, rows_out, ck, s->c_out,
-                                                 (float*)(ws + p.split), nullptr, 1.0f, stream))
+                                                 (float*)(ws + p.split), nullptr, 1.0f, stream, 0, nullptr, share))
       return rc;
+  }
+  if (share) {
+    shared.next_order = 0;
+    if (u_form)
+      if (int rc = grad_x()) return rc;
+    shared.next_order = 1;
+    if (grad_weights)
+      if (int rc = grad_w()) return rc;
+    if (int rc = shared.launch(stream)) return rc;
   }
   if (edge_major) {  // the feature gradient per frame-edge from grad_T, then its per-source sums
     float* d_rows = (float*)(ws + p.dx_rows);
@@ -977,27 +1040,13 @@ extern "C" int se3conv_bwd_prepared(const float* pts_in, const float* pts_out, c
       return rc;
     final_sums.params(partials, n_part, grad_axes, grad_biases, 0.5f);
   }
-  if (u_form) {
-    if (int rc = launch_gemm_nn_bf16("gemm_gradX", u, bx_hi, bx_lo, grad_feat, false, rows_in, s->c_in, s->c_out * kb,
-                                     (float*)(ws + p.split_x), nu, inv_phi, stream, p.fmt_u, &final_sums))
-      return rc;
-  }
-  if (grad_weights) {
-    if (p.dw == WeightGrad::u) {  // C'[(o,k), i] = sum_p U[p,(o,k)] f[p,i]; the batched reduction stores it as dW[i,k,o]
-      if (int rc = launch_gemm_tn_bf16("gemm_gradW", u, featpk, grad_weights, tn_partials, p.tn.splits, p.tn.m, p.tn.ka, p.tn.n,
-                                       nu, inv_phi, stream, p.fmt_u, &final_sums, true))
-        return rc;
-    } else {  // dW[(i,k),o] = sum_m T[m,(i,k)] g[m,o]
-      const uint32_t* t = (const uint32_t*)t_save;
-      if (p.dw == WeightGrad::t_recomputed) {
-        uint32_t* tt = (uint32_t*)(ws + p.t);
-        if (int rc = launch_edge_t_bf16("edge_t_recompute", g, featpk, s->c_in, rows_in, axes_ext, rho, tt, stream, p.fmt_t)) return rc;
-        t = tt;
-      }
-      if (int rc = launch_gemm_tn_bf16("gemm_gradW", t, gpk, grad_weights, tn_partials, p.tn.splits, p.tn.m, p.tn.ka, p.tn.n, nu,
-                                       inv_phi, stream, p.fmt_t, &final_sums))
-        return rc;
-    }
+  for (int i = 0; i < shared_sums.jobs.count; ++i) final_sums.jobs.job[final_sums.jobs.count++] = shared_sums.jobs.job[i];
+  if (!share) {
+    if (u_form)
+      if (int rc = grad_x()) return rc;
+    if (int rc = recompute_t()) return rc;
+    if (grad_weights)
+      if (int rc = grad_w()) return rc;
   }
   return final_sums.launch(stream);
 }

@@ -387,7 +387,9 @@ struct Switches {
   bool no_t24, no_pair, pg_single, tr_merge_sort;  // SE3_NO_T24, SE3_NO_PAIR, SE3_PG_SINGLE, SE3_TR_MERGE_SORT: set at all
   int dx_path;                // SE3_DX_PATH.  -1: cost model, 0: never, 1: wherever implemented
   int edge_stream_min_items;  // SE3_EDGE_STREAM.  4096 by default
+  int64_t dense_share_rows;   // SE3_DX_PATH's field "dense=".  Levels of at most this many rows share a launch (plan_bwd); 0: never
 };
+constexpr int64_t kDenseShareRows = 32768;  // the default gate of the shared launch of backward's dense products (api.hip: plan_dense_shared)
 const Switches& switches();   // the process's switches, read from the environment once, at first use (api.hip)
 
 inline int check_launch() {
@@ -479,6 +481,38 @@ struct ReduceBatch {
   void params(const float* partials, int n_partials, float* grad_axes, float* grad_biases, float scale);
   int launch(hipStream_t stream);
 };
+
+// The dense products of a backward call on an under-filled level in ONE launch (gemm_bf16.hip, bwd_dense_shared_kernel):
+// grad_T = g W^T, dX = U W' and the weight gradient's TN product are independent of each other once U is written, and none
+// of them fills the chip there.  A launcher that is handed a DenseShare decides its form as always and, instead of launching,
+// adds a role: the body its kernel would run, its grid as a virtual grid, its arguments.  launch() starts every role's
+// workgroups as one grid; a workgroup finds its role by its index and runs that role's body on the role's virtual index, so
+// every role computes, bit for bit, what its own launch computes.  Nothing passes between workgroups.
+struct DenseRole {
+  int kind;                     // the body (family, output mode, width: gemm_bf16.hip)
+  unsigned begin, gx, gy, gz;   // first workgroup of the role in the shared grid; its virtual grid
+  const void *a, *b0, *b1;      // strip, NN: A rows and the weight planes hi / lo.  TN: A rows, B rows, -
+  void* c;                      // the output (NN split over k, TN: the partials)
+  int64_t m, chunk;             // rows; TN: rows per range
+  int n, k, kp, per;            // columns, k (TN: ka); NN: padded k and k tiles (super tiles) per split
+  const float* alpha_num;
+  float alpha_scale;
+};
+struct DenseRoles {
+  int count;
+  DenseRole role[3];
+};
+struct DenseShare {
+  DenseRoles roles{};
+  int order[3] = {0, 0, 0}, next_order = 0;  // roles are laid out in the grid by ascending order (the longest k loops first)
+  int lds_bytes = 0;
+  // the reduction of a k-split product whose result a later stage of the call reads (grad_T): launched right behind
+  struct { const float* partials; void* out; int64_t count; int splits; const float* alpha_num; float alpha_scale; bool packed, set; } after{};
+  int add(const DenseRole& r, dim3 grid, int lds);
+  int launch(hipStream_t stream);
+};
+bool gemm_nn_bf16_sharable(int64_t m, int n, int k, bool out_packed, int afmt);
+bool gemm_tn_bf16_sharable(int64_t m, int ka, int n, int splits, int afmt);
 
 // split-bf16 path (edge_bf16.hip, gemm_bf16.hip)
 int launch_split_pack(const float* src, uint32_t* dst, int64_t n, hipStream_t stream);
@@ -598,15 +632,18 @@ struct PrepBatch {
 
 int launch_pack_geometry(const float* pts, const float* frames, int64_t n, int f, float* records, hipStream_t stream);
 bool gemm_strip_bf16_applicable(int64_t m, int n, int k);
+// (share, all three launchers: the product becomes a role of the caller's shared launch instead of a launch of its own)
 int launch_gemm_strip_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, uint32_t* c,
-                           int64_t m, int n, int k, hipStream_t stream);
+                           int64_t m, int n, int k, hipStream_t stream, DenseShare* share = nullptr);
 int launch_gemm_nn_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, void* c,
                         bool out_packed, int64_t m, int n, int k, float* split_ws, const float* alpha_num,
-                        float alpha_scale, hipStream_t stream, int afmt = 0, ReduceBatch* defer = nullptr);  // afmt: A rows 0 packed, 1 3-byte, 2 T16
+                        float alpha_scale, hipStream_t stream, int afmt = 0, ReduceBatch* defer = nullptr,  // afmt: A rows 0 packed, 1 3-byte, 2 T16
+                        DenseShare* share = nullptr);
 size_t gemm_nn_bf16_split_bytes(int64_t m, int n, int k);
 int launch_gemm_tn_bf16(const char* tag, const uint32_t* a, const uint32_t* b, float* c, float* partials, int splits,
                         int64_t m, int ka, int n, const float* alpha_num, float alpha_scale, hipStream_t stream, int afmt = 0,
                         ReduceBatch* defer = nullptr,  // defer (both GEMMs): the reduction joins the caller's ReduceBatch
-                        bool out_ikn = false);  // out_ikn (needs defer): ka = (o, k), n = i -> c is dW[i, k, o] (the weight gradient from U)
+                        bool out_ikn = false,  // out_ikn (needs defer): ka = (o, k), n = i -> c is dW[i, k, o] (the weight gradient from U)
+                        DenseShare* share = nullptr);
 
 }  // namespace se3

@@ -27,6 +27,8 @@
 
 #include "common.h"
 
+#define SE3_GRID_BLOCK blockIdx  // the stand-alone kernels: see gemm_nn_bf16_body.h
+
 namespace se3 {
 
 namespace {
@@ -51,6 +53,24 @@ __device__ __forceinline__ u32x4 ld4_words(const uint32_t* p, int64_t avail, boo
                  w = avail > 3 ? p[3] : 0u;
   return u32x4{x, y, z, w};
 }
+
+// Where a workgroup stands in its grid: HwGrid is the launch's own grid (a stand-alone kernel), VirtGrid a role's virtual
+// grid inside the shared launch of backward's dense products (bwd_dense_shared_kernel).  The strip GEMM's body is a function
+// over one of these (it compiles to the same device code as the kernel it was); the bodies with LDS tiles are included
+// texts (gemm_nn_bf16_body.h) that read SE3_GRID_BLOCK.
+struct HwGrid {
+  __device__ __forceinline__ unsigned bx() const { return blockIdx.x; }
+  __device__ __forceinline__ unsigned by() const { return blockIdx.y; }
+  __device__ __forceinline__ unsigned bz() const { return blockIdx.z; }
+  __device__ __forceinline__ unsigned gdy() const { return gridDim.y; }
+};
+struct VirtGrid {
+  unsigned x, y, z, ny;
+  __device__ __forceinline__ unsigned bx() const { return x; }
+  __device__ __forceinline__ unsigned by() const { return y; }
+  __device__ __forceinline__ unsigned bz() const { return z; }
+  __device__ __forceinline__ unsigned gdy() const { return ny; }
+};
 
 // ---- Pieces the NN kernels share (who takes which: the table in the header comment) -------------------------------------
 
@@ -91,10 +111,10 @@ __device__ __forceinline__ void nn_mfma_tiles(u32x4 a_hi, u32x4 a_lo, const LDS&
 }
 
 // The accumulators of a wavefront (rows m0 + 32 wave .., columns n0 ..) -> C.
-// OUT_MODE 0: fp32 C * alpha, 1: packed words of C * alpha, 2: raw fp32 partial of split blockIdx.z (no alpha).
+// OUT_MODE 0: fp32 C * alpha, 1: packed words of C * alpha, 2: raw fp32 partial of split bz (the workgroup's z index; no alpha).
 template <int OUT_MODE, int NB>
 __device__ __forceinline__ void nn_store_acc(const f32x16 (&acc)[2 * NB], void* c, int64_t m, int n, int64_t m0, int n0,
-                                             int wave, int rl, int h, const float* alpha_num, float alpha_scale) {
+                                             int wave, int rl, int h, const float* alpha_num, float alpha_scale, unsigned bz) {
   const float alpha = OUT_MODE == 2 ? 1.0f : (alpha_num ? *alpha_num : 1.0f) * alpha_scale;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -107,7 +127,7 @@ __device__ __forceinline__ void nn_store_acc(const f32x16 (&acc)[2 * NB], void* 
         if constexpr (OUT_MODE == 1) {
           static_cast<uint32_t*>(c)[gr * n + gc] = split_pack(alpha * acc[ct][r]);
         } else {
-          float* out = static_cast<float*>(c) + (OUT_MODE == 2 ? (int64_t)blockIdx.z * m * n : 0);
+          float* out = static_cast<float*>(c) + (OUT_MODE == 2 ? (int64_t)bz * m * n : 0);
           out[gr * n + gc] = alpha * acc[ct][r];
         }
       }
@@ -133,130 +153,7 @@ __global__ __launch_bounds__(256) void gemm_nn_bf16_kernel(const uint32_t* __res
   constexpr int BNW = BN * NB;  // columns per workgroup
   __shared__ __attribute__((aligned(16))) uint16_t bsh[2][BNW][B_LD];
   __shared__ __attribute__((aligned(16))) uint16_t bsl[2][BNW][B_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rl = lane & 31, h = lane >> 5;
-  // (row blocks last-to-first -- A was written front-to-back just before, its tail is still in the memory-side cache --
-  // was measured: no difference, 0.245 ms either way)
-  const int64_t m0 = (int64_t)blockIdx.x * BM;
-  const int n0 = blockIdx.y * BNW;
-  const bool a_vec = (k % 4) == 0;
-  const int kt_begin = blockIdx.z * kt_per_split;
-  const int nk = min(kp / BK - kt_begin, kt_per_split);  // k-tiles of this block (> 0 by construction)
-
-  struct Tile { u32x4 a0, a1, a2, a3, bh[NB], bl[NB]; };
-  const u32x4 zero4 = {0u, 0u, 0u, 0u};
-  const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint32_t*>(a), (short)0, FAST ? (int)(uint32_t)(m * k * 4) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t bh_rs = weight_plane_rsrc(bt_hi, n, kp, FAST), bl_rs = weight_plane_rsrc(bt_lo, n, kp, FAST);
-  // Every block walks its k-tiles from a different starting phase (the sum is order-independent up to
-  // rounding): with a common phase all resident blocks read the same 128-byte column strip of their
-  // 8 KB rows at the same time, which concentrates the traffic on a few HBM channels.
-  const int phase = FAST ? (int)((blockIdx.x * 5u) % (unsigned)nk) : 0;
-  auto load_tile = [&](Tile& t, int kt_seq) {
-    int kt = kt_seq + phase;
-    if (kt >= nk) kt -= nk;
-    const int k0 = (kt_begin + kt) * BK;
-    const int row = tid >> 3, kq = (tid & 7) * 4;
-    if constexpr (FAST) {
-      const uint32_t aoff = (uint32_t)(((m0 + row) * k + k0 + kq) * 4);  // rows >= m fall outside the buffer -> 0
-      const uint32_t rstep = (uint32_t)k * 32u * 4u;
-      t.a0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, aoff, 0, 0));
-      t.a1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, aoff + rstep, 0, 0));
-      t.a2 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, aoff + 2 * rstep, 0, 0));
-      t.a3 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, aoff + 3 * rstep, 0, 0));
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        const uint32_t boff = (uint32_t)((((int64_t)(n0 + 64 * nb + (tid >> 2))) * kp + k0 + (tid & 3) * 8) * 2);
-        t.bh[nb] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(bh_rs, boff, 0, 0));
-        t.bl[nb] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(bl_rs, boff, 0, 0));
-      }
-      return;
-    }
-    const uint32_t* ap = a + (m0 + row) * k + k0 + kq;
-    const int64_t avail = k - (k0 + kq);
-    t.a0 = ld4_words(ap, m0 + row < m ? avail : 0, a_vec);
-    t.a1 = ld4_words(ap + (int64_t)32 * k, m0 + row + 32 < m ? avail : 0, a_vec);
-    t.a2 = ld4_words(ap + (int64_t)64 * k, m0 + row + 64 < m ? avail : 0, a_vec);
-    t.a3 = ld4_words(ap + (int64_t)96 * k, m0 + row + 96 < m ? avail : 0, a_vec);
-    const int kq8 = (tid & 3) * 8;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      const int nl = 64 * nb + (tid >> 2);
-      const bool ok = n0 + nl < n;
-      const int64_t boff = (int64_t)(ok ? n0 + nl : 0) * kp + k0 + kq8;
-      const u32x4 vh = *reinterpret_cast<const u32x4*>(bt_hi + boff), vl = *reinterpret_cast<const u32x4*>(bt_lo + boff);
-      t.bh[nb] = ok ? vh : zero4;
-      t.bl[nb] = ok ? vl : zero4;
-    }
-  };
-  f32x16 acc[2 * NB];
-#pragma unroll
-  for (int c = 0; c < 2 * NB; ++c) acc[c] = zero16();
-  auto store_tile = [&](const Tile& t, int buf) {
-    const int row = tid >> 3, kq = (tid & 7) * 4;
-    *reinterpret_cast<u32x4*>(&as[buf][row][kq]) = t.a0;
-    *reinterpret_cast<u32x4*>(&as[buf][row + 32][kq]) = t.a1;
-    *reinterpret_cast<u32x4*>(&as[buf][row + 64][kq]) = t.a2;
-    *reinterpret_cast<u32x4*>(&as[buf][row + 96][kq]) = t.a3;
-    const int kq8 = (tid & 3) * 8;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      *reinterpret_cast<u32x4*>(&bsh[buf][64 * nb + (tid >> 2)][kq8]) = t.bh[nb];
-      *reinterpret_cast<u32x4*>(&bsl[buf][64 * nb + (tid >> 2)][kq8]) = t.bl[nb];
-    }
-  };
-
-  auto compute = [&](int buf) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int kk = 16 * s + 8 * h;
-      const u32x4 w0 = *reinterpret_cast<const u32x4*>(&as[buf][wave * 32 + rl][kk]);
-      const u32x4 w1 = *reinterpret_cast<const u32x4*>(&as[buf][wave * 32 + rl][kk + 4]);
-      const u32x4 a_hi = {pair_hi(w0[0], w0[1]), pair_hi(w0[2], w0[3]), pair_hi(w1[0], w1[1]), pair_hi(w1[2], w1[3])};
-      const u32x4 a_lo = {pair_lo(w0[0], w0[1]), pair_lo(w0[2], w0[3]), pair_lo(w1[0], w1[1]), pair_lo(w1[2], w1[3])};
-      nn_mfma_tiles<NB>(a_hi, a_lo, bsh, bsl, buf, kk, rl, acc);
-    }
-  };
-  // k-tile kt lives in register set (kt mod DEPTH) until it is written to LDS buffer (kt & 1).  The kernel's
-  // occupancy is set by its LDS tiles (2 blocks per CU), which leaves 256 VGPRs per wavefront: they hold DEPTH
-  // tiles in flight.  Measured on MI355X: 3, 4, 6 and 8 tiles give the same time, and so does the kernel with
-  // everything but the A loads removed (a diagnostic build of round 1): 0.245 ms for 1.07 GB = 4.4 TB/s, while the same walk
-  // over a buffer that was not just written by the previous kernel reads at 5.8-6.3 TB/s (tools/probes/): the
-  // producer's dirty lines are still draining from L2 / the memory-side cache into HBM while this kernel reads.
-  constexpr int DEPTH = kGemmDepth;
-  static_assert(DEPTH % 2 == 0, "the LDS buffer parity of a step must be a compile-time constant");
-  Tile t[DEPTH];
-#pragma unroll
-  for (int u = 0; u < DEPTH; ++u)
-    if (u < nk) load_tile(t[u], u);
-  store_tile(t[0], 0);
-  __syncthreads();
-  // steady state without any condition around the loads (conditional loads make the compiler drain
-  // vmcnt(0) every step), then a checked tail
-  int kt0 = 0;
-  for (; kt0 + 2 * DEPTH <= nk; kt0 += DEPTH) {
-#pragma unroll
-    for (int u = 0; u < DEPTH; ++u) {
-      load_tile(t[u], kt0 + u + DEPTH);
-      compute(u & 1);
-      store_tile(t[(u + 1) % DEPTH], (u & 1) ^ 1);
-      __syncthreads();
-    }
-  }
-  for (; kt0 < nk; kt0 += DEPTH) {
-#pragma unroll
-    for (int u = 0; u < DEPTH; ++u) {
-      const int kt = kt0 + u;
-      if (kt < nk) {
-        if (kt + DEPTH < nk) load_tile(t[u], kt + DEPTH);
-        compute(u & 1);
-        if (kt + 1 < nk) store_tile(t[(u + 1) % DEPTH], (u & 1) ^ 1);
-        __syncthreads();
-      }
-    }
-  }
-
-  nn_store_acc<OUT_MODE, NB>(acc, c, m, n, m0, n0, wave, rl, h, alpha_num, alpha_scale);
+#include "gemm_nn_bf16_body.h"
 }
 
 // NN GEMM over A rows in the 3-byte format (common.h, T24; k a multiple of 64).  What bounds the A stream of these
@@ -277,125 +174,11 @@ __global__ __launch_bounds__(256) void gemm_nn_t24_kernel(const uint8_t* __restr
                                                           const uint16_t* __restrict__ bt_lo, void* __restrict__ c,
                                                           int64_t m, int n, int k, int st_per_split,
                                                           const float* __restrict__ alpha_num, float alpha_scale) {
-  constexpr int BNW = BN * NB;
-  constexpr int RB = BM;           // rows per workgroup
-  constexpr int RP = 32;           // rows one load pass of the hi plane covers (8 threads per row): 4 passes = RB rows
-  constexpr int RPL = 64;          // rows one load pass of the lo plane covers (4 threads per row): 2 passes = RB rows
-  constexpr int CP = kWeightPassCols, NBP = 2 * NB;
-  // one block of LDS, carved into the four tile images
-  constexpr int kAsh = 2 * RB * (BK + 8) * 2, kAsl = 2 * RB * (BK + 16), kBs = 2 * BNW * B_LD * 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // gemm_nn_t24_lds_bytes: 52 / 72 KB
-  auto ash = reinterpret_cast<uint16_t(*)[RB][BK + 8]>(smem);                    // [2][RB][BK + 8], 80-byte pitch
-  auto asl = reinterpret_cast<uint8_t(*)[RB][BK + 16]>(smem + kAsh);             // [2][RB][BK + 16], 48-byte pitch
-  auto bsh = reinterpret_cast<uint16_t(*)[BNW][B_LD]>(smem + kAsh + kAsl);       // [2][BNW][B_LD]
-  auto bsl = reinterpret_cast<uint16_t(*)[BNW][B_LD]>(smem + kAsh + kAsl + kBs);
-  // (`& 255` changes no value at 256 threads, but without it the compiler allocates registers differently: kept, so that
-  // the kernel stays the code that was measured)
-  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-  const int rl = lane & 31, h = lane >> 5;
-  const int64_t m0 = (int64_t)blockIdx.x * RB;
-  const int n0 = blockIdx.y * BNW;
-  const int ns = min(k / 64 - (int)blockIdx.z * st_per_split, st_per_split);  // super tiles of this workgroup (> 0 by construction)
-  const int st_begin = blockIdx.z * st_per_split;
-
-  struct Super { u32x4 ah[4], al[2], bh[NBP], bl[NBP]; };
-  const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(a), (short)0, (int)(uint32_t)(m * k * 3), 0x00020000);
-  const __amdgpu_buffer_rsrc_t bh_rs = weight_plane_rsrc(bt_hi, n, k), bl_rs = weight_plane_rsrc(bt_lo, n, k);
-  const int phase = (int)((blockIdx.x * 5u) % (unsigned)ns);  // see gemm_nn_bf16_kernel
-  const uint32_t rb = (uint32_t)k * 3u;
-  const int hsel = (tid >> 2) & 1, lsel = (tid >> 1) & 1;
-  auto load_super = [&](Super& t, int seq) {
-    int st = seq + phase;
-    if (st >= ns) st -= ns;
-    const uint32_t k0 = (uint32_t)(st_begin + st) * 64u;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const uint32_t off = (uint32_t)(m0 + p * RP + (tid >> 3)) * rb + k0 * 2u + (uint32_t)((tid & 7) ^ ((p & 1) << 2)) * 16u;
-      t.ah[p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, off, 0, 0));
-    }
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const uint32_t off = (uint32_t)(m0 + p * RPL + (tid >> 2)) * rb + (uint32_t)k * 2u + k0 + (uint32_t)((tid & 3) ^ (p << 1)) * 16u;
-      t.al[p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, off, 0, 0));
-    }
-    // (the weight loads stay written out here and in gemm_nn_t16_kernel: as a shared function the offset is associated
-    // otherwise -- k0 joins the thread's piece, not the row -- and waits move inside the k loop, profiles/gemm_nn_pieces.txt)
-#pragma unroll
-    for (int j = 0; j < NBP; ++j) {  // pass j: columns CP * j + (tid >> 3); passes alternate which 32-k half a thread holds
-      const uint32_t off = ((uint32_t)(n0 + CP * j + (tid >> 3)) * (uint32_t)k + k0 + (uint32_t)((tid & 7) ^ ((j & 1) << 2)) * 8u) * 2u;
-      t.bh[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(bh_rs, off, 0, 0));
-      t.bl[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(bl_rs, off, 0, 0));
-    }
-  };
-  // the 32-k half `hf` of a super tile -> LDS buffer `buf`: pieces whose column bit 2 (hi, B) / bit 1 (lo) equals hf
-  auto store_half = [&](const Super& t, int hf, int buf) {
-    const bool q = (hf ^ hsel) != 0, ql = (hf ^ lsel) != 0;
-    const int r8 = tid >> 3, c4 = (tid & 3) * 8;
-    *reinterpret_cast<u32x4*>(&ash[buf][(q ? RP : 0) + r8][c4]) = q ? t.ah[1] : t.ah[0];
-    *reinterpret_cast<u32x4*>(&ash[buf][(q ? 3 * RP : 2 * RP) + r8][c4]) = q ? t.ah[3] : t.ah[2];
-    *reinterpret_cast<u32x4*>(&asl[buf][(ql ? RPL : 0) + (tid >> 2)][(tid & 1) * 16]) = ql ? t.al[1] : t.al[0];
-    nn_store_weights_half<NB>(t.bh, t.bl, bsh, bsl, buf, q, r8, c4);
-  };
-  f32x16 acc[2 * NB];
-#pragma unroll
-  for (int ct = 0; ct < 2 * NB; ++ct) acc[ct] = zero16();
-  auto compute = [&](int buf) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int kk = 16 * s + 8 * h;
-      // the hi fragment is one 16-byte read; the lo fragment is rebuilt from the 8 lo bytes (7 VALU per pair)
-      const u32x4 a_hi = *reinterpret_cast<const u32x4*>(&ash[buf][wave * 32 + rl][kk]);
-      const uint32_t* lp = reinterpret_cast<const uint32_t*>(&asl[buf][wave * 32 + rl][kk]);
-      const uint32_t l0 = lp[0], l1 = lp[1];
-      const u32x4 a_lo = {t24_lo_word<0>(a_hi[0], l0), t24_lo_word<2>(a_hi[1], l0), t24_lo_word<0>(a_hi[2], l1),
-                          t24_lo_word<2>(a_hi[3], l1)};
-      nn_mfma_tiles<NB>(a_hi, a_lo, bsh, bsl, buf, kk, rl, acc);
-    }
-  };
-  // Two super tiles in registers (= the 4 k-tiles in flight of the kernel above).  Step A computes the first half
-  // while the second goes to LDS buffer 1; step B computes the second half, stores the next super tile's first half
-  // to buffer 0 and refills the register set that just emptied.
-  Super t0, t1;
-  load_super(t0, 0);
-  if (ns > 1) load_super(t1, 1);
-  store_half(t0, 0, 0);
-  __syncthreads();
-#define SE3_T24_STEP(CUR, NEXT, ST)                       \
-  compute(0);                                             \
-  store_half(CUR, 1, 1);                                  \
-  __syncthreads();                                        \
-  if ((ST) + 2 < ns) load_super(CUR, (ST) + 2);           \
-  compute(1);                                             \
-  if ((ST) + 1 < ns) store_half(NEXT, 0, 0);              \
-  __syncthreads();
-#define SE3_T24_STEP_FULL(CUR, NEXT, ST) \
-  compute(0);                            \
-  store_half(CUR, 1, 1);                 \
-  __syncthreads();                       \
-  load_super(CUR, (ST) + 2);             \
-  compute(1);                            \
-  store_half(NEXT, 0, 0);                \
-  __syncthreads();
-  int st = 0;
-  const int prio_slot = wave_slot_id();
-  for (; st + 4 <= ns; st += 2) {  // no conditions around the loads (see gemm_nn_bf16_kernel)
-    rotate_priority(prio_slot + (st >> 1));
-    SE3_T24_STEP_FULL(t0, t1, st)
-    SE3_T24_STEP_FULL(t1, t0, st + 1)
-  }
-  for (; st < ns; st += 2) {
-    SE3_T24_STEP(t0, t1, st)
-    if (st + 1 < ns) {
-      SE3_T24_STEP(t1, t0, st + 1)
-    }
-  }
-#undef SE3_T24_STEP
-#undef SE3_T24_STEP_FULL
-
-  nn_store_acc<OUT_MODE, NB>(acc, c, m, n, m0, n0, wave, rl, h, alpha_num, alpha_scale);
+#include "gemm_nn_t24_body.h"
 }
 
+// LDS of gemm_nn_bf16_kernel: the A image, then the two weight images of nb 64-column blocks (nb = 0: the A image alone)
+constexpr int gemm_nn_bf16_lds_bytes(int nb) { return 2 * BM * A_LD * 4 + 2 * (2 * BN * nb * B_LD * 2); }
 constexpr int gemm_nn_t24_lds_bytes(int nb) {
   return 2 * BM * (BK + 8) * 2 + 2 * BM * (BK + 16) + 2 * (2 * BN * nb * B_LD * 2);
 }
@@ -541,7 +324,7 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
     __syncthreads();
   }
 
-  nn_store_acc<OUT_MODE, NB>(acc, c, m, n, m0, n0, wave, rl, h, alpha_num, alpha_scale);
+  nn_store_acc<OUT_MODE, NB>(acc, c, m, n, m0, n0, wave, rl, h, alpha_num, alpha_scale, blockIdx.z);
 }
 
 // Row-strip GEMM for the wide, write-dominated products with a short k (grad_T = g W^T, H = f W''):
@@ -553,16 +336,16 @@ __global__ __launch_bounds__(256) void gemm_nn_t16_kernel(const uint8_t* __restr
 // SIMD and the 4096 strips of the headline shape are resident at once (the previous 64-column version needed
 // ~150 VGPRs: 3 per SIMD, i.e. a second, mostly empty round).  alpha is folded into the prepared weights.
 constexpr int kStripRot = 17;  // column tiles a strip's walk starts further on than its predecessor's ("Column order rotated" below)
-template <int KS>  // kp / 16: 2, 4 (k <= 64, 120 VGPRs) or 8 (k <= 128: twice the fragments, 3 waves per SIMD)
-__global__ __launch_bounds__(256, KS <= 4 ? 4 : 2) void gemm_strip_bf16_kernel(const uint32_t* __restrict__ a,
-                                                                 const uint16_t* __restrict__ bt_hi,
-                                                                 const uint16_t* __restrict__ bt_lo,
-                                                                 uint32_t* __restrict__ c, int64_t m, int n, int k) {
+// (body and stand-alone kernel: see HwGrid)
+template <int KS, class G>  // kp / 16: 2, 4 (k <= 64, 120 VGPRs) or 8 (k <= 128: twice the fragments, 3 waves per SIMD)
+__device__ __forceinline__ void gemm_strip_bf16_body(const G g, const uint32_t* a,
+                                                     const uint16_t* bt_hi, const uint16_t* bt_lo,
+                                                     uint32_t* c, int64_t m, int n, int k) {
   constexpr int KP = KS * 16;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: feeds a buffer descriptor
   const int rl = lane & 31, h = lane >> 5;
-  const int64_t row0 = (int64_t)blockIdx.x * 128 + wave * 32;
+  const int64_t row0 = (int64_t)g.bx() * 128 + wave * 32;
   if (row0 >= m) return;
   const __amdgpu_buffer_rsrc_t a_rs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a), (short)0, (int)(uint32_t)(m * k * 4), 0x00020000);
@@ -641,14 +424,14 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : 2) void gemm_strip_bf16_kernel(c
   // Column order rotated per strip: with a power-of-two row pitch (n * 4 = 8 KB) every wavefront of the chip would
   // otherwise write the same 128-byte column window of its rows at the same time, i.e. all traffic of a moment
   // lands on a handful of L2 / HBM channels.
-  // blockIdx.y selects a contiguous range of column tiles (small M: the row strips alone cannot fill the chip)
+  // the block's y index selects a contiguous range of column tiles (small M: the row strips alone cannot fill the chip)
   const int n_tiles_all = (n + 31) / 32;
-  const int per = (n_tiles_all + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int tile_lo = (int)blockIdx.y * per;
+  const int per = (n_tiles_all + (int)g.gdy() - 1) / (int)g.gdy();
+  const int tile_lo = (int)g.by() * per;
   const int n_tiles = min(per, n_tiles_all - tile_lo);
   if (n_tiles <= 0) return;
   const int n_lo = tile_lo * 32, n_hi = min(n, (tile_lo + n_tiles) * 32);
-  int n0 = n_lo + (int)(((blockIdx.x * 4 + wave) * (unsigned)kStripRot) % (unsigned)n_tiles) * 32;
+  int n0 = n_lo + (int)(((g.bx() * 4 + wave) * (unsigned)kStripRot) % (unsigned)n_tiles) * 32;
   load_b(n0);
   SE3_WAIT_B(0);
   // (rotating wave priority, common.h rotate_priority, was measured here too -- every strip is resident for the whole
@@ -673,6 +456,14 @@ __global__ __launch_bounds__(256, KS <= 4 ? 4 : 2) void gemm_strip_bf16_kernel(c
 #undef SE3_WAIT_B
 }
 
+template <int KS>
+__global__ __launch_bounds__(256, KS <= 4 ? 4 : 2) void gemm_strip_bf16_kernel(const uint32_t* __restrict__ a,
+                                                                 const uint16_t* __restrict__ bt_hi,
+                                                                 const uint16_t* __restrict__ bt_lo,
+                                                                 uint32_t* __restrict__ c, int64_t m, int n, int k) {
+  gemm_strip_bf16_body<KS>(HwGrid{}, a, bt_hi, bt_lo, c, m, n, k);
+}
+
 // out = alpha * sum_z partials[z]  (fp32 or packed words)
 template <bool OUT_PACKED>
 __global__ void reduce_splits_kernel(const float* __restrict__ partials, void* __restrict__ out, int64_t count,
@@ -694,6 +485,13 @@ __global__ void reduce_splits_kernel(const float* __restrict__ partials, void* _
 // AFMT 2: A rows in the 2.25-byte block format (T16; ka a multiple of 128): a stage reads 256 B of mantissas per row
 // and the two exponent bytes of every thread's piece, decodes to the same hi / lo 16-bit images (the lo plane is then
 // the bf16 lo operand itself: no rebuild in the MFMA stage); partial rows at t16_k_of().
+// The six LDS images of gemm_tn_bf16_kernel<., AFMT> as one buffer (the shared launch carves them from its dynamic LDS)
+template <int AFMT>
+struct TnLds {
+  static constexpr int kARows = AFMT != 0 ? 1 : BK, kPRows = AFMT != 0 ? BK : 1, kAPitch = 128 + 32, kBPitch = BN + 32;
+  static constexpr int o_ath = 2 * kARows * 128 * 4, o_atl = o_ath + 2 * kPRows * kAPitch * 2, o_bt = o_atl + 2 * kPRows * kAPitch * 2,
+                       o_bth = o_bt + 2 * kARows * BN * 4, o_btl = o_bth + 2 * kPRows * kBPitch * 2, bytes = o_btl + 2 * kPRows * kBPitch * 2;
+};
 template <bool FAST, int AFMT>
 __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const uint32_t* __restrict__ a,
                                                            const uint32_t* __restrict__ b,
@@ -713,211 +511,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const uint32_t* __res
   __shared__ __attribute__((aligned(16))) uint32_t bt[2][A24 ? 1 : BK][BN];
   __shared__ __attribute__((aligned(16))) uint16_t bth[2][A24 ? BK : 1][BPITCH];
   __shared__ __attribute__((aligned(16))) uint16_t btl[2][A24 ? BK : 1][BPITCH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rl = lane & 31, h = lane >> 5;
-  const int ka0 = blockIdx.x * 128;
-  const int n0 = blockIdx.y * BN;
-  const int64_t mb = (int64_t)blockIdx.z * chunk;
-  const int64_t me = min(m, mb + chunk);
-  const bool b_vec = (n % 4) == 0;
-  const int64_t nst = me > mb ? (me - mb + BK - 1) / BK : 0;
-
-  struct Stage { u32x4 a0, a1, a2, a3, b0, b1; };
-  const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint32_t*>(a), (short)0, FAST ? (int)(uint32_t)(me * gemm_a_row_bytes(AFMT, ka)) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t b_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint32_t*>(b), (short)0, FAST ? (int)(uint32_t)(me * n * 4) : 0, 0x00020000);
-  const int arow = tid >> 5, acq = (tid & 31) * 4, brow = tid >> 4, bcq = (tid & 15) * 4;
-  const bool a_ok = ka0 + acq < ka, b_ok = n0 + bcq < n;
-  auto load_stage = [&](Stage& t, int64_t st) {
-    const int64_t mm = mb + st * BK;
-    if constexpr (A16) {
-      const uint32_t oob = 0xfffffff0u;
-      const uint32_t rb = (uint32_t)gemm_a_row_bytes(AFMT, ka);
-      constexpr int kNtLoad = 2;
-      // mantissas: 32 rows x 256 B = 2 pieces of 16 B per thread (rows tid >> 4 and + 16, piece tid & 15 = 8 mantissas =
-      // blocks 2 pc, 2 pc + 1 of the 128 columns); their exponent bytes are adjacent in the plane (t16_exp_pos: bit 0)
-      const bool h_ok = ka0 + (tid & 15) * 8 < ka;
-      const uint32_t ho = (uint32_t)(mm + (tid >> 4)) * rb + (uint32_t)(ka0 + (tid & 15) * 8) * 2u;
-      const uint32_t eo = (uint32_t)(mm + (tid >> 4)) * rb + (uint32_t)ka * 2u + (uint32_t)t16_exp_pos((ka0 + (tid & 15) * 8) >> 2);
-      const uint32_t bo = b_ok ? (uint32_t)(((mm + brow) * n + n0 + bcq) * 4) : oob;
-      const uint32_t bs16 = (uint32_t)n * 64u;
-      t.a0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, h_ok ? ho : oob, 0, kNtLoad));
-      t.a1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, h_ok ? ho + 16u * rb : oob, 0, kNtLoad));
-      t.a2[0] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(a_rs, h_ok ? eo : oob, 0, kNtLoad);
-      t.a2[1] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(a_rs, h_ok ? eo + 16u * rb : oob, 0, kNtLoad);
-      t.b0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, bo, 0, 0));
-      t.b1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_ok ? bo + bs16 : oob, 0, 0));
-    } else if constexpr (A24) {
-      const uint32_t oob = 0xfffffff0u;
-      const uint32_t rb = (uint32_t)ka * 3u;
-      // hi: 32 rows x 256 B = 2 pieces of 16 B per thread; lo: 32 rows x 128 B = 1 piece per thread.  The rows are
-      // read once: non-temporal loads keep them from displacing the g tiles the 16 column blocks share in L2
-      // (0.178 -> 0.170 ms; the same hint on the NN GEMM's A stream costs it 0.01 ms)
-      constexpr int kNtLoad = 2;
-      const bool h_ok = ka0 + (tid & 15) * 8 < ka, l_ok = ka0 + (tid & 7) * 16 < ka;
-      const uint32_t ho = (uint32_t)(mm + (tid >> 4)) * rb + (uint32_t)(ka0 + (tid & 15) * 8) * 2u;
-      const uint32_t lo = (uint32_t)(mm + (tid >> 3)) * rb + (uint32_t)ka * 2u + (uint32_t)(ka0 + (tid & 7) * 16);
-      const uint32_t bo = b_ok ? (uint32_t)(((mm + brow) * n + n0 + bcq) * 4) : oob;
-      const uint32_t bs16 = (uint32_t)n * 64u;
-      t.a0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, h_ok ? ho : oob, 0, kNtLoad));
-      t.a1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, h_ok ? ho + 16u * rb : oob, 0, kNtLoad));
-      t.a2 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, l_ok ? lo : oob, 0, kNtLoad));
-      t.b0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, bo, 0, 0));
-      t.b1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_ok ? bo + bs16 : oob, 0, 0));
-    } else if constexpr (FAST) {
-      const uint32_t oob = 0xfffffff0u;  // beyond num_records: the load returns 0
-      const uint32_t ao = a_ok ? (uint32_t)(((mm + arow) * ka + ka0 + acq) * 4) : oob;
-      const uint32_t bo = b_ok ? (uint32_t)(((mm + brow) * n + n0 + bcq) * 4) : oob;
-      const uint32_t as8 = (uint32_t)ka * 32u, bs16 = (uint32_t)n * 64u;
-      t.a0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, ao, 0, 0));
-      t.a1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, a_ok ? ao + as8 : oob, 0, 0));
-      t.a2 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, a_ok ? ao + 2 * as8 : oob, 0, 0));
-      t.a3 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, a_ok ? ao + 3 * as8 : oob, 0, 0));
-      t.b0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, bo, 0, 0));
-      t.b1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_ok ? bo + bs16 : oob, 0, 0));
-    } else {
-      u32x4* ta[4] = {&t.a0, &t.a1, &t.a2, &t.a3};
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int64_t gr = mm + p * 8 + arow;
-        *ta[p] = ld4_words(a + gr * ka + ka0 + acq, gr < me ? ka - (ka0 + acq) : 0, true);
-      }
-      u32x4* tb[2] = {&t.b0, &t.b1};
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const int64_t gr = mm + p * 16 + brow;
-        *tb[p] = ld4_words(b + gr * n + n0 + bcq, gr < me ? n - (n0 + bcq) : 0, b_vec);
-      }
-    }
-  };
-  // the hi / lo halves of a stage's B words (rows brow and brow + 16) into the 16-bit images of the row-plane forms (A16, A24)
-  auto store_b_planes = [&](const Stage& t, int buf) {
-    *reinterpret_cast<u32x2*>(&bth[buf][brow][bcq]) = u32x2{pair_hi(t.b0[0], t.b0[1]), pair_hi(t.b0[2], t.b0[3])};
-    *reinterpret_cast<u32x2*>(&btl[buf][brow][bcq]) = u32x2{pair_lo(t.b0[0], t.b0[1]), pair_lo(t.b0[2], t.b0[3])};
-    *reinterpret_cast<u32x2*>(&bth[buf][brow + 16][bcq]) = u32x2{pair_hi(t.b1[0], t.b1[1]), pair_hi(t.b1[2], t.b1[3])};
-    *reinterpret_cast<u32x2*>(&btl[buf][brow + 16][bcq]) = u32x2{pair_lo(t.b1[0], t.b1[1]), pair_lo(t.b1[2], t.b1[3])};
-  };
-  auto store_stage = [&](const Stage& t, int buf) {
-    if constexpr (A16) {
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const u32x4 mw = p ? t.a1 : t.a0;
-        const uint32_t e2 = t.a2[p];
-        u32x4 vh, vl;
-        t16_unpack8(mw, e2, vh, vl);
-        *reinterpret_cast<u32x4*>(&ath[buf][16 * p + (tid >> 4)][(tid & 15) * 8]) = vh;
-        *reinterpret_cast<u32x4*>(&atl[buf][16 * p + (tid >> 4)][(tid & 15) * 8]) = vl;
-      }
-      store_b_planes(t, buf);
-    } else if constexpr (A24) {
-      *reinterpret_cast<u32x4*>(&ath[buf][tid >> 4][(tid & 15) * 8]) = t.a0;
-      *reinterpret_cast<u32x4*>(&ath[buf][16 + (tid >> 4)][(tid & 15) * 8]) = t.a1;
-      u32x4 e0, e1;  // 16 lo bytes -> 16 half-words
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        e0[2 * i] = __builtin_amdgcn_perm(0u, t.a2[i], 0x0c010c00u), e0[2 * i + 1] = __builtin_amdgcn_perm(0u, t.a2[i], 0x0c030c02u);
-        e1[2 * i] = __builtin_amdgcn_perm(0u, t.a2[2 + i], 0x0c010c00u), e1[2 * i + 1] = __builtin_amdgcn_perm(0u, t.a2[2 + i], 0x0c030c02u);
-      }
-      *reinterpret_cast<u32x4*>(&atl[buf][tid >> 3][(tid & 7) * 16]) = e0;
-      *reinterpret_cast<u32x4*>(&atl[buf][tid >> 3][(tid & 7) * 16 + 8]) = e1;
-      store_b_planes(t, buf);
-    } else {
-      *reinterpret_cast<u32x4*>(&at[buf][arow][acq]) = t.a0;
-      *reinterpret_cast<u32x4*>(&at[buf][arow + 8][acq]) = t.a1;
-      *reinterpret_cast<u32x4*>(&at[buf][arow + 16][acq]) = t.a2;
-      *reinterpret_cast<u32x4*>(&at[buf][arow + 24][acq]) = t.a3;
-      *reinterpret_cast<u32x4*>(&bt[buf][brow][bcq]) = t.b0;
-      *reinterpret_cast<u32x4*>(&bt[buf][brow + 16][bcq]) = t.b1;
-    }
-  };
-
-  f32x16 acc0 = zero16(), acc1 = zero16();
-  auto compute = [&](int buf) {
-    if constexpr (A24) {
-      const int grp = lane >> 4, q = (lane >> 2) & 3, p4 = (lane & 3) * 4;
-      const int col = 16 * (grp & 1) + p4;  // this lane's address: row q of the block, 4 columns from here
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int r0 = 16 * s + 8 * (grp >> 1) + q;
-        const u32x4 a_hi = lds_frag_tr16(&ath[buf][r0][wave * 32 + col], &ath[buf][r0 + 4][wave * 32 + col]);
-        const u32x4 lw = lds_frag_tr16(&atl[buf][r0][wave * 32 + col], &atl[buf][r0 + 4][wave * 32 + col]);
-        u32x4 a_lo = lw;  // T16: the lo plane holds the bf16 lo operand itself
-        if constexpr (!A16)
-          a_lo = u32x4{t24_lo_word<0, 2>(a_hi[0], lw[0]), t24_lo_word<0, 2>(a_hi[1], lw[1]),
-                       t24_lo_word<0, 2>(a_hi[2], lw[2]), t24_lo_word<0, 2>(a_hi[3], lw[3])};
-        u32x4 b_hi = lds_frag_tr16(&bth[buf][r0][col], &bth[buf][r0 + 4][col]);
-        u32x4 b_lo = lds_frag_tr16(&btl[buf][r0][col], &btl[buf][r0 + 4][col]);
-        acc0 = mfma_bf16x3(a_hi, a_lo, b_hi, b_lo, acc0);
-        b_hi = lds_frag_tr16(&bth[buf][r0][32 + col], &bth[buf][r0 + 4][32 + col]);
-        b_lo = lds_frag_tr16(&btl[buf][r0][32 + col], &btl[buf][r0 + 4][32 + col]);
-        acc1 = mfma_bf16x3(a_hi, a_lo, b_hi, b_lo, acc1);
-      }
-      return;
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      uint32_t wa[8], wb0[8], wb1[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int row = 16 * s + 8 * h + j;
-        wa[j] = at[buf][row][wave * 32 + rl];
-        wb0[j] = bt[buf][row][rl];
-        wb1[j] = bt[buf][row][32 + rl];
-      }
-      u32x4 a_hi, a_lo, b_hi, b_lo;
-      frags_from_words(wa, a_hi, a_lo);
-      frags_from_words(wb0, b_hi, b_lo);
-      acc0 = mfma_bf16x3(a_hi, a_lo, b_hi, b_lo, acc0);
-      frags_from_words(wb1, b_hi, b_lo);
-      acc1 = mfma_bf16x3(a_hi, a_lo, b_hi, b_lo, acc1);
-    }
-  };
-  if (nst > 0) {
-    Stage t0, t1, t2;
-    load_stage(t0, 0);
-    if (1 < nst) load_stage(t1, 1);
-    if (2 < nst) load_stage(t2, 2);
-    store_stage(t0, 0);
-    __syncthreads();
-#define SE3_TN_STEP_FULL(ST, CUR, NEXT) \
-  load_stage(CUR, (ST) + 3);            \
-  compute((int)((ST) & 1));             \
-  store_stage(NEXT, (int)((ST) & 1) ^ 1); \
-  __syncthreads();
-#define SE3_TN_STEP(ST, CUR, NEXT)                                   \
-  if ((ST) < nst) {                                                  \
-    if ((ST) + 3 < nst) load_stage(CUR, (ST) + 3);                   \
-    compute((int)((ST) & 1));                                        \
-    if ((ST) + 1 < nst) store_stage(NEXT, (int)((ST) & 1) ^ 1);      \
-    __syncthreads();                                                 \
-  }
-    int64_t st = 0;
-    const int prio_slot = wave_slot_id();
-    for (; st + 6 <= nst; st += 3) {
-      rotate_priority(prio_slot + (int)(st / 3));  // every workgroup of this product is resident for the whole launch (common.h)
-      SE3_TN_STEP_FULL(st, t0, t1)
-      SE3_TN_STEP_FULL(st + 1, t1, t2)
-      SE3_TN_STEP_FULL(st + 2, t2, t0)
-    }
-    for (; st < nst; st += 3) {
-      SE3_TN_STEP(st, t0, t1)
-      SE3_TN_STEP(st + 1, t1, t2)
-      SE3_TN_STEP(st + 2, t2, t0)
-    }
-#undef SE3_TN_STEP
-#undef SE3_TN_STEP_FULL
-  }
-  float* out = partials + (int64_t)blockIdx.z * ka * n;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int kq = ka0 + wave * 32 + acc_row(r, h);
-    if (kq < ka) {
-      const int row = A16 ? t16_k_of(kq) : (A24 ? t24_k_of(kq) : kq);
-      if (n0 + rl < n) out[(int64_t)row * n + n0 + rl] = acc0[r];
-      if (n0 + 32 + rl < n) out[(int64_t)row * n + n0 + 32 + rl] = acc1[r];
-    }
-  }
+#include "gemm_tn_bf16_body.h"
 }
 
 // Bt[nn][kk] (two bf16 planes, pitch kp) from the layer weights W[C_in, K, C_out]:
@@ -948,6 +542,101 @@ __global__ void prep_weights_kernel(const float* __restrict__ w, int c_in, int k
                            : idx;
     bt_hi[o] = (uint16_t)(pk >> 16);
     bt_lo[o] = (uint16_t)(pk & 0xffffu);
+  }
+}
+
+
+// ---- Backward's dense products in one launch (common.h: DenseShare) --------------------------------------------------------
+// A role's kind: family | output mode << 4 | width (strip: k-steps; NN: 64-column blocks; TN: the format of the A rows).
+// Only the buffer-load forms with 64-column workgroups take part (gemm_*_sharable): the T16 rows and the guarded-load forms
+// keep their own launches, and so do the 128-column NN forms -- at 260-268 registers they would hold every role of the
+// launch to one workgroup per CU, where the forms below leave two (profiles/bwd_dense_shared.txt).
+constexpr int kRoleStrip = 1 << 8, kRoleNnWords = 2 << 8, kRoleNnT24 = 3 << 8, kRoleTn = 4 << 8;
+constexpr int dense_role_kind(int family, int mode, int width) { return family | mode << 4 | width; }
+
+// The bodies of the kernels above on a role's virtual index and on LDS images carved from the launch's dynamic LDS (every
+// role's images start at its first byte: a workgroup costs the largest role's LDS, not their sum).  The locals carry the names
+// of the kernels' parameters: the included texts read them.
+// the dynamic LDS of the launch (every declaration of an unsized shared array names its first byte)
+__device__ __forceinline__ char* dynamic_lds() {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  return smem;
+}
+#undef SE3_GRID_BLOCK
+#define SE3_GRID_BLOCK vblock
+template <int OUT_MODE, int NB>
+__device__ __forceinline__ void dense_role_nn_words(const VirtGrid vblock, const DenseRole& r) {
+  constexpr bool FAST = true;
+  constexpr int BNW = BN * NB;
+  char* const lds = dynamic_lds();
+  auto as = reinterpret_cast<uint32_t(*)[BM][A_LD]>(lds);
+  auto bsh = reinterpret_cast<uint16_t(*)[BNW][B_LD]>(lds + gemm_nn_bf16_lds_bytes(0));
+  auto bsl = reinterpret_cast<uint16_t(*)[BNW][B_LD]>(lds + gemm_nn_bf16_lds_bytes(0) + 2 * BNW * B_LD * 2);
+  const uint32_t* __restrict__ a = static_cast<const uint32_t*>(r.a);
+  const uint16_t* __restrict__ bt_hi = static_cast<const uint16_t*>(r.b0);
+  const uint16_t* __restrict__ bt_lo = static_cast<const uint16_t*>(r.b1);
+  void* __restrict__ c = r.c;
+  const int64_t m = r.m;
+  const int n = r.n, k = r.k, kp = r.kp, kt_per_split = r.per;
+  const float* __restrict__ alpha_num = r.alpha_num;
+  const float alpha_scale = r.alpha_scale;
+#include "gemm_nn_bf16_body.h"
+}
+template <int OUT_MODE, int NB>
+__device__ __forceinline__ void dense_role_nn_t24(const VirtGrid vblock, const DenseRole& r) {
+  const uint8_t* __restrict__ a = static_cast<const uint8_t*>(r.a);
+  const uint16_t* __restrict__ bt_hi = static_cast<const uint16_t*>(r.b0);
+  const uint16_t* __restrict__ bt_lo = static_cast<const uint16_t*>(r.b1);
+  void* __restrict__ c = r.c;
+  const int64_t m = r.m;
+  const int n = r.n, k = r.k, st_per_split = r.per;
+  const float* __restrict__ alpha_num = r.alpha_num;
+  const float alpha_scale = r.alpha_scale;
+#include "gemm_nn_t24_body.h"
+}
+template <int AFMT>
+__device__ __forceinline__ void dense_role_tn(const VirtGrid vblock, const DenseRole& r) {
+  constexpr bool FAST = true, A16 = AFMT == 2, A24 = AFMT != 0;
+  using L = TnLds<AFMT>;
+  char* const lds = dynamic_lds();
+  auto at = reinterpret_cast<uint32_t(*)[L::kARows][128]>(lds);
+  auto ath = reinterpret_cast<uint16_t(*)[L::kPRows][L::kAPitch]>(lds + L::o_ath);
+  auto atl = reinterpret_cast<uint16_t(*)[L::kPRows][L::kAPitch]>(lds + L::o_atl);
+  auto bt = reinterpret_cast<uint32_t(*)[L::kARows][BN]>(lds + L::o_bt);
+  auto bth = reinterpret_cast<uint16_t(*)[L::kPRows][L::kBPitch]>(lds + L::o_bth);
+  auto btl = reinterpret_cast<uint16_t(*)[L::kPRows][L::kBPitch]>(lds + L::o_btl);
+  const uint32_t* __restrict__ a = static_cast<const uint32_t*>(r.a);
+  const uint32_t* __restrict__ b = static_cast<const uint32_t*>(r.b0);
+  float* __restrict__ partials = static_cast<float*>(r.c);
+  const int64_t m = r.m, chunk = r.chunk;
+  const int ka = r.k, n = r.n;
+#include "gemm_tn_bf16_body.h"
+}
+#undef SE3_GRID_BLOCK
+#define SE3_GRID_BLOCK blockIdx
+
+__global__ __launch_bounds__(256) void bwd_dense_shared_kernel(const DenseRoles roles) {
+  const unsigned id = blockIdx.x;
+  int ri = 0;
+  if (roles.count > 1 && id >= roles.role[1].begin) ri = 1;
+  if (roles.count > 2 && id >= roles.role[2].begin) ri = 2;
+  const DenseRole& r = roles.role[ri];
+  const unsigned local = id - r.begin, rest = local / r.gx;
+  const VirtGrid g{local % r.gx, rest % r.gy, rest / r.gy, r.gy};
+  const auto a = static_cast<const uint32_t*>(r.a);
+  const auto b0 = static_cast<const uint16_t*>(r.b0), b1 = static_cast<const uint16_t*>(r.b1);
+  switch (r.kind) {
+    case dense_role_kind(kRoleStrip, 1, 2): gemm_strip_bf16_body<2>(g, a, b0, b1, static_cast<uint32_t*>(r.c), r.m, r.n, r.k); break;
+    case dense_role_kind(kRoleStrip, 1, 4): gemm_strip_bf16_body<4>(g, a, b0, b1, static_cast<uint32_t*>(r.c), r.m, r.n, r.k); break;
+    case dense_role_kind(kRoleStrip, 1, 8): gemm_strip_bf16_body<8>(g, a, b0, b1, static_cast<uint32_t*>(r.c), r.m, r.n, r.k); break;
+    case dense_role_kind(kRoleNnWords, 0, 1): dense_role_nn_words<0, 1>(g, r); break;
+    case dense_role_kind(kRoleNnWords, 1, 1): dense_role_nn_words<1, 1>(g, r); break;
+    case dense_role_kind(kRoleNnWords, 2, 1): dense_role_nn_words<2, 1>(g, r); break;
+    case dense_role_kind(kRoleNnT24, 0, 1): dense_role_nn_t24<0, 1>(g, r); break;
+    case dense_role_kind(kRoleNnT24, 2, 1): dense_role_nn_t24<2, 1>(g, r); break;
+    case dense_role_kind(kRoleTn, 2, 0): dense_role_tn<0>(g, r); break;
+    case dense_role_kind(kRoleTn, 2, 1): dense_role_tn<1>(g, r); break;
+    default: break;  // (the host adds no other kind)
   }
 }
 
@@ -1026,13 +715,75 @@ static GemmStripForm gemm_strip_bf16_form(int64_t m, int n, int k) {
   return {kp == 32 ? 2 : kp == 64 ? 4 : 8, dim3((unsigned)row_blocks, (unsigned)n_split)};
 }
 
+// A kernel whose dynamic LDS exceeds the default limit of 64 KB: the limit is raised once per (device, instantiation) -- a
+// runtime that keeps the attribute per device must see it on every device the process uses; `raised` is the instantiation's
+// set of devices done.  A failure is not cached.
+static int raise_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_t>& raised) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return SE3_ERR_LAUNCH;
+  const uint64_t bit = 1ull << (dev & 63);
+  if (raised.load(std::memory_order_relaxed) & bit) return SE3_OK;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return SE3_ERR_LAUNCH;
+  raised.fetch_or(bit, std::memory_order_relaxed);
+  return SE3_OK;
+}
+
+// ---- DenseShare: the roles of a shared launch ------------------------------------------------------------------------------
+int DenseShare::add(const DenseRole& r, dim3 grid, int lds) {
+  if (roles.count >= 3 || (int64_t)grid.x * grid.y * grid.z >= (1ll << 30)) return SE3_ERR_UNSUPPORTED;
+  int at = roles.count;
+  while (at > 0 && order[at - 1] > next_order) roles.role[at] = roles.role[at - 1], order[at] = order[at - 1], --at;
+  roles.role[at] = r;
+  roles.role[at].gx = grid.x, roles.role[at].gy = grid.y, roles.role[at].gz = grid.z;
+  order[at] = next_order;
+  ++roles.count;
+  if (lds > lds_bytes) lds_bytes = lds;
+  return SE3_OK;
+}
+
+constexpr int kDenseSharedMaxLds = TnLds<1>::bytes;  // the widest role: 65.5 KB (NN over packed words: 56 KB, over 3-byte rows: 52 KB, TN over words: 50 KB)
+static_assert(kDenseSharedMaxLds >= gemm_nn_bf16_lds_bytes(1) && kDenseSharedMaxLds >= gemm_nn_t24_lds_bytes(1) && kDenseSharedMaxLds >= TnLds<0>::bytes, "");
+
+int DenseShare::launch(hipStream_t stream) {
+  if (forms_only()) return form_report("bwd_dense_shared", "one_launch");
+  if (roles.count == 0) return SE3_OK;
+  unsigned blocks = 0;
+  for (int i = 0; i < roles.count; ++i) {
+    DenseRole& r = roles.role[i];
+    r.begin = blocks;
+    blocks += r.gx * r.gy * r.gz;
+  }
+  {
+    ProfScope prof("bwd_dense_shared", stream);
+    static std::atomic<uint64_t> raised;
+    if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(bwd_dense_shared_kernel), kDenseSharedMaxLds, raised)) return rc;
+    hipLaunchKernelGGL(bwd_dense_shared_kernel, dim3(blocks), dim3(256), lds_bytes, stream, roles);
+  }
+  if (after.set) {
+    const int rb = (int)((after.count + 255) / 256 < 2048 ? (after.count + 255) / 256 : 2048);
+    if (after.packed)
+      hipLaunchKernelGGL(reduce_splits_kernel<true>, dim3(rb), dim3(256), 0, stream, after.partials, after.out, after.count,
+                         after.splits, after.alpha_num, after.alpha_scale);
+    else
+      hipLaunchKernelGGL(reduce_splits_kernel<false>, dim3(rb), dim3(256), 0, stream, after.partials, after.out, after.count,
+                         after.splits, after.alpha_num, after.alpha_scale);
+  }
+  return check_launch();
+}
+
 int launch_gemm_strip_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, uint32_t* c,
-                           int64_t m, int n, int k, hipStream_t stream) {
+                           int64_t m, int n, int k, hipStream_t stream, DenseShare* share) {
   if (m == 0 || n == 0) return SE3_OK;
   if (!gemm_strip_bf16_applicable(m, n, k)) return SE3_ERR_UNSUPPORTED;
   const GemmStripForm f = gemm_strip_bf16_form(m, n, k);
   if (forms_only()) return form_report(tag, "gemm_strip_bf16<ks=%d>", f.ks);
-  ProfScope prof(tag, stream);
+  ProfScope prof(tag, stream);  // (a role of a shared launch keeps its stage's launch count; its time is the shared launch's)
+  if (share) {
+    DenseRole r{};
+    r.kind = dense_role_kind(kRoleStrip, 1, f.ks);
+    r.a = a, r.b0 = bt_hi, r.b1 = bt_lo, r.c = c, r.m = m, r.n = n, r.k = k;
+    return share->add(r, f.grid, 0);
+  }
   const auto kernel = f.ks == 2 ? gemm_strip_bf16_kernel<2> : f.ks == 4 ? gemm_strip_bf16_kernel<4> : gemm_strip_bf16_kernel<8>;
   hipLaunchKernelGGL(kernel, f.grid, dim3(256), 0, stream, a, bt_hi, bt_lo, c, m, n, k);
   return check_launch();
@@ -1089,22 +840,9 @@ static constexpr NnKernels nn_kernels() {
 }
 static const NnKernels kNnKernels[3] = {nn_kernels<0>(), nn_kernels<1>(), nn_kernels<2>()};
 
-// A kernel whose dynamic LDS exceeds the default limit of 64 KB: the limit is raised once per (device, instantiation) -- a
-// runtime that keeps the attribute per device must see it on every device the process uses; `raised` is the instantiation's
-// set of devices done.  A failure is not cached.
-static int raise_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_t>& raised) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return SE3_ERR_LAUNCH;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (raised.load(std::memory_order_relaxed) & bit) return SE3_OK;
-  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return SE3_ERR_LAUNCH;
-  raised.fetch_or(bit, std::memory_order_relaxed);
-  return SE3_OK;
-}
-
 static int gemm_nn_bf16_rows(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, void* c,
                              bool out_packed, int64_t m, int n, int k, float* split_ws, const float* alpha_num, float alpha_scale,
-                             hipStream_t stream, int afmt, ReduceBatch* defer) {
+                             hipStream_t stream, int afmt, ReduceBatch* defer, DenseShare* share) {
   const GemmNnBf16Form f = gemm_nn_bf16_form(m, n, k, split_ws != nullptr, out_packed, afmt);
   if (f.status) return f.status;
   const int kp = f.kp, per = f.per, st_per = f.st_per, splits = f.splits;
@@ -1118,7 +856,14 @@ static int gemm_nn_bf16_rows(const char* tag, const uint32_t* a, const uint16_t*
     const bool planes = f.afmt == 1 || f.afmt == 2;
     if (f.mode < 0 || f.mode > 2 || f.nb < 1 || f.nb > 2 || (f.afmt != 0 && !planes)) return SE3_ERR_UNSUPPORTED;
     const NnKernels& ks = kNnKernels[f.mode];
-    if (planes) {
+    if (share) {  // a role of the caller's shared launch: the buffer-load forms over packed words and 3-byte rows
+      if (f.afmt == 2 || (f.afmt == 0 && !f.fast) || f.nb != 1) return SE3_ERR_UNSUPPORTED;
+      DenseRole r{};
+      r.kind = dense_role_kind(planes ? kRoleNnT24 : kRoleNnWords, f.mode, f.nb);
+      r.a = a, r.b0 = bt_hi, r.b1 = bt_lo, r.c = out, r.m = m, r.n = n, r.k = k, r.kp = kp, r.per = planes ? st_per : per;
+      r.alpha_num = alpha_num, r.alpha_scale = alpha_scale;
+      if (int rc = share->add(r, grid, planes ? gemm_nn_t24_lds_bytes(f.nb) : gemm_nn_bf16_lds_bytes(f.nb))) return rc;
+    } else if (planes) {
       const NnPlanesKernel kernel = f.afmt == 1 ? ks.t24[f.nb - 1] : ks.t16[f.nb - 1];
       const int lds_bytes = f.afmt == 1 ? gemm_nn_t24_lds_bytes(f.nb) : 0;  // t16: static LDS
       // per t24 instantiation [mode][nb - 1]: the devices whose limit has been raised (only nb = 2, 72 KB, is beyond the default)
@@ -1139,6 +884,8 @@ static int gemm_nn_bf16_rows(const char* tag, const uint32_t* a, const uint16_t*
       defer->sum(split_ws, c, count, splits, alpha_num, alpha_scale, out_packed);
     else if (forms_only())
       ;
+    else if (share)  // behind the shared launch
+      share->after = {split_ws, c, count, splits, alpha_num, alpha_scale, out_packed, true};
     else if (out_packed)
       hipLaunchKernelGGL(reduce_splits_kernel<true>, dim3(rb), dim3(256), 0, stream, split_ws, c, count, splits,
                          alpha_num, alpha_scale);
@@ -1159,22 +906,30 @@ static int64_t gemm_nn_bf16_row_block(int64_t m, int k) {
 
 int launch_gemm_nn_bf16(const char* tag, const uint32_t* a, const uint16_t* bt_hi, const uint16_t* bt_lo, void* c,
                         bool out_packed, int64_t m, int n, int k, float* split_ws, const float* alpha_num,
-                        float alpha_scale, hipStream_t stream, int afmt, ReduceBatch* defer) {
+                        float alpha_scale, hipStream_t stream, int afmt, ReduceBatch* defer, DenseShare* share) {
   if (m == 0 || n == 0) return SE3_OK;
   const int64_t max_rows = gemm_nn_bf16_row_block(m, k);
+  if (share && max_rows) return SE3_ERR_UNSUPPORTED;  // (gemm_nn_bf16_sharable)
   if (forms_only() && max_rows) form_report(tag, "gemm_nn_row_blocks");
   ProfScope prof(tag, stream);
   if (!max_rows)
-    return gemm_nn_bf16_rows(tag, a, bt_hi, bt_lo, c, out_packed, m, n, k, split_ws, alpha_num, alpha_scale, stream, afmt, defer);
+    return gemm_nn_bf16_rows(tag, a, bt_hi, bt_lo, c, out_packed, m, n, k, split_ws, alpha_num, alpha_scale, stream, afmt, defer, share);
   const int64_t a_row_bytes = gemm_a_row_bytes(afmt, k);
   for (int64_t m0 = 0; m0 < m; m0 += max_rows) {
     const int64_t mb = m - m0 < max_rows ? m - m0 : max_rows;
     if (int rc = gemm_nn_bf16_rows(tag, reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a) + m0 * a_row_bytes), bt_hi,
                                    bt_lo, static_cast<char*>(c) + m0 * (int64_t)n * 4, out_packed, mb, n, k, nullptr, alpha_num,
-                                   alpha_scale, stream, afmt, nullptr))
+                                   alpha_scale, stream, afmt, nullptr, nullptr))
       return rc;
   }
   return SE3_OK;
+}
+
+// Whether the product can be a role of a shared launch: one block of rows, a buffer-load form with 64-column workgroups, no T16 rows
+bool gemm_nn_bf16_sharable(int64_t m, int n, int k, bool out_packed, int afmt) {
+  if (m <= 0 || n <= 0 || gemm_nn_bf16_row_block(m, k)) return false;
+  const GemmNnBf16Form f = gemm_nn_bf16_form(m, n, k, true, out_packed, afmt);
+  return !f.status && f.afmt != 2 && (f.afmt == 1 || f.fast) && f.nb == 1;
 }
 
 size_t gemm_nn_bf16_split_bytes(int64_t m, int n, int k) {
@@ -1206,9 +961,15 @@ static GemmTnBf16Form gemm_tn_bf16_form(int64_t m, int ka, int n, int splits, in
   return f;
 }
 
+bool gemm_tn_bf16_sharable(int64_t m, int ka, int n, int splits, int afmt) {
+  if (m <= 0 || ka <= 0 || n <= 0 || splits < 1) return false;
+  const GemmTnBf16Form f = gemm_tn_bf16_form(m, ka, n, splits, afmt);
+  return !f.status && f.fast && f.afmt != 2 && f.zs >= splits;
+}
+
 int launch_gemm_tn_bf16(const char* tag, const uint32_t* a, const uint32_t* b, float* c, float* partials, int splits,
                         int64_t m, int ka, int n, const float* alpha_num, float alpha_scale, hipStream_t stream, int afmt,
-                        ReduceBatch* defer, bool out_ikn) {
+                        ReduceBatch* defer, bool out_ikn, DenseShare* share) {
   if (ka == 0 || n == 0) return SE3_OK;
   if (out_ikn && (!defer || ka % kBasis != 0)) return SE3_ERR_INVALID_ARGUMENT;  // the permuted store lives in the batched reduction
   const GemmTnBf16Form f = gemm_tn_bf16_form(m, ka, n, splits, afmt);
@@ -1223,6 +984,17 @@ int launch_gemm_tn_bf16(const char* tag, const uint32_t* a, const uint32_t* b, f
   }
   ProfScope prof(tag, stream);
   const int64_t chunk = f.chunk, zs = f.zs;
+  if (share) {  // a role of the caller's shared launch: every row range in one grid, a buffer-load form (gemm_tn_bf16_sharable)
+    if (!f.fast || f.afmt == 2 || zs < splits || m <= 0 || !defer) return SE3_ERR_UNSUPPORTED;
+    DenseRole r{};
+    r.kind = dense_role_kind(kRoleTn, 2, f.afmt);
+    r.a = a, r.b0 = b, r.c = partials, r.m = m, r.chunk = chunk, r.n = n, r.k = ka;
+    if (int rc = share->add(r, dim3((unsigned)((ka + 127) / 128), (unsigned)((n + BN - 1) / BN), (unsigned)splits),
+                            f.afmt == 1 ? TnLds<1>::bytes : TnLds<0>::bytes))
+      return rc;
+    defer->sum(partials, c, (int64_t)ka * n, splits, alpha_num, alpha_scale, false, out_ikn ? n : 0);
+    return SE3_OK;
+  }
   const auto kernel = !f.fast      ? gemm_tn_bf16_kernel<false, 0>
                       : f.afmt == 2 ? gemm_tn_bf16_kernel<true, 2>
                       : f.afmt == 1 ? gemm_tn_bf16_kernel<true, 1>

@@ -263,6 +263,32 @@ AUG_CONSTS = 12      # SE3_AUG_CONSTS
 AUG_KINDS = {"rot_axis": 0, "rot_3d": 1, "center": 2, "linear": 3, "mirror": 4, "translation": 5, "stdnorm": 6,
              "drop": 16, "crop_box": 17, "crop_pts": 18}
 
+# the optimizer step: gradient norm in a fixed order, clip coefficient, AdamW, schedule table and accumulation gate in device words
+class Se3OptimTensor(C.Structure):
+    """struct se3_optim_tensor (include/se3conv_optim.h): one row of the tensor table."""
+
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("numel", C.c_int64), ("state_offset", C.c_int64)]
+
+
+class Se3OptimChunk(C.Structure):
+    """struct se3_optim_chunk (include/se3conv_optim.h): chunk `index` of tensor `tensor`."""
+
+    _fields_ = [("tensor", C.c_int32), ("index", C.c_int32)]
+
+
+_DBL = C.c_double
+_I64P = C.POINTER(C.c_int64)  # host
+OPTIM_SIGNATURES = {
+    "se3_optim_plan": (C.c_int, [_I64P, _I32, C.POINTER(Se3OptimTensor), C.POINTER(Se3OptimChunk), _I64, _I64P, _I64P]),
+    "se3_optim_workspace_bytes": (_SZ, [_I64]),
+    "se3_optim_grad_norm": (C.c_int, [_P, _I32, _P, _I64, _P, _P, _SZ, _P]),
+    "se3_optim_adamw_step": (C.c_int, [_P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _DBL, _DBL, _DBL, _F, _I32, _I32, _I32,
+                                       _P, _SZ, _P]),
+}
+OPTIM_CHUNK = 1024        # SE3_OPTIM_CHUNK: elements per chunk of the order of additions of the gradient norm
+OPTIM_STATE_WORDS = 5     # SE3_OPTIM_STATE_WORDS: it, t, b1p, b2p, skipped (8 bytes each)
+OPTIM_READOUT_WORDS = 4   # SE3_OPTIM_READOUT_WORDS: grad_norm, clip_coef, lr, stepped (4 bytes each)
+
 # The third registry, and meant to be the last: tests/test_knn_edges_abi.py pins ADDED_TABLES to its one header the way
 # tests/test_abi_tables.py pins TABLES to seven, so a header after those stands here, under the same rule and with the same
 # checks from a test file of its own.  Such a test asserts that its header is IN this registry, never what the registry
@@ -275,6 +301,7 @@ EXTENSION_TABLES = {
     "se3conv_seg_head.h": SEG_HEAD_SIGNATURES,
     "se3conv_basis_att.h": BASIS_ATT_SIGNATURES,
     "se3conv_augment.h": AUGMENT_SIGNATURES,
+    "se3conv_optim.h": OPTIM_SIGNATURES,
     "se3conv_pne.h": PNE_SIGNATURES,
 }
 

@@ -8,7 +8,7 @@ Layout mirrors the slice of ``point_cloud_lib`` that the path touches:
                          around the conv)
   se3conv3d_amd.pc       Pointcloud(RotEquiv), BQNeighborhood, PointHierarchy(RotEquiv), frame sampling
   se3conv3d_amd.ops      FeatBasisProj, BallQuery, ComputeKeys, SE3ConvFunction, SegLoss, LinearPNE, KPPNE, PneEmbed, NeighConvMax,
-                         BasisAttention (ctypes -> C ABI)
+                         BasisAttention, FusedBasisAttention (ctypes -> C ABI)
   se3conv3d_amd.metrics  SemSegMetrics: the reference's counters, kept on the device (include/se3conv_seg_head.h)
   se3conv3d_amd.augment  AugPipeline and the reference's augmentation classes on a whole batch (include/se3conv_augment.h)
   se3conv3d_amd.optim    AdamW with clipping, accumulation gate and schedule table in one capturable call, clip_grad_norm,
@@ -25,7 +25,7 @@ from .layers import (IConvLayer, IConvLayerFactory, LoRAttConvLayer, LoRAttConvL
                      MultiHeadAttLayerFactory, PNEConvLayer, PNEConvLayerFactory,
                      PNEConvLayerRotEquiv, PNEConvLayerRotEquivFactory, PreProcessModule, create_pts_icosphere)
 from .metrics import SemSegMetrics  # noqa: F401
-from .ops import (KPPNE, BallQuery, BasisAttention, ComputeKeys, FeatBasisProj, KNNQuery, LinearPNE, NeighConvMax, PneEmbed,  # noqa: F401
+from .ops import (KPPNE, BallQuery, BasisAttention, ComputeKeys, FeatBasisProj, FusedBasisAttention, KNNQuery, LinearPNE, NeighConvMax, PneEmbed,  # noqa: F401
                   SE3ConvFunction, SegLoss, get_precision, seg_loss, set_precision)
 from .optim import AdamW, ParamTables, clip_grad_norm, one_cycle_table  # noqa: F401
 from .pc import (BQNeighborhood, KnnNeighborhood, Pointcloud, PointcloudRotEquiv, PointHierarchy,  # noqa: F401

@@ -244,6 +244,15 @@ BASIS_ATT_SIGNATURES = {
 BASIS_ATT_CHUNK = 256        # SE3_BASIS_ATT_CHUNK: points per chunk of the order of additions of dpe
 BASIS_ATT_MAX_BASIS = 64     # SE3_BASIS_ATT_MAX_BASIS
 
+# the same attention edge-wise, without the aggregate [N, 2V, K]: per-edge scalars in place of T and dT
+ATT_FUSED_SIGNATURES = {
+    "se3_att_fused_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32, _I32]),
+    "se3_att_fused_fwd": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _P]),
+    "se3_att_fused_bwd": (C.c_int, [_P] * 10 + [_I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+}
+ATT_FUSED_CHUNK = 256        # SE3_ATT_FUSED_CHUNK: points per chunk of the order of additions of dpe
+ATT_FUSED_SLAB = 64          # SE3_ATT_FUSED_SLAB: edges of a sample a wavefront holds at a time
+
 # the augmentation pipeline on a batch: statistics per element, the affine table, apply + noise, keep masks, compaction
 _U32 = C.c_uint32
 _D = C.POINTER(C.c_double)   # host: the constants of a step
@@ -302,6 +311,7 @@ EXTENSION_TABLES = {
     "se3conv_basis_att.h": BASIS_ATT_SIGNATURES,
     "se3conv_augment.h": AUGMENT_SIGNATURES,
     "se3conv_optim.h": OPTIM_SIGNATURES,
+    "se3conv_att_fused.h": ATT_FUSED_SIGNATURES,
     "se3conv_pne.h": PNE_SIGNATURES,
 }
 

@@ -485,10 +485,14 @@ class MultiHeadAttLayer(IConvLayer):
     Parameters and buffers by the reference's names and shapes (``kernel_pts_ [13|55,3]``, ``proj_axes_ [J,K]``, ``proj_biases_ [K]``,
     ``linear_kqv_``, ``w_out_``, ``pe_ [1,K,V]``) and its init bounds; the kernel points are rotated once with a uniformly drawn
     rotation.  As in the reference there is no ``1/sqrt(D)`` and the bias of ``w_out_`` is scaled by ``nu`` too (DESIGN.md "Quirks").
-    ``p_num_basis`` is one of FeatBasisProj's; input and output cloud are one object; capacity-bounded neighbourhoods are refused."""
+    ``p_num_basis`` is one of FeatBasisProj's; input and output cloud are one object; capacity-bounded neighbourhoods are refused.
 
-    def __init__(self, p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads):
+    ``p_fused=True`` (the attribute ``fused_``; no parameter or buffer, so the state dict is the reference's either way) runs
+    ``PneEmbed -> linear_kqv_ -> ops.FusedBasisAttention -> w_out_``: the same function edge-wise, without ``T``."""
+
+    def __init__(self, p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads, p_fused=False):
         super().__init__(p_dims, p_in_features, p_out_features)
+        self.fused_ = bool(p_fused)
         if p_dims != 3:
             raise NotImplementedError(f"{type(self).__name__} on the HIP library: 3-D points")
         if p_kp_res not in _KP_RES:
@@ -531,24 +535,49 @@ class MultiHeadAttLayer(IConvLayer):
         agg = ops.BasisAttention.apply(t, x[:, 2 * v:], self.pe_, self.num_heads_)
         return self.w_out_(agg), t
 
+    def _attend_fused(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
+        """``(w_out_(attention), phi, x, nb32)`` of the edge-wise operator: no ``T``."""
+        if p_pc_in is not p_pc_out:
+            raise AssertionError(f"{type(self).__name__}: the input and the output cloud must be the same object, as in the reference")
+        if getattr(p_neighborhood, "edge_info_", None) is not None:
+            raise NotImplementedError("a capacity-bounded neighbourhood (rows past the edge count are unset) cannot feed "
+                                      "the fused attention (p_fused=True): build the neighbourhood without p_capacity")
+        nb32 = getattr(p_neighborhood, "neighbors_i32_", None)
+        if nb32 is None:
+            nb32 = p_neighborhood.neighbors_
+        phi = ops.PneEmbed.apply(p_pc_in.pts_, p_pc_out.pts_, nb32, self.proj_axes_, self.proj_biases_, self.norm_neigh_dist_,
+                                 "kp_gauss", self.kernel_pts_, self.kp_sigma_)
+        x = self.linear_kqv_(p_in_features)
+        agg = ops.FusedBasisAttention.apply(phi, x, self.pe_, nb32, p_neighborhood.start_ids_, self.num_heads_, p_neighborhood)
+        return self.w_out_(agg), phi, x, nb32
+
     def __compute_convolution__(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
+        if self.fused_:
+            return self._attend_fused(p_pc_in, p_pc_out, p_in_features, p_neighborhood)[0] * self.norm_num_neighs_
         return self._attend(p_pc_in, p_pc_out, p_in_features, p_neighborhood)[0] * self.norm_num_neighs_
 
 
 class LoRAttConvLayer(MultiHeadAttLayer):
     """The reference's low-rank attention convolution (``layers/LoRAttConvLayer.py:11-163``): ``MultiHeadAttLayer`` plus an ordinary
     continuous convolution on the value half of the same aggregate, ``sum_{k,i} Tv[s,i,k] conv_weights_[k,i,o]``, both scaled by
-    ``nu``.  ``conv_weights_ [K,V,C_out]`` as in the reference; the product reads ``Tv`` as a view of ``T``."""
+    ``nu``.  ``conv_weights_ [K,V,C_out]`` as in the reference; the product reads ``Tv`` as a view of ``T``.
 
-    def __init__(self, p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads):
-        super().__init__(p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads)
+    ``p_fused=True``: the attention goes through ``ops.FusedBasisAttention``; the dense product keeps ``FeatBasisProj``, but over the
+    ``V`` value columns only (``x[:, :V]``): ``Tv [N,V,K]``, half of the unfused ``T`` and none of its query half."""
+
+    def __init__(self, p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads, p_fused=False):
+        super().__init__(p_dims, p_in_features, p_out_features, p_num_basis, p_kp_res, p_num_heads, p_fused)
         bound = math.sqrt(1.0 / (self.value_size_ * p_num_basis))
         self.conv_weights_ = torch.nn.Parameter(torch.empty(p_num_basis, self.value_size_, p_out_features).uniform_(-bound, bound))
 
     def __compute_convolution__(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
-        att, t = self._attend(p_pc_in, p_pc_out, p_in_features, p_neighborhood)
         v, k = self.value_size_, self.num_basis_
         w = self.conv_weights_.permute(1, 0, 2).reshape(v * k, self.feat_output_size_)
+        if self.fused_:
+            att, phi, x, nb32 = self._attend_fused(p_pc_in, p_pc_out, p_in_features, p_neighborhood)
+            tv = ops.FeatBasisProj.apply(phi, x[:, :v], nb32, p_neighborhood.start_ids_)
+            return (att + torch.matmul(tv.reshape(tv.shape[0], v * k), w)) * self.norm_num_neighs_
+        att, t = self._attend(p_pc_in, p_pc_out, p_in_features, p_neighborhood)
         conv = torch.matmul(t[:, :v, :].reshape(t.shape[0], v * k), w)
         return (att + conv) * self.norm_num_neighs_
 
@@ -558,11 +587,12 @@ class MultiHeadAttLayerFactory(IConvLayerFactory):
 
     _layer = MultiHeadAttLayer
 
-    def __init__(self, p_dims, p_num_basis, p_kp_res, p_num_heads):
+    def __init__(self, p_dims, p_num_basis, p_kp_res, p_num_heads, p_fused=False):
         super().__init__(p_dims)
         self.num_basis_ = p_num_basis
         self.kp_res_ = p_kp_res
         self.num_heads_ = p_num_heads
+        self.fused_ = bool(p_fused)   # handed to the layers: the edge-wise attention without T
 
     def update_parameters(self, **kwargs):
         # an `elif` chain, as in the reference: only the first key present is applied (DESIGN.md "Quirks")
@@ -574,7 +604,7 @@ class MultiHeadAttLayerFactory(IConvLayerFactory):
             self.num_heads_ = kwargs["num_heads"]
 
     def __create_conv_layer_imp__(self, p_in_features, p_out_features):
-        return self._layer(self.dims_, p_in_features, p_out_features, self.num_basis_, self.kp_res_, self.num_heads_)
+        return self._layer(self.dims_, p_in_features, p_out_features, self.num_basis_, self.kp_res_, self.num_heads_, self.fused_)
 
 
 class LoRAttConvLayerFactory(MultiHeadAttLayerFactory):

@@ -2065,6 +2065,76 @@ class BasisAttention(torch.autograd.Function):
         return d_t.to(dt_t), d_key.to(dt_key), d_pe.reshape(shape_pe).to(dt_pe), None
 
 
+class FusedBasisAttention(torch.autograd.Function):
+    """``FeatBasisProj -> BasisAttention`` as one edge-wise operator (``se3_att_fused_fwd`` / ``_bwd``, include/se3conv_att_fused.h):
+    with ``phi [E,K]``, ``x = linear_kqv_(f) [N,3V]`` (value | query | key), ``pe [K,V]`` or ``[1,K,V]`` and the edges (sample, source)
+    of one cloud grouped by sample,
+
+        c[e,h] = sum_{i in h} xq[p_e,i] key[s,i]      att[s,:,h] = softmax_k(sum_{e in s} phi[e,k] c[e,h] + sum_{i in h} pe[k,i] key[s,i])
+        a[e,h] = sum_k phi[e,k] att[s,k,h]            out[s,i] = sum_{e in s} a[e,h(i)] xv[p_e,i]
+
+    which is what the two operators compute through ``T [N,2V,K]`` -- ``T`` is linear in ``phi``, so it never exists.  Returns
+    ``out [N,V]``; gradients go to ``phi``, ``x`` and ``pe``.  ``cache``: an object (the neighbourhood) that keeps the source-major
+    transposition the backward needs (``neigh_transposition``)."""
+
+    @staticmethod
+    def forward(ctx, phi, x, pe, neighbors, ends, num_heads, cache=None):
+        lib = _lib.load()
+        f32, i32 = torch.float32, torch.int32
+        for name, t in (("phi", phi), ("x", x), ("pe", pe), ("neighbors", neighbors), ("ends", ends)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"FusedBasisAttention: {name} must be a GPU tensor (the HIP path has no CPU fallback)")
+        ph, xr = _as(phi, f32), _as(x, f32)
+        nb, en = _as(neighbors, i32), _as(ends, i32)
+        if ph.dim() != 2 or xr.dim() != 2 or xr.shape[1] % 3:
+            raise ValueError(f"FusedBasisAttention: phi of shape {tuple(phi.shape)} and x of shape {tuple(x.shape)}, expected [E, K] and [N, 3V]")
+        (e, k), n, v = ph.shape, xr.shape[0], xr.shape[1] // 3
+        h = int(num_heads)
+        if h < 1 or v < 1 or v % h:
+            raise ValueError(f"FusedBasisAttention: {h} heads do not divide the value size {v}")
+        if not 1 <= k <= _lib.BASIS_ATT_MAX_BASIS:
+            raise ValueError(f"FusedBasisAttention: {k} basis functions, expected 1 .. {_lib.BASIS_ATT_MAX_BASIS}")
+        if tuple(pe.shape) not in ((k, v), (1, k, v)):
+            raise ValueError(f"FusedBasisAttention: pe of shape {tuple(pe.shape)}, expected {(k, v)} or {(1, k, v)}")
+        if nb.dim() != 2 or nb.shape[1] != 2 or nb.shape[0] != e:
+            raise ValueError("FusedBasisAttention: neighbors must be [E,2], one row per row of phi")
+        if tuple(en.shape) != (n,):
+            raise ValueError(f"FusedBasisAttention: ends of shape {tuple(ends.shape)} for {n} rows of x (samples and sources are one cloud)")
+        p = _as(pe, f32).reshape(k, v)
+        dev = xr.device
+        att = _empty((n, k, h), dtype=f32, device=dev)
+        out = _empty((n, v), dtype=f32, device=dev)
+        _lib.check(lib.se3_att_fused_fwd(_ptr(ph, f32, "phi", dev), _ptr(xr, f32, "x"), _ptr(p, f32, "pe", dev),
+                                         _ptr(nb, i32, "neighbors", dev), _ptr(en, i32, "ends", dev), n, e, v, h, k,
+                                         _ptr(att, f32, "att"), _ptr(out, f32, "out"), _stream(dev)), "se3_att_fused_fwd")
+        ctx.save_for_backward(ph, xr, p, nb, en, att)
+        ctx.cache = cache
+        ctx.call = (h, phi.dtype, x.dtype, pe.dtype, tuple(pe.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f32, i32 = torch.float32, torch.int32
+        ph, xr, p, nb, en, att = ctx.saved_tensors
+        h, dt_phi, dt_x, dt_pe, shape_pe = ctx.call
+        (e, k), n, v = ph.shape, xr.shape[0], xr.shape[1] // 3
+        g = _as(g, f32)
+        dev = xr.device
+        if e:
+            ts, te, tid = neigh_transposition(nb, n, ctx.cache)
+        else:  # nothing to transpose: no source has an incoming edge
+            ts, te, tid = None, torch.zeros(n, dtype=i32, device=dev), None
+        d_phi, d_x, d_pe = _empty_like(ph), _empty_like(xr), _empty_like(p)
+        ws = _workspace(lib.se3_att_fused_workspace_bytes(n, e, v, h, k), dev)
+        _lib.check(lib.se3_att_fused_bwd(_ptr(g, f32, "grad_out", dev), _ptr(ph, f32, "phi"), _ptr(xr, f32, "x"), _ptr(p, f32, "pe"),
+                                         _ptr(att, f32, "att"), _ptr(nb, i32, "neighbors"), _ptr(en, i32, "ends"),
+                                         _ptr(ts, i32, "t_samples"), _ptr(te, i32, "t_ends"), _ptr(tid, i32, "t_edge_ids"), n, e, v, h, k,
+                                         _ptr(d_phi, f32, "dphi"), _ptr(d_x, f32, "dx"), _ptr(d_pe, f32, "dpe"),
+                                         C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dev)), "se3_att_fused_bwd")
+        return d_phi.to(dt_phi), d_x.to(dt_x), d_pe.reshape(shape_pe).to(dt_pe), None, None, None, None
+
+
 # ------------------------------------------------------------------ row-wise glue of a block (row f-3)
 def _glue_ws(c: int, dev) -> torch.Tensor:
     return _workspace(_lib.load().se3_glue_workspace_bytes(int(c)), dev)

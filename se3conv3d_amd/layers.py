@@ -65,7 +65,9 @@ class IConvLayer(PreProcessModule, ABC):
 
     def forward(self, p_pc_in, p_pc_out, p_in_features, p_neighborhood):
         if self.pre_process_:
-            with torch.no_grad():
+            # (inference_mode(False): a buffer rebound inside a caller's inference_mode block would be an inference tensor,
+            # which autograd refuses to save in the next training step)
+            with torch.no_grad(), torch.inference_mode(False):
                 # IConvLayer.py:76-97.  Ball query: 1/radius.  (kNN neighbourhoods use half the
                 # inverse mean edge length.)  nu uses point-level M / E.
                 radius = getattr(p_neighborhood, "radius_", None)
@@ -130,7 +132,7 @@ def _geometry_of(p_pc_in, p_pc_out, p_neighborhood) -> ops.ConvGeometry:
                (p_pc_out.local_frames_, geom.frames_out))
     # the tensors the geometry holds as converted COPIES (float64 points, non-contiguous frames, ...), with the version of
     # the cloud's tensor they were made from: an in-place update of the cloud must reach them
-    copies = [[src, held, src._version] for src, held in sources if held.data_ptr() != src.data_ptr()]
+    copies = [[src, held, ops.version_key(src)] for src, held in sources if held.data_ptr() != src.data_ptr()]
     try:
         p_neighborhood._se3_geom = (key, geom, copies)
     except AttributeError:
@@ -147,9 +149,9 @@ def _refresh_copies(geom: ops.ConvGeometry, copies) -> None:
     capturing = geom.pts_out.is_cuda and torch.cuda.is_current_stream_capturing()
     for entry in copies:
         src, held, version = entry
-        if capturing or src._version != version:
+        if capturing or ops.version_key(src) != version:
             held.copy_(src.detach().reshape(held.shape))
-            entry[2] = src._version
+            entry[2] = ops.version_key(src)
 
 
 _ACTIVATIONS = {"mlp_gelu": torch.nn.functional.gelu, "mlp_relu": torch.relu, "mlp_sin": torch.sin, "mlp_linear": (lambda t: t),

@@ -84,6 +84,14 @@ def _as(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return t.detach().to(dtype).contiguous()
 
 
+def version_key(t: torch.Tensor):
+    """What a per-cloud cache key holds for "the contents of ``t`` are still those": the tensor's version counter.  A
+    tensor created under ``torch.inference_mode()`` has none (reading ``_version`` raises) and can be updated in place
+    without a trace, so nothing is cached on it: its key entry is a fresh object, equal to no other, and every cache that
+    carries it rebuilds -- as they do while a graph is being captured."""
+    return object() if t.is_inference() else t._version
+
+
 def _valid_word(n_valid, device, who: str) -> C.c_void_p:
     """The row-count word of a padded cloud (include/se3conv_padded.h): one int32 on the device, or None = every row."""
     p = _ptr(n_valid, torch.int32, "n_valid", device)
@@ -315,9 +323,9 @@ class SourceGrids:
         temporary's address says nothing about the cloud and may be recycled by the next temporary.  A padded cloud's grid
         is also keyed on its row-count word (storage and version: a new count is a new grid), which keeps it apart from
         the grids of the other queries."""
-        key = (pts.data_ptr(), pts._version, batch_ids.data_ptr(), batch_ids._version, int(pts.shape[0]),
+        key = (pts.data_ptr(), version_key(pts), batch_ids.data_ptr(), version_key(batch_ids), int(pts.shape[0]),
                int(n_batches or 0), str(pts.device))
-        return key if n_valid is None else key + (n_valid.data_ptr(), n_valid._version)
+        return key if n_valid is None else key + (n_valid.data_ptr(), version_key(n_valid))
 
     def slot(self, key, radius, nbytes, device):
         """``(buffer, valid)`` for this radius; ``valid`` says the buffer already holds the grid of ``key``.  A buffer
@@ -1486,7 +1494,8 @@ class PreparedRecords:
         self.tensor, self.valid, self.key, self.capture = None, False, None, None
 
     def bind(self, pts: torch.Tensor, frames: torch.Tensor) -> "PreparedRecords":
-        key = (pts.data_ptr(), pts._version, frames.data_ptr(), frames._version, tuple(frames.shape), str(pts.device))
+        key = (pts.data_ptr(), version_key(pts), frames.data_ptr(), version_key(frames), tuple(frames.shape),
+               str(pts.device))
         if key != self.key:
             rows = frames.shape[0] * frames.shape[1]
             if self.tensor is None or self.tensor.shape[0] != rows or self.tensor.device != pts.device:

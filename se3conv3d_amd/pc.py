@@ -216,11 +216,12 @@ class Pointcloud(object):
         them in every ball query, BallQuery.py:35-36; a cloud is the source of three or four queries per step)."""
         box = getattr(self, "_se3_aabb", None)
         # (points or batch ids replaced or changed in place: new boxes)
-        key = (self.pts_.data_ptr(), self.pts_._version, self.batch_ids_.data_ptr(), self.batch_ids_._version)
+        key = (self.pts_.data_ptr(), ops.version_key(self.pts_), self.batch_ids_.data_ptr(),
+               ops.version_key(self.batch_ids_))
         if self.n_valid_ is not None:
             # a padded cloud: the boxes of the present rows -- recomputed when the count word changes, and inside a graph
             # capture once per capture (a replay must follow the word; boxes from an earlier node of the same graph do)
-            key += (self.n_valid_.data_ptr(), self.n_valid_._version)
+            key += (self.n_valid_.data_ptr(), ops.version_key(self.n_valid_))
             if torch.cuda.is_current_stream_capturing():
                 key += (ops._capture_id(self.pts_.device),)
                 held = getattr(self, "_se3_aabb_captured", None)
@@ -329,9 +330,9 @@ class PointcloudRotEquiv(Pointcloud):
         if self.pts_.is_cuda and torch.cuda.is_current_stream_capturing():
             return query()
         cache = self.__dict__.setdefault("_se3_knn_ids", {})
-        key = (int(k), self.pts_.data_ptr(), self.pts_._version)
+        key = (int(k), self.pts_.data_ptr(), ops.version_key(self.pts_))
         if self.n_valid_ is not None:
-            key += (self.n_valid_.data_ptr(), self.n_valid_._version)
+            key += (self.n_valid_.data_ptr(), ops.version_key(self.n_valid_))
         if key not in cache:
             cache.clear()
             cache[key] = query()

@@ -2,7 +2,7 @@
  * se3conv_augment.h -- the augmentation pipeline of libse3conv_hip.so: what point_cloud_lib/augment/ of the reference does
  * to ONE scene on the host, done to a whole batch on the device.  Every batch element is augmented on its own, every random
  * choice comes from numbers the caller supplies (`draws`) or from a counter-based hash of a seed word, crops write into
- * padded clouds and leave the surviving count in a device word.  ElasticDistortionAug has no entry point here.
+ * padded clouds and leave the surviving count in a device word.  ElasticDistortionAug has no entry point here: se3conv_elastic.h.
  *
  * Same conventions as se3conv.h (extern "C", device pointers unless marked "host", caller-owned outputs and workspace,
  * asynchronous on `stream`, no host synchronisation, capturable into a HIP graph, no memset calls, int status).  These

@@ -272,6 +272,17 @@ AUG_CONSTS = 12      # SE3_AUG_CONSTS
 AUG_KINDS = {"rot_axis": 0, "rot_3d": 1, "center": 2, "linear": 3, "mirror": 4, "translation": 5, "stdnorm": 6,
              "drop": 16, "crop_box": 17, "crop_pts": 18}
 
+# ElasticDistortionAug on a batch: grid dims and offsets per (element, octave), blurred hashed noise grids, the look-up per row
+ELASTIC_SIGNATURES = {
+    "se3_elastic_workspace_bytes": (_SZ, [_I32, _I32]),
+    "se3_elastic_plan": (C.c_int, [_P, _P, _P, _F, _D, _I32, _I32, _I64, _P, _P, _P, _SZ, _P]),
+    "se3_elastic_grids": (C.c_int, [_P, _I32, _I32, _I64, _U32, _P, _U32, _P, _P, _P, _SZ, _P]),
+    "se3_elastic_displace": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _I32, _D, _P, _P, _P]),
+}
+ELASTIC_MAX_OCTAVES = 4            # SE3_ELASTIC_MAX_OCTAVES
+ELASTIC_TILE = 8                   # SE3_ELASTIC_TILE: edge of the blur kernel's output tile
+ELASTIC_MAX_QUOTIENT = 1 << 20     # SE3_ELASTIC_MAX_QUOTIENT: extent / granularity from which a box counts as not finite
+
 # the optimizer step: gradient norm in a fixed order, clip coefficient, AdamW, schedule table and accumulation gate in device words
 class Se3OptimTensor(C.Structure):
     """struct se3_optim_tensor (include/se3conv_optim.h): one row of the tensor table."""
@@ -312,6 +323,7 @@ EXTENSION_TABLES = {
     "se3conv_augment.h": AUGMENT_SIGNATURES,
     "se3conv_optim.h": OPTIM_SIGNATURES,
     "se3conv_att_fused.h": ATT_FUSED_SIGNATURES,
+    "se3conv_elastic.h": ELASTIC_SIGNATURES,
     "se3conv_pne.h": PNE_SIGNATURES,
 }
 

@@ -15,7 +15,12 @@ the table: the transformed cloud is not written for that), and writes points onl
 Differences from the reference, all stated in the header: ``CropBoxAug`` draws its box once (an element whose box holds no
 point comes out empty, the reference draws again); ``CropPtsAug`` breaks distance ties by row order; the Gaussian numbers are
 Box-Muller on hashed words; ``RotationAug3D`` makes its quaternion from four uniform draws; ``LinearAug``'s per-epoch value
-tables are taken in float32; ``ElasticDistortionAug`` is not implemented and refused."""
+tables are taken in float32.
+
+``ElasticDistortionAug`` (include/se3conv_elastic.h) is opt-in, ``AugPipeline(p_elastic=True)``; without the switch the name is
+refused as before.  It is a switch because the step needs a grid buffer the caller sizes (``grid_capacity``, in cells: nothing
+is read back to size it, an element that does not fit stays undistorted and ``overflow_`` says so), and because its random
+field is the hash's, reproducible from (seed, step, element), not torch's ``randn`` stream."""
 from __future__ import annotations
 
 import ctypes as C
@@ -122,6 +127,62 @@ def aug_compact(mask, batch_ids, n_batches: int, n_valid=None, idx_in=None):
                                    ops._ptr(counts, torch.int32, "counts"), C.c_void_p(ws.data_ptr()), nbytes, ops._stream(dev)),
                "se3_aug_compact")
     return idx, n_out, counts, idx_orig
+
+
+def _octaves(values, what) -> C.Array:
+    if not 1 <= len(values) <= _lib.ELASTIC_MAX_OCTAVES:
+        raise ValueError(f"{what}: 1 to {_lib.ELASTIC_MAX_OCTAVES} octaves, got {len(values)}")
+    return (C.c_double * len(values))(*[float(v) for v in values])
+
+
+def aug_elastic_plan(counts, stats, draws, prob: float, granularity, grid_capacity: int):
+    """``(grid_table [B, L, 4] int64 = (nx, ny, nz, offset), overflow [1] int32, workspace)`` (``se3_elastic_plan``): the noise
+    grid of every (element, octave) laid into ``grid_capacity`` cells; offset -1 for an element that is not distorted; the
+    workspace holds the tile prefix ``aug_elastic_grids`` deals its tiles by."""
+    dev, nb = stats.device, int(stats.shape[0])
+    lib = _lib.load()
+    g = _octaves(granularity, "p_granularity")
+    table = ops._empty((nb, len(g), 4), dtype=torch.int64, device=dev)
+    overflow = ops._empty(1, dtype=torch.int32, device=dev)
+    nbytes = lib.se3_elastic_workspace_bytes(nb, len(g))
+    ws = ops._workspace(nbytes, dev)
+    _lib.check(lib.se3_elastic_plan(ops._ptr(counts, torch.int32, "counts", dev), ops._ptr(stats, torch.float32, "stats"),
+                                    ops._ptr(draws, torch.float32, "draws", dev), float(prob), g, len(g), nb, int(grid_capacity),
+                                    ops._ptr(table, torch.int64, "grid_table"), ops._ptr(overflow, torch.int32, "overflow"),
+                                    C.c_void_p(ws.data_ptr()), nbytes, ops._stream(dev)), "se3_elastic_plan")
+    return table, overflow, ws
+
+
+def aug_elastic_grids(grid_table, workspace, grid_capacity: int, seed: int = 0, seed_tensor=None, step: int = 0, noise_in=None, grid=None):
+    """``grid [grid_capacity, 4]`` float32 (``se3_elastic_grids``): the blurred noise of every placed entry of ``grid_table``,
+    lanes 0..2 the displacement along x, y, z.  ``noise_in`` (same layout): raw numbers in place of the hash's; ``grid``: a
+    buffer to write into (rows behind the placed total are left as they are)."""
+    dev, (nb, nl) = grid_table.device, (int(grid_table.shape[0]), int(grid_table.shape[1]))
+    cap = int(grid_capacity)
+    if grid is None:
+        grid = ops._empty((max(cap, 1), 4), dtype=torch.float32, device=dev)   # (one row at least: a pointer to hand on)
+    for name, buf in (("grid", grid), ("noise_in", noise_in)):
+        if buf is not None and (buf.dim() != 2 or buf.shape[1] != 4 or buf.shape[0] < cap):
+            raise ValueError(f"{name}: expected [>= {cap}, 4], got {tuple(buf.shape)}")
+    _lib.check(_lib.load().se3_elastic_grids(
+        ops._ptr(grid_table, torch.int64, "grid_table"), nb, nl, cap, int(seed) & 0xFFFFFFFF, _seed_word(seed_tensor, dev), int(step),
+        ops._ptr(noise_in, torch.float32, "noise_in", dev), ops._ptr(grid, torch.float32, "grid", dev), C.c_void_p(workspace.data_ptr()),
+        int(workspace.numel()), ops._stream(dev)), "se3_elastic_grids")
+    return grid
+
+
+def aug_elastic_displace(x, batch_ids, n_batches: int, stats, grid_table, magnitude, grid, n_valid=None):
+    """The rows of every distorted element moved through their octaves in turn, the others copied (``se3_elastic_displace``)."""
+    dev, n = _cloud(x, batch_ids, "aug_elastic_displace")
+    m = _octaves(magnitude, "p_magnitude")
+    if tuple(grid_table.shape) != (n_batches, len(m), 4):
+        raise ValueError(f"grid_table: expected {(n_batches, len(m), 4)}, got {tuple(grid_table.shape)}")
+    y = ops._empty((n, 3), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().se3_elastic_displace(
+        ops._ptr(x, torch.float32, "x"), ops._ptr(batch_ids, torch.int32, "batch_ids", dev), n, ops._valid_word(n_valid, dev, "aug_elastic_displace"),
+        n_batches, ops._ptr(stats, torch.float32, "stats", dev), ops._ptr(grid_table, torch.int64, "grid_table", dev), len(m), m,
+        ops._ptr(grid, torch.float32, "grid", dev), ops._ptr(y, torch.float32, "y"), ops._stream(dev)), "se3_elastic_displace")
+    return y
 
 
 # ------------------------------------------------------------------------------------------------------------------ the classes
@@ -279,7 +340,25 @@ class CropPtsAug(Augmentation):
         return [self.max_pts_, self.crop_ratio_]
 
 
-NOT_IMPLEMENTED = ("ElasticDistortionAug",)   # names of the reference that have no kernel here
+class ElasticDistortionAug(Augmentation):
+    """One blurred noise grid per octave, sampled at the points the octave before moved (include/se3conv_elastic.h).  The
+    reference returns the extra tensors untouched whatever their flags (ElasticDistortionAug.py:91), and so does this one."""
+    kind_ = "elastic"
+
+    def __init__(self, p_prob=1.0, p_granularity=[0.1], p_magnitude=[0.2], p_apply_extra_tensors=[], **kwargs):
+        if len(p_granularity) != len(p_magnitude) or not 1 <= len(p_granularity) <= _lib.ELASTIC_MAX_OCTAVES:
+            raise ValueError(f"ElasticDistortionAug: p_granularity and p_magnitude are lists of one length, 1 to {_lib.ELASTIC_MAX_OCTAVES} "
+                             f"octaves; got {len(p_granularity)} and {len(p_magnitude)}")
+        if not all(float(g) > 0 for g in p_granularity):
+            raise ValueError(f"ElasticDistortionAug: p_granularity {list(p_granularity)}")
+        self.granularity_, self.magnitude_ = list(p_granularity), list(p_magnitude)
+        super().__init__(p_prob, p_apply_extra_tensors)
+
+    def _consts(self):
+        return self.granularity_ + self.magnitude_
+
+
+OPT_IN = ("ElasticDistortionAug",)   # names AugPipeline knows only with p_elastic=True; refused as not implemented without
 
 
 class AugmentedBatch:
@@ -287,21 +366,29 @@ class AugmentedBatch:
     ``n_valid_`` is the device word of present rows (None when nothing can remove points and none was given); ``idx_`` the
     original row of every surviving row (-1 behind them; None without a removal); ``extra_tensors_`` the extra tensors, the
     cropped ones padded like the points; ``affine_`` the composed table of the last write of the points (None: none was
-    needed); ``overflow_`` the flag of the elastic grid, None as long as that step is not implemented."""
+    needed); ``overflow_`` the flag of the elastic grid, a device word (bit 0: an element did not fit into ``grid_capacity`` and
+    stayed undistorted, bit 1: an element's box was not finite; the OR over the pipeline's elastic steps), None for a
+    pipeline without that step."""
 
-    def __init__(self, pts, batch_ids, n_valid, idx, extra_tensors, affine, cropped, extra_n_valid):
+    def __init__(self, pts, batch_ids, n_valid, idx, extra_tensors, affine, cropped, extra_n_valid, overflow=None):
         self.pts_, self.batch_ids_, self.n_valid_, self.idx_ = pts, batch_ids, n_valid, idx
-        self.extra_tensors_, self.affine_, self.overflow_ = extra_tensors, affine, None
+        self.extra_tensors_, self.affine_, self.overflow_ = extra_tensors, affine, overflow
         self.cropped_ = cropped   # per extra tensor: whether it went through a compaction
         self.extra_n_valid_ = extra_n_valid   # per extra tensor: the device word of ITS present rows (the points' word only for
         #                                       those that went through every removing step; None: all rows)
 
 
 class AugPipeline:
-    """The reference's ``AugPipeline``: ``create_pipeline(list of dict)`` with the classes looked up by ``name``."""
+    """The reference's ``AugPipeline``: ``create_pipeline(list of dict)`` with the classes looked up by ``name``.
 
-    def __init__(self):
-        self.aug_classes_ = {sub.__name__: sub for sub in Augmentation.__subclasses__()}
+    ``p_elastic=True`` makes ``ElasticDistortionAug`` known, so that the reference's ScanNet training lists are taken
+    unchanged.  It is a switch and off by default for two reasons: the step needs a grid the caller sizes (``augment_batch(...,
+    grid_capacity=cells)``; a pipeline that holds the step cannot run without it), and its random field comes from the hash of
+    (seed, step, element), not from torch's ``randn`` stream as in the reference."""
+
+    def __init__(self, p_elastic: bool = False):
+        self.elastic_ = bool(p_elastic)
+        self.aug_classes_ = {sub.__name__: sub for sub in Augmentation.__subclasses__() if self.elastic_ or sub.__name__ not in OPT_IN}
         self.pipeline_: List[Augmentation] = []
         self._identity = {}   # (device, n_batches) -> the identity table; made on first use, copied (never zero-filled) afterwards
 
@@ -309,7 +396,7 @@ class AugPipeline:
         pipeline = []
         for cur_dict in p_dict_list:
             name = cur_dict["name"]
-            if name in NOT_IMPLEMENTED:
+            if name in OPT_IN and not self.elastic_:
                 raise NotImplementedError(f"{name} is not implemented on the device")
             if name not in self.aug_classes_:
                 raise KeyError(f"unknown augmentation {name!r}: known are {sorted(self.aug_classes_)}")
@@ -327,15 +414,41 @@ class AugPipeline:
     def removes_points(self) -> bool:
         return any(a.kind_ in ("crop_box", "crop_pts") or (a.kind_ == "drop" and not a.keep_zeros_) for a in self.pipeline_)
 
+    def elastic_capacity(self, extent, n_batches: int = 1) -> int:
+        """Cells that ``n_batches`` elements of box ``extent`` (3 numbers) need in the largest elastic step of the pipeline, however
+        the steps in front of it turn the cloud (they may scale it, by ``LinearAug``'s largest factor, and rotate it, so every axis
+        is given the scaled diagonal): a host-side upper bound for ``grid_capacity``, 0 without an elastic step."""
+        diag = float(np.sqrt(sum(float(e) ** 2 for e in extent)))
+        cells = 0
+        for at, aug in enumerate(self.pipeline_):
+            if aug.kind_ != "elastic":
+                continue
+            scale = 1.0
+            for prev in self.pipeline_[:at]:
+                if prev.kind_ == "linear":
+                    factors = [prev.min_a_, prev.max_a_] if prev.a_values_ is None else prev.a_values_
+                    scale *= max(float(np.max(np.abs(v))) for v in factors)
+                elif prev.kind_ == "stdnorm":
+                    raise ValueError("elastic_capacity: STDDevNormAug in front of ElasticDistortionAug rescales the cloud by its own "
+                                     "statistics; size grid_capacity by hand")
+                elif prev.kind_ == "elastic":
+                    scale *= 1.0 + sum(abs(float(m)) for m in prev.magnitude_)   # (|blurred normal| < 1 in all but vanishing cases)
+            cells = max(cells, sum((int(diag * scale / float(g)) + 4) ** 3 for g in aug.granularity_))
+        return cells * int(n_batches)
+
     def augment_batch(self, pts, batch_ids, n_batches: int, extra_tensors: Sequence = (), n_valid=None, seed: Optional[int] = None,
                       seed_tensor=None, draws=None, grid_capacity=None) -> AugmentedBatch:
         """Augment every element of a batch on its own.  ``pts [n_rows, 3]`` float32 and ``batch_ids [n_rows]`` int32 (sorted)
         on the GPU, ``n_valid`` the device word of a padded cloud; ``draws [steps, n_batches, AUG_DRAWS]`` uniform numbers
         (``torch.rand`` on the device when None); ``seed`` (drawn when None) plus the device word ``seed_tensor`` key the hashed
         numbers of ``NoiseAug`` and ``DropAug``, so a captured call draws fresh ones when the word changes between replays.
-        No host synchronisation; capturable.  ``grid_capacity`` belongs to the elastic step and is ignored."""
+        No host synchronisation; capturable.  ``grid_capacity``: the cells of the noise grids of ONE ``ElasticDistortionAug``
+        step over the whole batch (all elements, all octaves; 16 bytes each); required when the pipeline holds that step, not
+        looked at otherwise.  Elements that do not fit stay as they are and set bit 0 of ``overflow_``."""
         dev, n = _cloud(pts, batch_ids, "augment_batch")
         steps = len(self.pipeline_)
+        if any(a.kind_ == "elastic" for a in self.pipeline_) and (grid_capacity is None or int(grid_capacity) < 0):
+            raise ValueError("augment_batch: the pipeline holds ElasticDistortionAug, which needs grid_capacity (cells of its noise grids)")
         if draws is None:
             draws = torch.rand((steps, n_batches, AUG_DRAWS), dtype=torch.float32, device=dev)
         if tuple(draws.shape) != (steps, n_batches, AUG_DRAWS):
@@ -347,7 +460,7 @@ class AugPipeline:
             if not isinstance(e, torch.Tensor) or not e.is_cuda:
                 raise ValueError("extra tensors: expected GPU tensors (the HIP path has no CPU fallback)")
         table, etables, idx, last = None, [None] * len(extras), None, None
-        cropped = [False] * len(extras)
+        cropped, overflow = [False] * len(extras), None
         # An extra tensor follows the points' rows only through the removing steps it is flagged for (CropPtsAug.py:67-69 and
         # the like leave the others at their length), so each carries the ids and the count of ITS rows: its pending table is
         # written with those, whatever has happened to the points since.  `in_step`: it has been through every compaction.
@@ -398,6 +511,13 @@ class AugPipeline:
                     extras[i] = aug_apply(extras[i], batch_ids, n_batches, etables[i], False,
                                           (draws[step], aug.prob_, aug.stddev_, aug.clip_, aug.stddev_), seed, seed_tensor, step, None, n_valid)
                     etables[i] = None
+            elif aug.kind_ == "elastic":   # (the extra tensors stay as they are, whatever their flags)
+                write_points()
+                counts, stats = aug_stats(pts, batch_ids, n_batches, None, n_valid)
+                gtab, word, ws = aug_elastic_plan(counts, stats, draws[step], aug.prob_, aug.granularity_, grid_capacity)
+                grid = aug_elastic_grids(gtab, ws, grid_capacity, seed, seed_tensor, step)
+                pts = aug_elastic_displace(pts, batch_ids, n_batches, stats, gtab, aug.magnitude_, grid, n_valid)
+                overflow = word if overflow is None else torch.bitwise_or(overflow, word)
             else:
                 write_points()
                 stats = aug_stats(pts, batch_ids, n_batches, None, n_valid)[1] if aug.kind_ == "crop_box" else None
@@ -424,18 +544,24 @@ class AugPipeline:
         write_points()
         for i in range(len(extras)):
             write_extra(i)
-        return AugmentedBatch(pts, batch_ids, n_valid, idx, extras, last, cropped, evalid)
+        return AugmentedBatch(pts, batch_ids, n_valid, idx, extras, last, cropped, evalid, overflow)
 
     def augment(self, p_tensor, p_extra_tensors=[]):
         """The reference's signature for ONE cloud: a batch of one, trimmed tensors back, ``(aug_tensor, params, extras)`` with
         an empty parameter list (the draws stay on the device).  When the pipeline removes points this reads the surviving
         count back (and the count of an extra tensor that was left out of a later removing step): the one host synchronisation
-        of this module."""
+        of this module.  A pipeline that holds ``ElasticDistortionAug`` has one more: the cloud's box is read back once, in
+        front of everything, to size the grid (``elastic_capacity``)."""
         if not isinstance(p_tensor, torch.Tensor) or not p_tensor.is_cuda:
             raise ValueError("augment: expected a GPU tensor (the HIP path has no CPU fallback)")
         pts = ops._as(p_tensor, torch.float32)
         ids = torch.zeros(pts.shape[0], dtype=torch.int32, device=pts.device)
-        res = self.augment_batch(pts, ids, 1, [e.contiguous() for e in p_extra_tensors])
+        cap = None
+        if any(a.kind_ == "elastic" for a in self.pipeline_) and pts.shape[0] > 0:
+            cap = self.elastic_capacity((pts.amax(0) - pts.amin(0)).cpu().tolist())
+        elif any(a.kind_ == "elastic" for a in self.pipeline_):
+            cap = 0
+        res = self.augment_batch(pts, ids, 1, [e.contiguous() for e in p_extra_tensors], grid_capacity=cap)
         if res.n_valid_ is None:
             return res.pts_, [], res.extra_tensors_
         counts = {}   # one read-back per distinct word: an extra tensor left out of a later crop keeps its own, longer count

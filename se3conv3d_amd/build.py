@@ -24,7 +24,7 @@ SUFFIX = os.environ.get("SE3_LIB_SUFFIX", "")
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj" + SUFFIX) if SUFFIX else LIBDIR
 LIB = os.path.join(LIBDIR, f"libse3conv_hip{SUFFIX}.so")
-SOURCES = ["geometry.hip", "edge_kernels.hip", "edge_bf16.hip", "edge_dx.hip", "gemm.hip", "gemm_bf16.hip", "prep.hip", "frames.hip", "glue.hip", "fps.hip", "knn_edges.hip", "global_pool.hip", "group_norm.hip", "seg_head.hip", "pne.hip", "basis_att.hip", "att_fused.hip", "augment.hip", "optim.hip", "api.hip"]
+SOURCES = ["geometry.hip", "edge_kernels.hip", "edge_bf16.hip", "edge_dx.hip", "gemm.hip", "gemm_bf16.hip", "prep.hip", "frames.hip", "glue.hip", "fps.hip", "knn_edges.hip", "global_pool.hip", "group_norm.hip", "seg_head.hip", "pne.hip", "basis_att.hip", "att_fused.hip", "augment.hip", "optim.hip", "elastic.hip", "api.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "edge_bf16_body.h")] + [
     os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.TABLES]  # every header of the pinned C surface
 ADDED_HEADERS = [os.path.join(os.path.dirname(PKG), "include", name) for name in _lib.ADDED_TABLES]  # ... and those added since
